@@ -12,16 +12,21 @@ downloaded), bf16 (or ``--dtype fp8`` weights).
     torchrun --nproc-per-node 8 bench.py --gpus 8     # 8 DP replicas of one GPU each (dp8)
     torchrun --nproc-per-node 8 bench.py --gpus 8 --tp 2   # BASELINE config 4: 4 replicas x TP2 (tp2dp4)
 
+A plain run sets up, warms up, times ``--steps`` steps and prints the result line; ``--dump-outputs DIR`` also
+writes what the last timed step returned (the generated token ids, ``DIR/token_ids.npy``, float64, one row per
+request; prompts and weights are seeded, so two runs with the same arguments see identical inputs).  Everything
+else runs only with ``--full``:
+
 Before the timed region the decode path is checked at the benchmark's batch (``eval/numerics.py``): the batch
 is decoded greedily for 64 steps with each step's logits recorded, and two of its sequences are fed, with the
 engine's own tokens, through the plain fp32 PyTorch forward over the same (for TP: the unsharded) weights
 (``models.llama.reference_forward``, emulating fp8 quantisation where the engine quantises); mean KL, top-1 and
 top-5 agreement over the 64 positions are reported as ``numerics``.
 
-One-GPU runs then also time, untimed by the headline (after its region), BASELINE config 2 (the same model at
-batch 1: ``p50_e2e_latency_s_b1``, ``decode_device_ms_per_step_b1``) and config 3 (Llama-3.2-3B /explain_error
+One-GPU ``--full`` runs then also time, untimed by the headline (after its region), BASELINE config 2 (the same
+model at batch 1: ``p50_e2e_latency_s_b1``, ``decode_device_ms_per_step_b1``) and config 3 (Llama-3.2-3B /explain_error
 with a 2k-token prompt, batch 1: ``explain_2k_p50_e2e_latency_s``, ``explain_2k_device_ms_per_step``), each with
-its own teacher-forced numerics check (``--no-extras`` skips them).
+its own teacher-forced numerics check (``--full --no-extras`` keeps the headline's numerics check and skips them).
 
 Prints ONE JSON line on rank 0.  ``value`` = whole-job output tokens/s (sum over replicas, timed by
 the slowest rank); ``vs_baseline`` = value / 4.0 tok/s, the only throughput figure BASELINE.md
@@ -186,6 +191,16 @@ def comm_record(tpg, world: int, tp: int, device) -> dict:
     return out
 
 
+def dump_outputs(out_dir: str, results, rank: int, world: int) -> None:
+    """What a caller of the timed path received in its last step: the generated token ids, one row per request
+    (every request emits exactly ``--new-tokens`` tokens), as float64 (ids are exact)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    ids = np.asarray([r.token_ids for r in results], dtype=np.float64)
+    np.save(os.path.join(out_dir, "token_ids.npy" if world == 1 else f"token_ids_rank{rank}.npy"), ids)
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -204,9 +219,15 @@ def main() -> int:
     ap.add_argument("--no-graphs", action="store_true")
     ap.add_argument("--cpu-rehearsal", action="store_true",
                     help="run the same bench flow on CPU over gloo (tests of the multi-rank path; not a measurement)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the teacher-forced numerics check before the "
+                         "warm-up and, on one-GPU-per-replica GPU benches, the untimed BASELINE config 2 (batch 1) / "
+                         "config 3 (3B 2k explain) rounds after the timed region")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the untimed BASELINE config 2 (batch 1) / config 3 (3B 2k explain) rounds after the "
-                         "timed region (they run on one-GPU-per-replica GPU benches by default)")
+                    help="with --full: skip the untimed BASELINE config 2 / config 3 rounds (numerics check only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's outputs as DIR/<name>.npy (token_ids: "
+                         "float64 [batch, new_tokens]; multi-rank runs write token_ids_rank<R>.npy per rank)")
     ap.add_argument("--set", action="append", default=[], metavar="NAME=VALUE",
                     help="experiment override (A/B runs; reported as 'overrides'): a ModelRunner attribute, or "
                          "ops.NAME for a module constant of ops, e.g. --set fused_norm_max_batch=32")
@@ -258,8 +279,11 @@ def main() -> int:
         assert all(r.eval_count == args.new_tokens for r in res), [r.eval_count for r in res]
         return res
 
-    # numerics before the warm-up: a teacher-forced decode of the same batch, >= 64 steps when the run has them
-    numerics = numerics_check(eng, prompts, min(64, args.new_tokens - 1), rank == 0, tp, args.model, args.dtype, device)
+    # numerics before the warm-up (--full): a teacher-forced decode of the same batch, >= 64 steps when the run has them
+    numerics = None
+    if args.full:
+        numerics = numerics_check(eng, prompts, min(64, args.new_tokens - 1), rank == 0, tp, args.model, args.dtype,
+                                  device)
     for i in range(args.warmup):
         one_step()
     eng.stats.update(decode_s=0.0, decode_steps=0, prefill_s=0.0, decode_device_s=0.0)  # timed rounds only
@@ -268,9 +292,10 @@ def main() -> int:
     sync()
     lat = []
     t0 = time.perf_counter()
+    last = None
     for _ in range(args.steps):
         s = time.perf_counter()
-        one_step()
+        last = one_step()
         lat.append(time.perf_counter() - s)
     sync()
     if world > 1:
@@ -290,19 +315,18 @@ def main() -> int:
     tp_comm = comm_record(tpg, world, tp, device) if world > 1 else None
     decode_ms_tok = 1000.0 * eng.stats["decode_s"] / max(1, eng.stats["decode_steps"])
     decode_dev_ms = 1000.0 * eng.stats["decode_device_s"] / max(1, eng.stats["decode_steps"])
+    dtype_label = (args.dtype if args.dtype == "bf16" else fp8_label(eng.runner, args.batch)) \
+        + ("; fp8 e4m3 KV cache" if eng.runner.kv_fp8 else "")
+    if args.dump_outputs and last is not None:
+        dump_outputs(args.dump_outputs, last, rank, world)
     extras = {}
-    if world == 1 and not cpu and not args.no_extras:
+    if args.full and world == 1 and not cpu and not args.no_extras:
         extras.update(batch1_round(eng, prompts[0], args))
-        dtype_label = (args.dtype if args.dtype == "bf16" else fp8_label(eng.runner, args.batch)) \
-            + ("; fp8 e4m3 KV cache" if eng.runner.kv_fp8 else "")
         del eng
         gc.collect()
         torch.cuda.empty_cache()
         extras.update(explain_round(device))
         eng = None
-    else:
-        dtype_label = (args.dtype if args.dtype == "bf16" else fp8_label(eng.runner, args.batch)) \
-            + ("; fp8 e4m3 KV cache" if eng.runner.kv_fp8 else "")
     if rank == 0:
         ref_p50 = REF_P50_S_LLAMA if args.model.startswith("llama") else REF_P50_S
         par = f"dp{dp}" if tp == 1 else f"tp{tp}dp{dp}"
@@ -333,7 +357,7 @@ def main() -> int:
             "decode_ms_per_token_step": round(decode_ms_tok, 3),
             "decode_device_ms_per_step": round(decode_dev_ms, 3),
             "per_gpu_tokens_per_sec": round(value / world, 2),
-            "numerics": numerics,
+            **({"numerics": numerics} if args.full else {}),
             **({"tp_comm": tp_comm} if tp_comm is not None else {}),
             **({"overrides": overrides} if overrides else {}),
             **extras,

@@ -1,6 +1,7 @@
 #!/bin/bash
 # Interleaved A/B of env-knob settings on ONE box: scripts/ab_env.sh <rounds> "<ENV=.. ENV=..>" "<...>" -- [bench args]
 # Each setting runs bench.py once per round (settings interleaved round by round); one summary line per run.
+# Pass --full among the bench args for the numerics check and the batch-1 / 3B 2k explain figures in the summary.
 export TMPDIR=/tmp
 cd "$(dirname "$0")/.."
 mkdir -p gpurun_out/benches

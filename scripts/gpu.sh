@@ -27,7 +27,7 @@ job() {
       timeout -k 10 200 python -u __graft_entry__.py smoke > gpurun_out/smoke.log 2>&1 \
         || { tail -n 20 gpurun_out/smoke.log; return 2; }
       tail -n 1 gpurun_out/smoke.log
-      job bench default ;;
+      job bench default --full ;;
     bench)
       local name=$1; shift
       timeout -k 10 500 python -u bench.py "$@" > gpurun_out/benches/$name.log 2>&1

@@ -39,7 +39,7 @@ def _run(nproc: int, extra=()):
 @pytest.mark.parametrize("nproc,extra,par,batch", [(1, (), "dp1", 3), (2, (), "dp2", 6), (2, ("--tp", "2"), "tp2dp1", 3),
                                                  (4, ("--tp", "2"), "tp2dp2", 6)])
 def test_bench_contract_cpu(nproc, extra, par, batch):
-    d = _run(nproc, extra)
+    d = _run(nproc, (*extra, "--full"))  # --full: the numerics check asserted below
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config"):
         assert k in d, k
@@ -61,3 +61,22 @@ def test_bench_contract_cpu(nproc, extra, par, batch):
             assert calls.get("gloo_all_gather_float32", 0) > 0, calls  # vocab-parallel logits
     else:
         assert "tp_comm" not in d
+
+
+def test_bench_plain_run_dumps_last_step_outputs(tmp_path):
+    """A plain run (no --full) carries the headline keys alone, and --dump-outputs writes the last timed step's
+    token ids: one float64 row of --new-tokens ids per request, identical from run to run (seeded inputs)."""
+    import numpy as np
+
+    dumps = []
+    for name in ("a", "b"):
+        d = _run(1, ("--dump-outputs", str(tmp_path / name)))
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in d, k
+        assert d["steps"] == 2 and d["ms_per_step"] > 0
+        assert "numerics" not in d and "numerics_b1" not in d and "explain_2k_ttft_s" not in d
+        assert sorted(p.name for p in (tmp_path / name).iterdir()) == ["token_ids.npy"]
+        dumps.append(np.load(tmp_path / name / "token_ids.npy"))
+    assert dumps[0].dtype == np.float64 and dumps[0].shape == (3, 4)
+    assert (dumps[0] == np.round(dumps[0])).all() and (dumps[0] >= 0).all()
+    assert np.array_equal(dumps[0], dumps[1])

@@ -1,4 +1,6 @@
 """Byte-level prompt contracts, executor semantics and the eval harness metrics (CPU)."""
+import hashlib
+import json
 import os
 
 import pytest
@@ -10,7 +12,7 @@ from llm_based_apache_spark_optimization_amd.runtime import native
 from llm_based_apache_spark_optimization_amd.serving.executor import (SQLExecutionError, SqliteExecutor,
                                                                       clean_sql, infer_spark_type, read_csv)
 
-REF = "/root/reference/Model_Evaluation_&_Comparision.py"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_eval_strings.json")
 
 
 def test_nl2sql_prompt_contract():
@@ -27,17 +29,17 @@ def test_explain_prompt_contract():
                                       "Provide clear, concise solutions.")
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="reference tree not mounted")
 def test_eval_strings_byte_identical_to_reference():
-    src = open(REF).read()
-    exp = src[src.index('EXPECTED_SQL = """') + 18:src.index('""".strip()')].strip()
-    assert exp == prompts.EVAL_EXPECTED_SQL
-    i = src.index('system="""') + 10
-    assert src[i:src.index('""",', i)] == prompts.EVAL_SINGLE_SYSTEM
-    i = src.index('system="Here') + 8
-    assert src[i:src.index('",', i)] == prompts.EVAL_MULTI_SYSTEM
+    """Against SHA-256 digests recorded from the reference's evaluation script (tests/golden): its expected SQL,
+    its two system prompts, and the digest of every string literal in it (the four-query set's members)."""
+    gold = json.load(open(GOLDEN))
+    sha = lambda s: hashlib.sha256(s.encode()).hexdigest()  # noqa: E731
+    assert sha(prompts.EVAL_EXPECTED_SQL) == gold["expected_sql_sha256"]
+    assert sha(prompts.EVAL_SINGLE_SYSTEM) == gold["single_system_sha256"]
+    assert sha(prompts.EVAL_MULTI_SYSTEM) == gold["multi_system_sha256"]
+    literals = set(gold["string_literal_sha256"])
     for q in prompts.EVAL_QUERIES:
-        assert f'"{q["nl"]}"' in src and f'"{q["expected_sql"]}"' in src
+        assert sha(q["nl"]) in literals and sha(q["expected_sql"]) in literals
 
 
 def test_levenshtein_native():
