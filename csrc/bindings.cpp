@@ -55,6 +55,15 @@ int lsa_attn_prefill(const void* q, const void* kc, const void* vc, const int* b
 int lsa_argmax_commit(const float* logits, int B, int V, unsigned long long* part, int* out_tokens, int max_new,
                       int* gen_len, int* input_ids, int* positions, int* finished, const int* eos, int neos,
                       const int* limit, const int* eos_on, hipStream_t s);
+int lsa_attn_verify(const void* q, const void* kc, const void* vc, const int* bt, int max_blocks, const int* pos0, int T,
+                    int H, int Hkv, float scale, int chunk_blocks, int nsplit, int unsplit_max, void* out, float* opart,
+                    float* mlpart, int* counters, hipStream_t s);
+int lsa_spec_draft(const int* prompt_tok, int prompt_ld, const int* prompt_len, const int* out_tokens, int max_new,
+                   const int* gen_len, const int* input_ids, const int* positions, int rows, int k, int n_max, int n_min,
+                   const int* forced, int nf, int* spec_ids, int* spec_pos, int* spec_draft, hipStream_t s);
+int lsa_spec_commit(const float* logits, int T, int V, unsigned long long* part, const int* draft, long long* stats,
+                    int* out_tokens, int max_new, int* gen_len, int* input_ids, int* positions, int* finished,
+                    const int* eos, int neos, const int* limit, const int* eos_on, hipStream_t s);
 int lsa_sample_commit(float* logits, int B, int V, unsigned long long* part, unsigned long long* cand, int* hist,
                       int window, const float* penalty, const int* last_n, const float* temperature, const int* top_k,
                       const float* top_p, const unsigned long long* seeds, int* out_tokens, int max_new, int* gen_len,
@@ -867,6 +876,91 @@ void argmax_commit(const at::Tensor& logits, at::Tensor& part, at::Tensor& out_t
         "argmax_commit");
 }
 
+// speculative decoding: attention of the T = k + 1 verify rows of one sequence (kernels/attention_verify.hip)
+void attn_verify(const at::Tensor& q, const at::Tensor& kc, const at::Tensor& vc, const at::Tensor& block_table,
+                 const at::Tensor& pos0, int64_t H, int64_t Hkv, double scale, int64_t chunk_blocks, int64_t nsplit,
+                 int64_t unsplit_max, at::Tensor& out, at::Tensor& opart, at::Tensor& mlpart, at::Tensor& counters) {
+  need(q, at::kBFloat16, "q");
+  need(out, at::kBFloat16, "out");
+  check_cache(kc, vc, c10::nullopt, c10::nullopt);
+  need(pos0, at::kInt, "pos0");
+  need(block_table, at::kInt, "block_table");
+  TORCH_CHECK(q.dim() == 3 && q.size(1) == H && q.size(2) == 128 && q.is_contiguous(), "q: contiguous [T, H, 128]");
+  const int64_t T = q.size(0);
+  TORCH_CHECK(H > 0 && Hkv > 0 && H % Hkv == 0 && kc.size(1) == Hkv, "heads: H % Hkv == 0, cache has Hkv heads");
+  TORCH_CHECK(T >= 1 && T <= 8 && T * (H / Hkv) <= 16, "attn_verify: T <= 8 and T * H / Hkv <= 16 query rows per kv head");
+  TORCH_CHECK(pos0.numel() >= 1, "pos0: one int32");
+  TORCH_CHECK(block_table.is_contiguous() && block_table.numel() >= 1 && (block_table.dim() == 1 || block_table.size(0) == 1),
+              "block_table: one contiguous row [max_blocks]");
+  TORCH_CHECK(out.is_contiguous() && out.numel() >= T * H * 128, "attn_verify out too small");
+  TORCH_CHECK(nsplit >= 1 && nsplit <= 256 && chunk_blocks >= 1, "attn_verify: 1 <= nsplit <= 256, chunk_blocks >= 1");
+  need(opart, at::kFloat, "opart");
+  need(mlpart, at::kFloat, "mlpart");
+  need(counters, at::kInt, "counters");
+  TORCH_CHECK(opart.numel() >= T * H * nsplit * 128 && mlpart.numel() >= T * H * nsplit * 2 && counters.numel() >= Hkv,
+              "attn_verify workspace too small");
+  TORCH_CHECK(opart.numel() * 4 < 0x7fffffffLL, "opart must stay below 2 GiB (buffer descriptor range)");
+  check(lsa_attn_verify(q.data_ptr(), kc.data_ptr(), vc.data_ptr(), block_table.data_ptr<int>(), block_table.numel(),
+                        pos0.data_ptr<int>(), T, H, Hkv, (float)scale, chunk_blocks, nsplit, (int)unsplit_max,
+                        out.data_ptr(), opart.data_ptr<float>(), mlpart.data_ptr<float>(), counters.data_ptr<int>(),
+                        cur_stream()),
+        "attn_verify");
+}
+
+// speculative decoding: the prompt-lookup drafter (kernels/spec.hip); rows = prompt_len.numel()
+void spec_draft(const at::Tensor& prompt_tok, const at::Tensor& prompt_len, const at::Tensor& out_tokens,
+                const at::Tensor& gen_len, const at::Tensor& input_ids, const at::Tensor& positions, int64_t k,
+                int64_t n_max, int64_t n_min, const c10::optional<at::Tensor>& forced, const at::Tensor& spec_ids,
+                const at::Tensor& spec_pos, const at::Tensor& spec_draft_out) {
+  const int64_t rows = prompt_len.numel();
+  for (const at::Tensor* t : {&prompt_tok, &prompt_len, &out_tokens, &gen_len, &input_ids, &positions, &spec_ids,
+                              &spec_pos, &spec_draft_out}) {
+    need(*t, at::kInt, "spec_draft operand");
+    TORCH_CHECK(t->is_contiguous(), "spec_draft operands must be contiguous");
+  }
+  TORCH_CHECK(rows >= 1 && k >= 1 && k <= 255 && n_max >= 1 && n_min >= 1 && n_min <= n_max,
+              "spec_draft: rows >= 1, 1 <= k <= 255, 1 <= n_min <= n_max");
+  TORCH_CHECK(prompt_tok.dim() == 2 && prompt_tok.size(0) >= rows && out_tokens.dim() == 2 && out_tokens.size(0) >= rows,
+              "spec_draft: prompt_tok [rows, max_len], out_tokens [rows, max_new]");
+  TORCH_CHECK(gen_len.numel() >= rows && input_ids.numel() >= rows && positions.numel() >= rows,
+              "spec_draft: state rows");
+  TORCH_CHECK(spec_ids.numel() >= rows * (k + 1) && spec_pos.numel() >= rows * (k + 1) && spec_draft_out.numel() >= rows * k,
+              "spec_draft outputs too small");
+  int64_t nf = 0;
+  if (forced.has_value()) {
+    need(*forced, at::kInt, "forced");
+    TORCH_CHECK(forced->is_contiguous() && forced->numel() >= k && forced->numel() % k == 0, "forced: contiguous [nf, k]");
+    nf = forced->numel() / k;
+  }
+  check(lsa_spec_draft(prompt_tok.data_ptr<int>(), prompt_tok.size(1), prompt_len.data_ptr<int>(),
+                       out_tokens.data_ptr<int>(), out_tokens.size(1), gen_len.data_ptr<int>(), input_ids.data_ptr<int>(),
+                       positions.data_ptr<int>(), rows, k, n_max, n_min, ptr<const int>(forced), nf,
+                       spec_ids.data_ptr<int>(), spec_pos.data_ptr<int>(), spec_draft_out.data_ptr<int>(), cur_stream()),
+        "spec_draft");
+}
+
+// speculative decoding: argmax of the T verify rows + in-order commit of the accepted run into state row 0
+void spec_commit(const at::Tensor& logits, at::Tensor& part, const at::Tensor& draft, at::Tensor& stats,
+                 at::Tensor& out_tokens, at::Tensor& gen_len, at::Tensor& input_ids, at::Tensor& positions,
+                 at::Tensor& finished, const at::Tensor& eos, const at::Tensor& limit, const at::Tensor& eos_on) {
+  need(logits, at::kFloat, "logits");
+  TORCH_CHECK(logits.dim() == 2 && logits.is_contiguous() && logits.size(0) >= 2, "logits: contiguous [T >= 2, V]");
+  const int T = logits.size(0), V = logits.size(1);
+  check_state(1, out_tokens, gen_len, input_ids, positions, finished, eos, limit, eos_on);
+  need(part, at::kLong, "part");
+  TORCH_CHECK(part.numel() >= (int64_t)T * ((V + 4095) / 4096), "argmax partials too small");
+  need(draft, at::kInt, "draft");
+  need(stats, at::kLong, "stats");
+  TORCH_CHECK(draft.numel() >= T - 1 && draft.is_contiguous() && stats.numel() >= 3 && stats.is_contiguous(),
+              "spec_commit: draft [T - 1], stats [3]");
+  check(lsa_spec_commit(logits.data_ptr<float>(), T, V, reinterpret_cast<unsigned long long*>(part.data_ptr()),
+                        draft.data_ptr<int>(), reinterpret_cast<long long*>(stats.data_ptr<int64_t>()),
+                        out_tokens.data_ptr<int>(), out_tokens.size(1), gen_len.data_ptr<int>(),
+                        input_ids.data_ptr<int>(), positions.data_ptr<int>(), finished.data_ptr<int>(),
+                        eos.data_ptr<int>(), eos.numel(), limit.data_ptr<int>(), eos_on.data_ptr<int>(), cur_stream()),
+        "spec_commit");
+}
+
 void sample_commit(at::Tensor& logits, at::Tensor& part, at::Tensor& cand, const c10::optional<at::Tensor>& hist,
                    const c10::optional<at::Tensor>& penalty, const c10::optional<at::Tensor>& last_n,
                    const at::Tensor& temperature, const at::Tensor& top_k,
@@ -1091,6 +1185,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("out"), py::arg("rows32") = 0, py::arg("xf_mt") = 0);
   m.def("argmax_commit", &argmax_commit);
   m.def("sample_commit", &sample_commit);
+  m.def("attn_verify", &attn_verify, py::arg("q"), py::arg("kc"), py::arg("vc"), py::arg("block_table"),
+        py::arg("pos0"), py::arg("H"), py::arg("Hkv"), py::arg("scale"), py::arg("chunk_blocks"), py::arg("nsplit"),
+        py::arg("unsplit_max"), py::arg("out"), py::arg("opart"), py::arg("mlpart"), py::arg("counters"));
+  m.def("spec_draft", &spec_draft, py::arg("prompt_tok"), py::arg("prompt_len"), py::arg("out_tokens"),
+        py::arg("gen_len"), py::arg("input_ids"), py::arg("positions"), py::arg("k"), py::arg("n_max"), py::arg("n_min"),
+        py::arg("forced"), py::arg("spec_ids"), py::arg("spec_pos"), py::arg("spec_draft"));
+  m.def("spec_commit", &spec_commit);
   m.def("fp8_dequant", &fp8_dequant);
   m.def("quant_rows_fp8", &quant_rows_fp8);
   m.def("fp8_gemm_t256", &fp8_gemm_t256, py::arg("x8"), py::arg("sx"), py::arg("wq"), py::arg("sw"), py::arg("N"),

@@ -248,6 +248,55 @@ extern "C" int lsa_argmax_commit(const float* logits, int B, int V, unsigned lon
   return (int)hipGetLastError();
 }
 
+// Speculative decoding (spec.hip drafts): logits [T, V] are the T = k + 1 verify rows of ONE sequence (state row 0
+// of st).  tok_i = argmax(logits[i]); a = the number of leading i < k with draft[i] == tok_i (a -1 draft never
+// matches); tok_0 .. tok_a are committed in order through commit_token, so nothing follows a finishing token (EOS /
+// length).  stats[3] += (1 step, drafts >= 0, tokens committed beyond the first).  A finished row changes nothing.
+__global__ __launch_bounds__(64) void spec_commit_kernel(const unsigned long long* __restrict__ part, int nch, int k,
+                                                         const int* __restrict__ draft, long long* __restrict__ stats,
+                                                         DecodeState st) {
+  int tok = 0;
+  bool run = true;  // tok_0 .. tok_{i-1} matched their drafts
+  int committed = 0, drafted = 0;
+  const bool live = !st.finished[0];
+  for (int i = 0; i <= k; ++i) {
+    unsigned long long best = 0ull;
+    for (int c = threadIdx.x; c < nch; c += 64) {
+      const unsigned long long key = part[(size_t)i * nch + c];
+      best = key > best ? key : best;
+    }
+    best = wave_max_u64(best);
+    tok = (int)(0xffffffffu - (uint32_t)(best & 0xffffffffull));
+    if (threadIdx.x == 0 && run && live && !st.finished[0]) {
+      commit_token(st, 0, tok);
+      ++committed;
+    }
+    if (i < k) {
+      const int d = draft[i];
+      drafted += d >= 0;
+      run = run && d >= 0 && d == tok;
+    }
+  }
+  if (threadIdx.x == 0 && live) {
+    stats[0] += 1;
+    stats[1] += drafted;
+    stats[2] += committed > 0 ? committed - 1 : 0;
+  }
+}
+
+extern "C" int lsa_spec_commit(const float* logits, int T, int V, unsigned long long* part, const int* draft,
+                               long long* stats, int* out_tokens, int max_new, int* gen_len, int* input_ids,
+                               int* positions, int* finished, const int* eos, int neos, const int* limit,
+                               const int* eos_on, hipStream_t s) {
+  if (T < 2) return -1;
+  const int chunk = 4096;
+  const int nch = (V + chunk - 1) / chunk;
+  hipLaunchKernelGGL(argmax_partial_kernel, dim3(nch, T), dim3(256), 0, s, logits, V, chunk, part, nch);
+  DecodeState st{out_tokens, max_new, gen_len, input_ids, positions, finished, eos, neos, limit, eos_on, nullptr, 0};
+  hipLaunchKernelGGL(spec_commit_kernel, dim3(1), dim3(64), 0, s, part, nch, T - 1, draft, stats, st);
+  return (int)hipGetLastError();
+}
+
 // workspace: part (B * ceil(V/4096) u64) + cand (B * ceil(V/2048) * 64 u64)
 extern "C" int lsa_sample_commit(float* logits, int B, int V, unsigned long long* part, unsigned long long* cand,
                                  int* hist, int window, const float* penalty, const int* last_n,

@@ -45,6 +45,11 @@ class Settings:
     explain_dtype: str = dataclasses.field(default_factory=lambda: _env("EXPLAIN_DTYPE", "bf16"))
     # paged KV cache dtype of every engine: "bf16" | "fp8" (e4m3 rows + per-row scales, ops.KV_FP8)
     kv_dtype: str = dataclasses.field(default_factory=lambda: _env("KV_DTYPE", "bf16"))
+    # prompt-lookup speculative decoding for batch-1 greedy requests: tokens drafted per verify step (0 = off; 3 works
+    # for every served model), and the acceptance guard's break-even (accepted drafts per verify step below which a
+    # request falls back to plain steps; < 0 = the runner's default)
+    spec_tokens: int = dataclasses.field(default_factory=lambda: _env("SPEC_TOKENS", 0, int))
+    spec_min_accept: float = dataclasses.field(default_factory=lambda: _env("SPEC_MIN_ACCEPT", -1.0, float))
     tp: int = dataclasses.field(default_factory=lambda: _env("TP", 1, int))
     dp: int = dataclasses.field(default_factory=lambda: _env("DP", 1, int))
     max_batch: int = dataclasses.field(default_factory=lambda: _env("MAX_BATCH", 32, int))

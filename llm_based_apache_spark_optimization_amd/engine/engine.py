@@ -54,6 +54,9 @@ class SamplingParams:
     repeat_last_n: int = 64
     num_ctx: Optional[int] = None     # Ollama context window (prompt + generated tokens); None = model's
     num_keep: int = 4
+    # prompt-lookup speculative decoding, where the engine runs it (LLMEngine(spec_tokens > 0), greedy, batch 1);
+    # the Ollama option extension "speculate": false opts a request out.  The tokens are the same either way.
+    speculate: bool = True
 
     @property
     def needs_sampler(self) -> bool:
@@ -76,7 +79,7 @@ class SamplingParams:
                               repeat_penalty=float(opts.get("repeat_penalty", 1.0)),
                               repeat_last_n=int(opts.get("repeat_last_n", 64)),
                               num_ctx=int(opts["num_ctx"]) if opts.get("num_ctx") else None,
-                              num_keep=int(opts.get("num_keep", 4)))
+                              num_keep=int(opts.get("num_keep", 4)), speculate=bool(opts.get("speculate", True)))
 
 
 @dataclasses.dataclass
@@ -101,6 +104,10 @@ class Request:
     # prompt_ids + resumed and its params.max_tokens the remaining budget
     resumed: list = dataclasses.field(default_factory=list)
     preemptions: int = 0
+    # speculative decoding: verify steps / accepted drafts of this request so far, and the acceptance guard's verdict
+    spec_steps: int = 0
+    spec_accepted: int = 0
+    spec_off: bool = False
 
     @property
     def ctx_ids(self) -> list:
@@ -123,8 +130,11 @@ class GenerationResult:
 
 class LLMEngine:
     def __init__(self, runner: ModelRunner, tokenizer=None, max_prefill_tokens: int = 16384, sync_every: int = 8,
-                 name: Optional[str] = None, prefill_chunk: Optional[int] = None, kv_reserve_tokens: int = BLOCK):
+                 name: Optional[str] = None, prefill_chunk: Optional[int] = None, kv_reserve_tokens: int = BLOCK,
+                 spec_tokens: int = 0):
         self.runner = runner
+        if spec_tokens:  # speculative decoding for batch-1 greedy requests (the runner clamps it to what it supports)
+            runner.spec_tokens = int(spec_tokens)
         self.spec = runner.spec
         self.name = name or self.spec.name
         self.tok = tokenizer or tokenizer_for(self.spec)
@@ -157,7 +167,8 @@ class LLMEngine:
         self.load_time_s = 0.0
         self.stats = {"requests": 0, "prompt_tokens": 0, "generated_tokens": 0, "decode_steps": 0,
                       "prefill_s": 0.0, "decode_s": 0.0, "decode_device_s": 0.0, "aborted": 0, "preempted": 0,
-                      "kv_grown_blocks": 0, "peak_running": 0}
+                      "kv_grown_blocks": 0, "peak_running": 0, "spec_steps": 0, "spec_drafted": 0, "spec_accepted": 0}
+        self._spec_seen = (0, 0, 0)  # runner.spec_counts() as of the last decode run
         # per-decode-run device timing (hipEvents around the graph replays, read after the host sync the
         # run ends with anyway): lsa_decode_step_device_seconds{model} = GPU time per token step
         self.device_timing = runner.on_gpu
@@ -258,14 +269,20 @@ class LLMEngine:
                 n_steps = remaining if self.run_ahead is None else min(self.run_ahead, remaining)
             else:
                 n_steps = min(self.sync_every, remaining)
-            if n_steps:
+            spec_T = self._spec_run(reqs, n_steps, remaining) if n_steps else 0
+            if spec_T:  # verify steps: each commits 1 .. spec_T tokens, so fewer cover the same budget
+                n_steps = min(n_steps, -(-remaining // spec_T))
+            elif n_steps:
                 reqs = self._grow_kv(reqs, n_steps)  # lazy KV: grow the tables for this run, preempting if needed
                 running = [q.rid for q in reqs]
                 if not reqs:
                     return []
             B = r.bucket(self.sched.highest_slot + 1)
             # host-side bound on every row's context during the run (selects the decode graph's split plan)
-            max_ctx = max(len(q.ctx_ids) + min(q.gen_host + n_steps, q.params.max_tokens) for q in reqs) + 1
+            if spec_T:
+                max_ctx = len(reqs[0].ctx_ids) + reqs[0].gen_host + n_steps * spec_T + spec_T
+            else:
+                max_ctx = max(len(q.ctx_ids) + min(q.gen_host + n_steps, q.params.max_tokens) for q in reqs) + 1
         # the decode run needs no scheduler state: new requests may be added meanwhile
         t0 = time.perf_counter()
         ev = None
@@ -273,13 +290,18 @@ class LLMEngine:
             if self.device_timing:
                 ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
                 ev[0].record()
-            r.decode(B, n_steps, sample, max_ctx=max_ctx)
+            if spec_T:
+                r.decode_spec(n_steps, max_ctx=max_ctx)
+            else:
+                r.decode(B, n_steps, sample, max_ctx=max_ctx)
             if ev is not None:
                 ev[1].record()
         fin, gl, _ = r.read_rows([q.slot for q in reqs])
         with self._lock:
             self.stats["decode_s"] += time.perf_counter() - t0
             self.stats["decode_steps"] += n_steps
+            if spec_T and n_steps:
+                self._spec_account(reqs[0])
             if ev is not None:
                 dev_s = ev[0].elapsed_time(ev[1]) / 1e3  # both recorded before read_rows' sync
                 self.stats["decode_device_s"] += dev_s
@@ -347,6 +369,50 @@ class LLMEngine:
             self.stats["kv_grown_blocks"] += sum(grown.values())
             self.runner.extend_tables([(self._reqs[rid].slot, self.sched.block_table(rid)) for rid in grown])
         return [q for q in reqs if q.rid in alive]
+
+    def _spec_run(self, reqs: list, n_steps: int, remaining: int) -> int:
+        """Whether this decode run is a run of verify steps (speculative decoding): returns T = drafted tokens + 1, or
+        0 for the plain run.  Verify steps need the runner's support (TP = 1, bf16 weights and KV cache), exactly one
+        running request, greedy, in slot 0 (decode bucket 1), that has not opted out or been dropped by the acceptance
+        guard; room for every position the run may write inside the model window; and the KV blocks of those
+        positions without preempting anyone: the worst case is T committed tokens per step plus T - 1 rows of
+        lookahead (also reserved so that a finished row, which rewrites its last T positions while the graph replays,
+        stays in its own blocks)."""
+        r = self.runner
+        if not (getattr(r, "spec_tokens", 0) > 0 and r.spec_supported()) or len(reqs) != 1:
+            return 0
+        q = reqs[0]
+        sp = q.params
+        if (q.slot != 0 or self.sched.highest_slot != 0 or self.sched.num_running != 1 or sp.needs_sampler
+                or not sp.speculate or q.spec_off):
+            return 0
+        T = r.spec_k() + 1
+        steps = min(n_steps, -(-remaining // T))
+        if len(q.ctx_ids) + q.gen_host + steps * T + T > r.max_model_len:
+            return 0
+        got = self.sched.grow(q.rid, len(q.ctx_ids) + q.gen_host - 1 + steps * T + T - 1)
+        if got < 0:
+            return 0
+        if got > 0:
+            self.stats["kv_grown_blocks"] += got
+            r.extend_tables([(q.slot, self.sched.block_table(q.rid))])
+        return T
+
+    def _spec_account(self, q: Request) -> None:
+        """Fold the runner's verify-step counters into the engine's and the request's; apply the acceptance guard: a
+        request whose accepted-per-step mean is below break-even after 16 verify steps takes plain steps from now on."""
+        now = self.runner.spec_counts()
+        d = [a - b for a, b in zip(now, self._spec_seen)]
+        self._spec_seen = now
+        for key, v in zip(("spec_steps", "spec_drafted", "spec_accepted"), d):
+            self.stats[key] += v
+        REGISTRY.inc("lsa_spec_steps_total", d[0], "speculative-decoding verify steps", model=self.name)
+        REGISTRY.inc("lsa_spec_drafted_tokens_total", d[1], "tokens drafted by the prompt-lookup drafter", model=self.name)
+        REGISTRY.inc("lsa_spec_accepted_tokens_total", d[2], "drafted tokens accepted by verification", model=self.name)
+        q.spec_steps += d[0]
+        q.spec_accepted += d[2]
+        if q.spec_steps >= 16 and q.spec_accepted / q.spec_steps < self.runner.spec_min_accept:
+            q.spec_off = True
 
     def _preempt(self, q: Request) -> None:
         """Release a running request's slot and KV blocks and re-queue it first; its generated tokens become part

@@ -47,8 +47,22 @@ class ModelRunner:
                  num_kv_blocks: Optional[int] = None, kv_memory_fraction: float = 0.85,
                  max_new_cap: Optional[int] = None, tp=None, use_graphs: bool = True,
                  fuse_rope: Optional[bool] = None, seq_parallel: Optional[bool] = None, sp_min_tokens: Optional[int] = None,
-                 kv_dtype: Optional[str] = None):
+                 kv_dtype: Optional[str] = None, spec_tokens: int = 0, spec_ngram: tuple = (3, 1)):
         self.w = weights
+        # prompt-lookup speculative decoding (``_verify_step``): tokens drafted per step (0 = off) and the drafter's
+        # (longest, shortest) n-gram.  Plain attributes: an experiment may set them on a built runner.
+        self.spec_tokens = int(spec_tokens)
+        self.spec_ngram = tuple(spec_ngram)
+        # acceptance guard of the engine: a request whose accepted-per-verify-step mean falls below this after 16
+        # verify steps takes plain steps for the rest of its life.  Break-even = verify-step time / plain-step time - 1.
+        # Measured on MI355X (scripts/bench_spec.py, profiles/spec/spec_decode_mi355x.jsonl; plain vs verify step, k = 3):
+        # duckdb-nsql-7B 128 + 128: 2.575 vs 2.845 ms -> 0.105; Llama-3.2-3B 2k + 128: 1.559 vs 1.828 ms -> 0.172
+        # (k = 1: 0.085 / 0.098; k = max: 0.133 at k = 7 / 0.224 at k = 4).  The default stays 0.0 = never drop until the
+        # guard has run against real (checkpoint) acceptance; set it per deployment (LSA_SPEC_MIN_ACCEPT).
+        self.spec_min_accept = 0.0
+        self._spec = None           # device buffers of the verify step (allocated on first use)
+        self._spec_forced = None    # [nf, k] int32 planted drafts (tests / a later drafter), see set_spec_forced
+        self._spec_clamp_logged = False
         # paged KV cache dtype: "bf16" or "fp8" (e4m3 rows with per-(token, kv-head) scales, ops.KV_FP8)
         kv_dtype = kv_dtype or ("fp8" if ops.KV_FP8 else "bf16")
         assert kv_dtype in ("bf16", "fp8"), kv_dtype
@@ -686,6 +700,190 @@ class ModelRunner:
         for _ in range(steps):
             g.replay()
 
+    # ------------------------------------------------------------------------------------ speculative decoding
+    def spec_k(self) -> int:
+        """Drafted tokens per verify step: ``spec_tokens`` clamped to what ``attn_verify`` takes (T = k + 1 <= 8
+        rows and T * G <= 16 query rows per kv head)."""
+        k = min(int(self.spec_tokens), 7, 16 // max(1, self.H // self.Hkv) - 1)
+        if 0 <= k < self.spec_tokens and not self._spec_clamp_logged:
+            self._spec_clamp_logged = True
+            import logging
+            logging.getLogger(__name__).warning("spec_tokens=%d clamped to %d (T <= 8, T * H / Hkv <= 16)",
+                                                self.spec_tokens, k)
+        return max(k, 0)
+
+    def spec_supported(self) -> bool:
+        """Whether this runner can run verify steps: TP = 1, bf16 weights, bf16 KV cache, at least one drafted token."""
+        tps = 1 if self.tp is None else self.tp.size
+        bf16 = ("bf16", "dense")  # packed for the GPU / plain on the CPU
+        return (self.spec_tokens > 0 and tps == 1 and not self.kv_fp8 and self.w.layers[0].wqkv.kind in bf16
+                and self.w.lm_head.kind in bf16 and self.spec_k() >= 1)
+
+    def _spec_bufs(self) -> dict:
+        """Device buffers of the verify step, sized for the largest T this runner can run (8 rows)."""
+        if self._spec is not None:
+            return self._spec
+        dev, TM = self.device, 8
+        i32 = dict(dtype=torch.int32, device=dev)
+        f32 = dict(dtype=torch.float32, device=dev)
+        bf = dict(dtype=torch.bfloat16, device=dev)
+        nqkv = (self.H + 2 * self.Hkv) * self.D
+        nsplit_max = max(4, ops.verify_split_plan(self.Hkv, self.max_model_len)[1])
+        self._spec = dict(
+            ctx=torch.zeros(1, self.max_model_len, **i32), ctx_len=torch.zeros(1, **i32),  # slot 0's prompt history
+            ids=torch.zeros(TM, **i32), pos=torch.zeros(TM, **i32), draft=torch.full((TM,), -1, **i32),
+            seq0=torch.zeros(TM, **i32), stats=torch.zeros(3, dtype=torch.int64, device=dev),
+            h=torch.zeros(TM, self.d, **f32), xn=torch.zeros(TM, self.d, **bf), q=torch.zeros(TM, self.H, self.D, **bf),
+            attn=torch.zeros(TM, self.H * self.D, **bf), act=torch.zeros(TM, self.ffn_l, **bf),
+            o_buf=torch.zeros(8 * TM * self.d, **f32), down_buf=torch.zeros(8 * TM * self.d, **f32),
+            qkv_buf=torch.zeros(8 * TM * nqkv, **f32), logits=torch.zeros(TM, self.Vl, **f32),
+            ssq=torch.zeros(2 * self.L + 2, TM, dtype=torch.int64, device=dev),
+            amax_part=torch.zeros(TM * ((self.V + 4095) // 4096), dtype=torch.int64, device=dev),
+            attn_ws=ops.verify_workspace(TM, self.H, self.Hkv, nsplit_max, dev))
+        return self._spec
+
+    def set_spec_forced(self, table: Optional[torch.Tensor]) -> None:
+        """Plant the drafts of the next verify steps instead of searching: ``table`` [nf, k] int32, a step whose row
+        has generated g tokens drafts row min(g, nf - 1) (None restores the n-gram search).  One device buffer per
+        table shape, rewritten in place: a captured verify graph is keyed by the buffer it reads."""
+        if table is None:
+            self._spec_forced = None
+            return
+        bufs = self.__dict__.setdefault("_spec_forced_bufs", {})
+        buf = bufs.get(tuple(table.shape))
+        if buf is None:
+            buf = bufs[tuple(table.shape)] = torch.zeros(tuple(table.shape), dtype=torch.int32, device=self.device)
+        buf.copy_(table.to(torch.int32))
+        self._spec_forced = buf
+
+    def _verify_step(self, plan: Optional[tuple] = None) -> None:
+        """One speculative-decoding step of the request in slot 0: a forward pass over T = k + 1 rows -- the row's input
+        token and k drafted tokens at positions p .. p + T - 1 -- and the in-order commit of the tokens greedy decoding
+        would have produced (``ops.spec_commit``): between 1 and T per step, the same sequence as plain steps.
+
+          spec_draft -> embed -> per layer: gemm qkv (f32 slabs) -> rope_append (RoPE + the T K/V rows into the cache)
+          -> attn_verify (all T rows share one pass over the cache) -> gemm o -> norm -> gemm gate_up -> gemm down
+          -> final norm -> lm_head over T rows -> spec_commit
+
+        KV invariant: a step writes cache positions p .. p + T - 1 and advances to p' = p + a + 1 (a accepted drafts).
+        The stale rows p' .. p + T - 1 lie inside the next step's write range p' .. p' + T - 1, so the next step (or
+        the next plain step, which writes p' before reading it) overwrites them before any query can see them: row t
+        sees only keys <= p' + t.  A finished row keeps its position and rewrites the same T positions when the graph
+        replays; the engine reserves those positions (LLMEngine._spec_run)."""
+        w, d, T = self.w, self.d, self.spec_k() + 1
+        sb = self._spec_bufs()
+        n_max, n_min = self.spec_ngram
+        st = (self.out_tokens[:1], self.gen_len[:1], self.input_ids[:1], self.positions[:1], self.finished[:1])
+        ids, pos, bt = sb["ids"][:T], sb["pos"][:T], self.block_tables[:1]
+        ops.spec_draft(sb["ctx"], sb["ctx_len"], st[0], st[1], st[2], st[3], T - 1, ids, pos, sb["draft"][:T - 1],
+                       n_max=n_max, n_min=n_min, forced=self._spec_forced)
+        h, xn, attn, act, q = sb["h"][:T], sb["xn"][:T], sb["attn"][:T], sb["act"][:T], sb["q"][:T]
+        nqkv = (self.H + 2 * self.Hkv) * self.D
+        sk_o = self._splitk(T, self.H * self.D)
+        sk_d = self._splitk(T, self.ffn_l)
+        sk_q = self._splitk(T, d, nqkv, tp_reduced=False)
+        o_parts = sb["o_buf"][: sk_o * T * d].view(sk_o, T, d)
+        d_parts = sb["down_buf"][: sk_d * T * d].view(sk_d, T, d)
+        qkv_parts = sb["qkv_buf"][: sk_q * T * nqkv].view(sk_q, T, nqkv)
+        plan = plan or ops.verify_split_plan(self.Hkv, self.max_model_len)
+        wn = self.wide_norm  # raw residual adds + the RMS row scale in the next GEMM (gammas folded), as _decode_step
+        ssq = sb["ssq"]
+        rn = lambda i: dict(rownorm=(ssq[i], self.eps)) if wn else {}  # noqa: E731
+        lin = ops.linear if self.on_gpu else self._verify_linear_cpu
+        for l, lw in enumerate(w.layers):
+            if l == 0 and wn:
+                ops.add_rmsnorm(h, lw.attn_norm, self.eps, xn, ids=ids, emb=w.embed, rows=T, ss_out=ssq.view(-1),
+                                ss_ld=ssq.shape[1], ss_nzero=2 * self.L)
+            elif l == 0:
+                ops.add_rmsnorm(h, lw.attn_norm, self.eps, xn, ids=ids, emb=w.embed, rows=T)
+            elif wn:
+                ops.res_add_ss(h, d_parts, xn, T, ssq[2 * l])
+            else:
+                ops.add_rmsnorm(h, lw.attn_norm, self.eps, xn, parts=d_parts, rows=T)
+            pre = {} if (self.on_gpu or l) else dict(pre=True)
+            lin(xn, lw.wqkv, "f32", out=qkv_parts, splitk=sk_q, **rn(2 * l), **pre)
+            kc, vc = self.kv[l, 0], self.kv[l, 1]
+            ops.rope_append(qkv_parts, pos, sb["seq0"][:T], bt, self.cos, self.sin, q, kc, vc, self.H, self.Hkv)
+            ops.attn_verify(q, kc, vc, bt, pos[:1], self.H, self.Hkv, self.scale, attn, workspace=sb["attn_ws"],
+                            plan=plan)
+            lin(attn, lw.wo, "f32", out=o_parts, splitk=sk_o)
+            if wn:
+                ops.res_add_ss(h, o_parts, xn, T, ssq[2 * l + 1])
+            else:
+                ops.add_rmsnorm(h, lw.mlp_norm, self.eps, xn, parts=o_parts, rows=T)
+            lin(xn, lw.w_gate_up, "silu", out=act, **(dict(rownorm=(h, self.eps)) if (wn and not self.on_gpu)
+                                                      else rn(2 * l + 1)))
+            lin(act, lw.w_down, "f32", out=d_parts, splitk=sk_d)
+        ops.add_rmsnorm(h, w.final_norm, self.eps, xn, parts=d_parts, rows=T)
+        logits = sb["logits"][:T]
+        lin(xn, w.lm_head, "f32", out=logits, splitk=1)
+        ops.spec_commit(logits, sb["draft"][:T - 1], sb["stats"], *st, self.eos, self.limit[:1], self.eos_on[:1],
+                        part=sb["amax_part"] if self.on_gpu else None)
+
+    def _verify_linear_cpu(self, x, wt, epi, out, splitk=1, rownorm=None, pre=False):
+        """CPU twin of the verify step's GEMMs, one row at a time with the rounding points of the plain batch-1 step's
+        own CPU twins, so that a verify row computes bit for bit what the plain step computes for that token (the GPU
+        kernels scale the GEMM's output rows; ``ops.linear``'s CPU twin scales its bf16 input rows instead).  With the
+        residual-reduce plain step (``rr_decode``): the product of the raw bf16 row, then the RMS row scale -- from the
+        Q24 row sum for an f32 epilogue (as ``attn_decode(rownorm=)`` applies it to the slabs), from the f32 residual
+        row itself for the SiLU epilogue (as ``linear_rr`` does; ``rownorm[0]`` is then the residual stream)."""
+        post = rownorm is not None and self.rr_decode and not self.rr_a8
+        for i in range(x.shape[0]):
+            row = x[i:i + 1]
+            if not post or pre:  # (pre: layer 0's qkv, where the plain step makes this very call)
+                kw = {} if rownorm is None else dict(rownorm=(rownorm[0][i:i + 1], rownorm[1]))
+                y = ops.linear(row, wt, epi, **kw)
+            elif epi == "f32":
+                r = torch.rsqrt(ops.ss_float(rownorm[0][i:i + 1]) / wt.K + rownorm[1])
+                y = ref.linear(row, wt.dense(), "f32").unsqueeze(0) * r.view(1, 1, 1)
+            else:
+                r = torch.rsqrt(rownorm[0][i].float().pow(2).sum() / wt.K + rownorm[1])
+                y = ref.linear(row, wt.dense(), "f32") * r
+                g, u = y.view(-1, 2, 16)[:, 0].reshape(1, -1), y.view(-1, 2, 16)[:, 1].reshape(1, -1)
+                y = (torch.nn.functional.silu(g) * u).to(torch.bfloat16)
+            (out[0, i] if (epi == "f32" and out.dim() == 3) else out[i]).copy_(y.reshape(-1))
+        return out
+
+    def spec_logits(self) -> torch.Tensor:
+        """[T, V] f32: the verify rows of the last verify step (the numerics check reads them)."""
+        return self._spec_bufs()["logits"][: self.spec_k() + 1]
+
+    def spec_drafts(self) -> torch.Tensor:
+        """[k] int32: the drafts of the last verify step (-1 = none)."""
+        return self._spec_bufs()["draft"][: self.spec_k()]
+
+    def decode_spec(self, steps: int, max_ctx: Optional[int] = None) -> None:
+        """Run ``steps`` verify steps of the request in slot 0 (the analogue of ``decode`` at bucket 1); ``max_ctx``
+        bounds pos0 + T during the run (picks the split plan's tier)."""
+        assert self.spec_supported(), "speculative decoding: TP = 1, bf16 weights and KV cache, spec_tokens > 0"
+        plan = tuple(self.ctx_plan(1, max_ctx))
+        if not self.use_graphs:
+            for _ in range(steps):
+                self._verify_step(plan)
+            return
+        key = ("spec", self.spec_k() + 1, plan, 0 if self._spec_forced is None else self._spec_forced.data_ptr())
+        if key not in self.graphs:
+            self._spec_bufs()
+            s = torch.cuda.Stream(device=self.device)
+            s.wait_stream(torch.cuda.current_stream(self.device))
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.stream(s):
+                with torch.cuda.graph(g, stream=s):
+                    self._verify_step(plan)
+            torch.cuda.current_stream(self.device).wait_stream(s)
+            self.graphs[key] = g
+        g = self.graphs[key]
+        for _ in range(steps):
+            g.replay()
+
+    def spec_counts(self) -> tuple[int, int, int]:
+        """(verify steps, drafted tokens, accepted tokens) since the runner was built (a device -> host read: call it
+        after the sync a decode run ends with)."""
+        if self._spec is None:
+            return (0, 0, 0)
+        a, b, c = self._spec["stats"].tolist()
+        return int(a), int(b), int(c)
+
     # ------------------------------------------------------------------------------------ slots
     def set_slot(self, slot: int, blocks: Sequence[int], limit: int, temperature: float = 0.0, top_k: int = 40,
                  top_p: float = 0.9, seed: int = 0, eos_on: bool = True, repeat_penalty: float = 1.0,
@@ -705,7 +903,10 @@ class ModelRunner:
         if not entries:
             return
         n, W, mb = len(entries), REPEAT_WINDOW, self.max_blocks
-        ints = torch.zeros(n, mb + 5, dtype=torch.int32)  # block-table row | limit top_k eos_on last_n visible
+        # speculative decoding: slot 0's context history (its length, then the tokens) rides in the same transfer
+        sx = (1 + self.max_model_len) if (self.spec_tokens > 0 and self.spec_supported()
+                                          and any(int(e["slot"]) == 0 for e in entries)) else 0
+        ints = torch.zeros(n, mb + 5 + sx, dtype=torch.int32)  # block-table row | limit top_k eos_on last_n visible
         flts = torch.zeros(n, 3, dtype=torch.float32)     # temperature top_p penalty
         seeds = torch.zeros(n, dtype=torch.int64)
         hist = None
@@ -713,9 +914,13 @@ class ModelRunner:
             blocks = list(e["blocks"])
             ints[i, : len(blocks)] = torch.tensor(blocks, dtype=torch.int32)
             last_n = max(0, min(int(e.get("repeat_last_n", REPEAT_WINDOW)), W))
-            ints[i, mb:] = torch.tensor([min(int(e["limit"]), self.max_new_cap), int(e.get("top_k", 40)),
-                                         1 if e.get("eos_on", True) else 0, last_n,
-                                         0 if e.get("defer_table", False) else 1], dtype=torch.int32)
+            ints[i, mb:mb + 5] = torch.tensor([min(int(e["limit"]), self.max_new_cap), int(e.get("top_k", 40)),
+                                               1 if e.get("eos_on", True) else 0, last_n,
+                                               0 if e.get("defer_table", False) else 1], dtype=torch.int32)
+            if sx and int(e["slot"]) == 0:
+                pids = list(e.get("prompt_ids", ()))[: self.max_model_len]
+                ints[i, mb + 5] = len(pids)
+                ints[i, mb + 6: mb + 6 + len(pids)] = torch.tensor(pids, dtype=torch.int32)
             flts[i] = torch.tensor([float(e.get("temperature", 0.0)), float(e.get("top_p", 0.9)),
                                     float(e.get("repeat_penalty", 1.0))])
             seeds[i] = int(e.get("seed", 0))
@@ -739,6 +944,11 @@ class ModelRunner:
             else:
                 self._pending_bt[sl] = dv[i, :mb].clone()
         self.block_tables.index_copy_(0, idx, dv[:, :mb] * dv[:, mb + 4:mb + 5])  # deferred rows stay zero
+        if sx:
+            sb = self._spec_bufs()
+            i0 = next(i for i, sl in enumerate(slots) if sl == 0)
+            sb["ctx_len"].copy_(dv[i0, mb + 5:mb + 6])
+            sb["ctx"].copy_(dv[i0:i0 + 1, mb + 6:])
         self.limit.index_copy_(0, idx, dv[:, mb])
         self.top_k.index_copy_(0, idx, dv[:, mb + 1])
         self.eos_on.index_copy_(0, idx, dv[:, mb + 2])

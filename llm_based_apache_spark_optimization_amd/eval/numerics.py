@@ -220,6 +220,65 @@ def check_recorded(eng, prompts, toks, elog, n_steps: int, check_rows: Sequence[
     return res
 
 
+def record_spec_logits(eng, prompt: Sequence[int], n_tokens: int, hidden: Optional[bool] = None):
+    """Greedy-decode ONE prompt through the speculative-decoding verify steps (``LLMEngine(spec_tokens > 0)``), one
+    verify step per engine iteration.  Returns (tokens [n_tokens + 1], logits [1, n_tokens, V] f32, steps) in
+    ``record_decode_logits``'s convention: logits[0, j - 1] is the verify row that chose token j (token 0 comes from
+    prefill) -- row i of the step that committed it as its i-th token.  ``hidden``: as in ``record_decode_logits``.
+    ``steps``: one dict per engine iteration -- first (index of its first committed token), committed (tokens it
+    committed), spec (whether it was a verify step), and for verify steps draft ([k] drafted ids, -1 = none) and
+    row_argmax ([T] argmax of every verify row)."""
+    from ..engine import SamplingParams
+
+    r = eng.runner
+    hidden = tied(r.w) if hidden is None else hidden
+    old = eng.run_ahead
+    eng.run_ahead = 1
+    try:
+        q = eng.add_request(list(prompt), SamplingParams(max_tokens=n_tokens + 1, temperature=0.0, ignore_eos=True))
+        out = torch.zeros(1, n_tokens, r.V, dtype=torch.float32, device=r.device)
+        hid = torch.zeros(1, n_tokens, r.d, dtype=torch.float32, device=r.device) if hidden else None
+        steps, have = [], 0
+        while not q.done.is_set():
+            before = r.spec_counts()[0]
+            slot = q.slot
+            eng.step()
+            now = len(q.output_ids) if q.done.is_set() else q.gen_host
+            c = now - have
+            if have == 0:  # the prefill's token; a decode run may have followed in the same iteration
+                c, have = now - 1, 1
+            if c <= 0:
+                continue
+            spec = r.spec_counts()[0] > before
+            slot = q.slot if q.slot >= 0 else slot
+            rows = r.spec_logits() if spec else r.logits[slot:slot + 1]
+            xh = (r._spec_bufs()["xn"] if spec else r.final_hidden(1)[slot:slot + 1]) if hidden else None
+            assert c <= rows.shape[0], (c, rows.shape)
+            for i in range(c):
+                j = have + i  # token index chosen by row i
+                if 1 <= j <= n_tokens:
+                    out[0, j - 1].copy_(rows[i].float())
+                    if hidden:
+                        hid[0, j - 1].copy_(xh[i].float())
+            rec = dict(first=have, committed=c, spec=spec)
+            if spec:
+                rec.update(draft=r.spec_drafts().tolist(), row_argmax=rows.float().argmax(-1).tolist())
+            steps.append(rec)
+            have = now
+        return q.output_ids, ((out, hid) if hidden else out), steps
+    finally:
+        eng.run_ahead = old
+
+
+def teacher_forced_check_spec(eng, prompt: Sequence[int], n_tokens: int = 64, weights=None) -> dict:
+    """``teacher_forced_check`` of the verify steps: every committed token's verify-row logits against the same oracle
+    under the same thresholds (``check_recorded``)."""
+    toks, elog, steps = record_spec_logits(eng, prompt, n_tokens)
+    res = check_recorded(eng, [list(prompt)], [toks], elog, n_tokens, (0,), weights)
+    res["verify_steps"] = sum(1 for s_ in steps if s_["spec"])
+    return res
+
+
 # ---- fault injection (tests/test_numerics_gpu.py, scripts/numerics_calibrate.py): the check must catch these
 @contextlib.contextmanager
 def scale_fault(eng, layer: int = 1, factor: float = 1.25):

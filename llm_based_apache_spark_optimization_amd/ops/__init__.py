@@ -1447,3 +1447,61 @@ def sample_commit(logits, hist, penalty, temperature, top_k, top_p, seeds, out_t
         part, cand = workspace
     ext().sample_commit(logits, part, cand, hist, penalty, last_n, temperature, top_k, top_p, seeds, out_tokens,
                         gen_len, input_ids, positions, finished, eos, limit, eos_on)
+
+
+# ----------------------------------------------------------------------------------- speculative decoding
+def verify_split_plan(Hkv: int, max_ctx: int) -> tuple[int, int, int]:
+    """(chunk_blocks, nsplit, unsplit_max) of ``attn_verify`` for contexts (pos0 + T) up to max_ctx: the batch-1
+    decode plan -- one workgroup per (kv head, split) either way."""
+    return decode_split_plan(1, Hkv, max_ctx)
+
+
+def verify_workspace(T: int, H: int, Hkv: int, nsplit: int, device) -> tuple:
+    """(opart, mlpart, counters) of ``attn_verify``: the split partials of T * H query rows and Hkv arrival tickets
+    (start zeroed; the kernel leaves them zeroed)."""
+    return decode_workspace(T, H, Hkv, nsplit, device)
+
+
+def attn_verify(q, kc, vc, block_table, pos0, H, Hkv, scale, out, workspace=None, plan=None):
+    """Speculative-decoding verify attention: q [T, H, 128] (rotated) are the T new tokens of ONE sequence whose block
+    table row is ``block_table``, at positions pos0 .. pos0 + T - 1 (``pos0``: int32 tensor, read on the device); their
+    K / V are already in the bf16 cache (``rope_append``).  Row t sees keys j <= pos0 + t.  out [T, H * 128] bf16.
+    T <= 8 and T * H / Hkv <= 16."""
+    T = q.shape[0]
+    if not _gpu(q):
+        return ref.attn_verify(q, kc, vc, block_table, pos0, H, Hkv, scale, out)
+    plan = plan if plan is not None else verify_split_plan(Hkv, block_table.numel() * 64)
+    chunk, nsplit = plan[0], plan[1]
+    unsplit_max = plan[2] if len(plan) > 2 else 4
+    if workspace is None:
+        workspace = verify_workspace(T, H, Hkv, nsplit, q.device)
+    opart, mlpart, counters = workspace
+    ext().attn_verify(q, kc, vc, block_table, pos0, H, Hkv, scale, chunk, nsplit, unsplit_max, out, opart, mlpart,
+                      counters)
+    return out
+
+
+def spec_draft(prompt_tok, prompt_len, out_tokens, gen_len, input_ids, positions, k, spec_ids, spec_pos, spec_draft_out,
+               n_max: int = 3, n_min: int = 1, forced=None):
+    """Prompt-lookup drafter, one row per entry of ``prompt_len`` (kernels/spec.hip).  forced [nf, k] int32 replaces
+    the search: the draft is its row min(gen_len, nf - 1)."""
+    if not _gpu(prompt_tok):
+        return ref.spec_draft(prompt_tok, prompt_len, out_tokens, gen_len, input_ids, positions, k, n_max, n_min,
+                              forced, spec_ids, spec_pos, spec_draft_out)
+    ext().spec_draft(prompt_tok, prompt_len, out_tokens, gen_len, input_ids, positions, k, n_max, n_min, forced,
+                     spec_ids, spec_pos, spec_draft_out)
+
+
+def spec_commit(logits, draft, stats, out_tokens, gen_len, input_ids, positions, finished, eos, limit=None,
+                eos_on=None, part=None):
+    """Greedy verification of the T = k + 1 verify rows ``logits`` of the sequence in state row 0 and the in-order
+    commit of the accepted tokens (kernels/sampling.hip spec_commit_kernel); stats int64 [3] += (steps, drafted,
+    accepted)."""
+    T, V = logits.shape
+    limit, eos_on = _row_defaults(1, out_tokens, limit, eos_on)
+    if not _gpu(logits):
+        return ref.spec_commit(logits, draft, stats, out_tokens, gen_len, input_ids, positions, finished, eos, limit,
+                               eos_on)
+    if part is None:
+        part = torch.empty(T * ((V + 4095) // 4096), device=logits.device, dtype=torch.int64)
+    ext().spec_commit(logits, part, draft, stats, out_tokens, gen_len, input_ids, positions, finished, eos, limit, eos_on)

@@ -203,6 +203,75 @@ def argmax_commit(logits, out_tokens, gen_len, input_ids, positions, finished, e
     commit(logits.float().argmax(-1), out_tokens, gen_len, input_ids, positions, finished, eos, limit, eos_on)
 
 
+# ----------------------------------------------------------------------------------- speculative decoding
+def attn_verify(q, kc, vc, block_table, pos0, H, Hkv, scale, out):
+    """Attention of the T = q.shape[0] new tokens of ONE sequence (their K / V already appended): row t is a decode
+    query at position pos0 + t, so it sees keys j <= pos0 + t."""
+    T = q.shape[0]
+    p0 = int(pos0.reshape(-1)[0])
+    pos = torch.arange(p0, p0 + T, dtype=torch.int32, device=q.device)
+    bt = block_table.reshape(1, -1).expand(T, -1)
+    return attn_decode(q, kc, vc, bt, pos, H, Hkv, scale, out.view(T, H, -1))
+
+
+def spec_draft(prompt_tok, prompt_len, out_tokens, gen_len, input_ids, positions, k, n_max, n_min, forced,
+               spec_ids, spec_pos, spec_draft_out):
+    """Prompt-lookup drafter (csrc/kernels/spec.hip): per row, the k tokens that followed the best earlier occurrence
+    of the context's last tokens -- the lexicographic maximum of (match length m <= n_max, the whole continuation
+    exists, end index j) over the candidate ends j <= L - 2 with m >= n_min; -1 where there is none."""
+    rows = prompt_len.numel()
+    T = k + 1
+    for row in range(rows):
+        pl = min(max(int(prompt_len[row]), 0), prompt_tok.shape[1])
+        gl = min(max(int(gen_len[row]), 0), out_tokens.shape[1])
+        draft = [-1] * k
+        if forced is not None:
+            f = forced.reshape(-1, k)
+            draft = [int(x) for x in f[min(gl, f.shape[0] - 1)]]
+        else:
+            ctx = torch.cat([prompt_tok[row, :pl], out_tokens[row, :gl]]).long()
+            L = ctx.numel()
+            if L >= 2:
+                j = torch.arange(L - 1)
+                m = torch.zeros(L - 1, dtype=torch.long)
+                run = torch.ones(L - 1, dtype=torch.bool)
+                for i in range(min(n_max, L)):
+                    run = run & (j - i >= 0) & (ctx[(j - i).clamp_min(0)] == ctx[L - 1 - i])
+                    m += run
+                key = (m << 33) | ((j + 1 + k <= L).long() << 32) | j
+                key = torch.where(m >= max(n_min, 1), key, torch.zeros_like(key))
+                best = int(key.max())
+                if best:
+                    jb = best & 0xFFFFFFFF
+                    draft = [int(ctx[jb + 1 + i]) if jb + 1 + i < L else -1 for i in range(k)]
+        spec_draft_out.view(-1)[row * k:(row + 1) * k] = torch.tensor(draft, dtype=spec_draft_out.dtype)
+        ids = [int(input_ids[row])] + [max(d, 0) for d in draft]
+        spec_ids.view(-1)[row * T:(row + 1) * T] = torch.tensor(ids, dtype=spec_ids.dtype)
+        spec_pos.view(-1)[row * T:(row + 1) * T] = int(positions[row]) + torch.arange(T, dtype=spec_pos.dtype)
+
+
+def spec_commit(logits, draft, stats, out_tokens, gen_len, input_ids, positions, finished, eos, limit=None,
+                eos_on=None):
+    """logits [T, V]: the verify rows of the sequence in state row 0.  Commits tok_0 .. tok_a in order (a = leading
+    drafts equal to the argmax of their row), stopping after a finishing token; stats += (1, drafts >= 0, tokens
+    committed beyond the first).  A finished row changes nothing."""
+    if int(finished[0]):
+        return
+    T = logits.shape[0]
+    toks = logits.float().argmax(-1)
+    committed = 0
+    for i in range(T):
+        if int(finished[0]):
+            break
+        commit(toks[i:i + 1], out_tokens, gen_len, input_ids, positions, finished, eos, limit, eos_on)
+        committed += 1
+        if i >= T - 1 or int(draft[i]) < 0 or int(draft[i]) != int(toks[i]):
+            break
+    stats[0] += 1
+    stats[1] += int((draft[:T - 1] >= 0).sum())
+    stats[2] += max(committed - 1, 0)
+
+
 def sample_probs(logits_row: torch.Tensor, temperature: float, top_k: int, top_p: float, topk_cap: int = 64):
     """Distribution the sampler draws from (top-k capped at 64, nucleus within it)."""
     k = top_k if 0 < top_k <= topk_cap else topk_cap

@@ -1,0 +1,196 @@
+"""Speculative decoding on MI355X: what a verify step costs and what it can gain.
+
+  kernel   attn_verify (T rows of one sequence, one pass over the cache) against attn_decode over a bucket of T rows
+           (T sequences' worth of cache reads) and against single-token attn_decode; achieved KV bytes/s.
+  step     device time of a verify step (k drafted tokens) against the plain batch-1 step on the same engine, with
+           planted all-wrong drafts so both arms decode the same tokens; break-even acceptance = ratio - 1.
+  e2e      tokens/s of a request at planted acceptance 0, about half, and all: the envelope.  (Random-init weights
+           give no meaningful natural acceptance; real acceptance needs a checkpoint, LSA_CHECKPOINT_DIR.)
+
+Every graph is warmed, times are device events, the arms alternate within one process.  Appends JSON lines to
+profiles/spec/spec_decode_mi355x.jsonl.  Needs a GPU.
+
+  python scripts/bench_spec.py [--layers N] [--skip kernel,step,e2e] [--reps 5]
+"""
+from __future__ import annotations
+
+import argparse
+import dataclasses
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from llm_based_apache_spark_optimization_amd import ops  # noqa: E402
+from llm_based_apache_spark_optimization_amd.engine import LLMEngine, ModelRunner, SamplingParams  # noqa: E402
+from llm_based_apache_spark_optimization_amd.models import get_spec  # noqa: E402
+from llm_based_apache_spark_optimization_amd.models.llama import init_random  # noqa: E402
+
+OUT = os.path.join(ROOT, "profiles", "spec", "spec_decode_mi355x.jsonl")
+
+
+def emit(rec: dict) -> None:
+    os.makedirs(os.path.dirname(OUT), exist_ok=True)
+    with open(OUT, "a") as f:
+        f.write(json.dumps(rec) + "\n")
+    print(json.dumps(rec), flush=True)
+
+
+def time_graph(fn, iters: int = 50) -> float:
+    """us per call of fn, replayed from a captured graph of 10 calls (device events)."""
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        fn()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, stream=s):
+            for _ in range(10):
+                fn()
+    torch.cuda.current_stream().wait_stream(s)
+    g.replay()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        g.replay()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) * 1e3 / (iters * 10)
+
+
+def bench_kernel(dev, reps: int) -> None:
+    D = 128
+    for name, H, Hkv, ctxs in (("llama3.2-3b", 24, 8, (2048,)), ("duckdb-nsql-7b", 32, 32, (256, 2048))):
+        G = H // Hkv
+        for ctx in ctxs:
+            for T in sorted({2, 4, min(8, 16 // G)}):
+                mb = (ctx + T + 63) // 64 + 1
+                g = torch.Generator().manual_seed(ctx + T)
+                kc = (torch.randn(T * mb + 1, Hkv, 64, D, generator=g) * 0.5).to(torch.bfloat16).to(dev)
+                vc = (torch.randn(T * mb + 1, Hkv, 64, D, generator=g) * 0.5).to(torch.bfloat16).to(dev)
+                bts = (torch.arange(T * mb, dtype=torch.int32) + 1).view(T, mb).to(dev)  # T disjoint sequences
+                q = (torch.randn(T, H, D, generator=g) * 0.7).to(torch.bfloat16).to(dev)
+                out = torch.zeros(T, H * D, dtype=torch.bfloat16, device=dev)
+                pos0 = torch.tensor([ctx - T], dtype=torch.int32, device=dev)
+                posT = torch.full((T,), ctx - 1, dtype=torch.int32, device=dev)
+                plan = ops.verify_split_plan(Hkv, ctx)
+                ws = ops.verify_workspace(T, H, Hkv, plan[1], dev)
+                planT = ops.decode_split_plan(T, Hkv, ctx)
+                wsT = ops.decode_workspace(T, H, Hkv, planT[1], dev)
+                arms = {
+                    "verify": lambda: ops.attn_verify(q, kc, vc, bts[:1], pos0, H, Hkv, D ** -0.5, out, workspace=ws,
+                                                      plan=plan),
+                    "decode_T_rows": lambda: ops.attn_decode(q, kc, vc, bts, posT, H, Hkv, D ** -0.5, out.view(T, H, D),
+                                                             workspace=wsT, plan=planT),
+                    "decode_1_row": lambda: ops.attn_decode(q[:1], kc, vc, bts[:1], posT[:1], H, Hkv, D ** -0.5,
+                                                            out[:1].view(1, H, D), workspace=ws, plan=plan),
+                }
+                us = {k: [] for k in arms}
+                for _ in range(reps):  # alternate the arms
+                    for k, fn in arms.items():
+                        us[k].append(time_graph(fn))
+                med = {k: round(statistics.median(v), 2) for k, v in us.items()}
+                kv_bytes = 2 * Hkv * ctx * D * 2
+                emit(dict(bench="kernel", model=name, H=H, Hkv=Hkv, ctx=ctx, T=T, us=med,
+                          verify_over_decode1=round(med["verify"] / med["decode_1_row"], 3),
+                          verify_over_decodeT=round(med["verify"] / med["decode_T_rows"], 3),
+                          verify_kv_GBps=round(kv_bytes / med["verify"] / 1e3, 1)))
+
+
+def forced(toks, kind: str, k: int, V: int) -> torch.Tensor:
+    n = len(toks)
+    right = lambda i: toks[i] if i < n else 0  # noqa: E731
+    rows = []
+    for g in range(n + 1):
+        if kind == "all":
+            rows.append([right(g + i) for i in range(k)])
+        elif kind == "none":
+            rows.append([(right(g + i) + 1) % V for i in range(k)])
+        else:  # about half: the first ceil(k / 2) right
+            h = (k + 1) // 2
+            rows.append([right(g + i) if i < h else (right(g + i) + 1) % V for i in range(k)])
+    return torch.tensor(rows, dtype=torch.int32)
+
+
+def bench_engine(dev, layers, reps: int, skip) -> None:
+    for base, plen, new in (("duckdb-nsql", 128, 128), ("llama3.2", 2048, 128)):
+        spec = get_spec(base)
+        if layers:
+            spec = dataclasses.replace(spec, n_layers=layers, name=f"{base}-{layers}l")
+        w = init_random(spec, dev, seed=5)
+        r = ModelRunner(w, max_slots=2, max_model_len=plen + new + 64, num_kv_blocks=2 * ((plen + new) // 64 + 3))
+        eng = LLMEngine(r, name=spec.name)
+        g = torch.Generator().manual_seed(7)
+        ids = [1] + torch.randint(3, 30000, (plen - 1,), generator=g).tolist()
+        sp = SamplingParams(max_tokens=new, ignore_eos=True)
+
+        def run(k: int, kind: str, toks=None):
+            """(tokens, decode device s, decode steps, tokens / s of the decode phase) of one request."""
+            r.spec_tokens = k
+            r.set_spec_forced(None if not k else forced(toks, kind, r.spec_k(), spec.vocab_size))
+            d0, n0 = eng.stats["decode_device_s"], eng.stats["decode_steps"]
+            out = eng.generate([ids], sp)[0].token_ids
+            ds, ns = eng.stats["decode_device_s"] - d0, eng.stats["decode_steps"] - n0
+            return out, ds, ns, (len(out) - 1) / ds
+
+        toks = run(0, "")[0]  # warms the plain graphs
+        kmax = min(7, 16 // (r.H // r.Hkv) - 1)
+        ks = sorted({1, 3, kmax})
+        for k in ks:
+            run(k, "none", toks)  # warms the verify graphs
+        if "step" not in skip:
+            plain, ver = [], {k: [] for k in ks}
+            for _ in range(reps):
+                _, ds, ns, _ = run(0, "")
+                plain.append(ds / ns)
+                for k in ks:
+                    out, ds, ns, _ = run(k, "none", toks)
+                    assert ns == new - 1, (ns, "all-wrong drafts commit one token per step")
+                    ver[k].append(ds / ns)
+            p = statistics.median(plain)
+            for k in ks:
+                v = statistics.median(ver[k])
+                emit(dict(bench="step", model=spec.name, layers=spec.n_layers, prompt=plen, new=new, k=k,
+                          plain_step_ms=round(p * 1e3, 4), verify_step_ms=round(v * 1e3, 4),
+                          break_even_accept=round(v / p - 1, 3), tokens_equal=out == toks))
+        if "e2e" not in skip:
+            res = {}
+            # the planted drafts follow the verify path's own greedy tokens (at random-init margins they can leave the
+            # plain run's after a few tokens, and drafts built from the plain run would then never be accepted)
+            toks = run(3, "none", toks)[0]
+            for _ in range(reps):
+                res.setdefault("plain", []).append(run(0, "")[3])
+                for kind in ("none", "half", "all"):
+                    out, _, ns, tps = run(3, kind, toks)
+                    res.setdefault(kind, []).append(tps)
+                    res[kind + "_steps"] = ns
+            emit(dict(bench="e2e", model=spec.name, layers=spec.n_layers, prompt=plen, new=new, k=3,
+                      decode_tok_s={k: round(statistics.median(v), 1) for k, v in res.items() if not k.endswith("_steps")},
+                      verify_steps={k[:-6]: v for k, v in res.items() if k.endswith("_steps")}))
+        del eng, r, w
+        torch.cuda.empty_cache()
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--layers", type=int, default=0, help="truncate the models to this many layers (0 = full depth)")
+    ap.add_argument("--skip", default="", help="comma list of kernel,step,e2e")
+    ap.add_argument("--reps", type=int, default=5)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_spec.py needs a GPU")
+    ops.ext()
+    dev = torch.device("cuda:0")
+    skip = set(a.skip.split(",")) if a.skip else set()
+    if "kernel" not in skip:
+        bench_kernel(dev, a.reps)
+    if not {"step", "e2e"} <= skip:
+        bench_engine(dev, a.layers, a.reps, skip)
+
+
+if __name__ == "__main__":
+    main()
