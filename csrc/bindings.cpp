@@ -58,6 +58,8 @@ int lsa_argmax_commit(const float* logits, int B, int V, unsigned long long* par
 int lsa_attn_verify(const void* q, const void* kc, const void* vc, const int* bt, int max_blocks, const int* pos0, int T,
                     int H, int Hkv, float scale, int chunk_blocks, int nsplit, int unsplit_max, void* out, float* opart,
                     float* mlpart, int* counters, hipStream_t s);
+int lsa_kv_copy_blocks(void* kv, void* scale, const int* pairs, int npairs, int planes, int nb, long long tile_bytes,
+                       long long scale_bytes, hipStream_t s);
 int lsa_spec_draft(const int* prompt_tok, int prompt_ld, const int* prompt_len, const int* out_tokens, int max_new,
                    const int* gen_len, const int* input_ids, const int* positions, int rows, int k, int n_max, int n_min,
                    const int* forced, int nf, int* spec_ids, int* spec_pos, int* spec_draft, hipStream_t s);
@@ -811,6 +813,28 @@ void kv8_dequant(const at::Tensor& kc, const at::Tensor& vc, const at::Tensor& k
         "kv8_dequant");
 }
 
+// prefix cache: copy whole KV blocks inside the arena kv [L, 2, NB, Hkv, 64, 128] (bf16, or e4m3 bytes with
+// scale [L, 2, NB, Hkv, 64] f32) for every (src, dst) row of pairs [n, 2] int32 (kernels/kv_copy.hip).  The ids
+// are validated on the host before they are uploaded (ops.kv_copy_blocks).
+void kv_copy_blocks(at::Tensor& kv, const c10::optional<at::Tensor>& scale, const at::Tensor& pairs) {
+  need(kv, scale.has_value() ? at::kByte : at::kBFloat16, "kv");
+  TORCH_CHECK(kv.dim() == 6 && kv.size(1) == 2 && kv.size(2) >= 2 && kv.size(4) == 64 && kv.size(5) == 128 &&
+                  kv.is_contiguous(), "kv must be a contiguous [L, 2, NB, Hkv, 64, 128] arena");
+  if (scale.has_value()) {
+    need(*scale, at::kFloat, "kv_scale");
+    TORCH_CHECK(scale->dim() == 5 && scale->is_contiguous() && scale->sizes() == kv.sizes().slice(0, 5),
+                "kv_scale must be a contiguous [L, 2, NB, Hkv, 64] tensor");
+  }
+  need(pairs, at::kInt, "pairs");
+  TORCH_CHECK(pairs.dim() == 2 && pairs.size(1) == 2 && pairs.is_contiguous(), "pairs must be a contiguous [n, 2] tensor");
+  const int64_t L = kv.size(0), NB = kv.size(2), Hkv = kv.size(3);
+  TORCH_CHECK(NB <= INT32_MAX && pairs.size(0) <= 65535 && 2 * L <= 65535, "kv_copy_blocks: arena or pair list too large");
+  check(lsa_kv_copy_blocks(kv.data_ptr(), scale.has_value() ? scale->data_ptr() : nullptr, pairs.data_ptr<int>(),
+                           (int)pairs.size(0), (int)(2 * L), (int)NB, Hkv * 64 * 128 * (int64_t)kv.element_size(),
+                           scale.has_value() ? Hkv * 64 * 4 : 0, cur_stream()),
+        "kv_copy_blocks");
+}
+
 void attn_prefill(const at::Tensor& q, const at::Tensor& kc, const at::Tensor& vc, const at::Tensor& block_tables,
                   const at::Tensor& cu_q, const at::Tensor& ctx_lens, const at::Tensor& work, int64_t H, int64_t Hkv,
                   double scale, at::Tensor& out, int64_t rows32, int64_t xf_mt) {
@@ -1166,6 +1190,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("cos"), py::arg("sin"), py::arg("q_out"), py::arg("kc"), py::arg("vc"), py::arg("H"), py::arg("Hkv"),
         py::arg("ks") = py::none(), py::arg("vs") = py::none());
   m.def("kv8_dequant", &kv8_dequant);
+  m.def("kv_copy_blocks", &kv_copy_blocks, py::arg("kv"), py::arg("kv_scale"), py::arg("pairs"));
   m.def("silu_mul", &silu_mul);
   m.def("attn_decode", &attn_decode, py::arg("q"), py::arg("kc"), py::arg("vc"), py::arg("block_tables"),
         py::arg("pos"), py::arg("H"), py::arg("Hkv"), py::arg("scale"), py::arg("chunk_blocks"), py::arg("nsplit"),

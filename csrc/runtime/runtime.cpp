@@ -7,7 +7,8 @@
 //                      slots (stable rows of the device-side decode state, so no compaction between
 //                      steps), prefill token budget per step, KV reservation of prompt + max_new
 //                      tokens at admission (no preemption needed: 288 GB of HBM makes the
-//                      reservation cheap), release on finish / abort.
+//                      reservation cheap), release on finish / abort.  Optional prefix cache: shared,
+//                      refcounted, evictable KV blocks of common prompt prefixes (runtime_core.h).
 //  * levenshtein     — character edit distance over Unicode code points (the eval harness metric of
 //                      Model_Evaluation_&_Comparision.py:51,125, which used the python-Levenshtein C
 //                      extension).
@@ -41,11 +42,25 @@ PYBIND11_MODULE(_lsa_runtime, m) {
       .def_property_readonly("num_blocks", &BlockAllocator::num_blocks)
       .def_property_readonly("block_size", &BlockAllocator::block_size);
   py::class_<Scheduler>(m, "Scheduler")
-      .def(py::init<int, int, int, int, int, int>(), py::arg("num_blocks"), py::arg("block_size"), py::arg("max_slots"),
-           py::arg("max_prefill_tokens"), py::arg("max_blocks_per_seq"), py::arg("reserve_tokens") = 64)
-      .def("add", &Scheduler::add)
+      .def(py::init<int, int, int, int, int, int, bool, int>(), py::arg("num_blocks"), py::arg("block_size"),
+           py::arg("max_slots"), py::arg("max_prefill_tokens"), py::arg("max_blocks_per_seq"),
+           py::arg("reserve_tokens") = 64, py::arg("prefix_cache") = false,
+           py::arg("cow_min_tokens") = Scheduler::kCowMinTokens)
+      .def("add", &Scheduler::add, py::arg("id"), py::arg("prompt_len"), py::arg("max_new"),
+           py::arg("tokens") = std::vector<int>(), py::arg("cacheable") = true)
       .def("grow", &Scheduler::grow, py::arg("id"), py::arg("tokens"))
-      .def("preempt", &Scheduler::preempt, py::arg("id"), py::arg("prompt_len"), py::arg("max_new"))
+      .def("preempt", &Scheduler::preempt, py::arg("id"), py::arg("prompt_len"), py::arg("max_new"),
+           py::arg("tokens") = std::vector<int>())
+      .def("cached_tokens", &Scheduler::cached_tokens)
+      .def("shared_blocks", &Scheduler::shared_blocks)
+      .def("take_copies", &Scheduler::take_copies)
+      .def("copies_done", &Scheduler::copies_done)
+      .def("publish", &Scheduler::publish)
+      .def("reset_prefix_cache", &Scheduler::reset_prefix_cache)
+      .def("prefix_nodes", &Scheduler::prefix_nodes)
+      .def_property_readonly("cached_blocks", &Scheduler::cached_blocks)
+      .def_property_readonly("prefix_cache", &Scheduler::prefix_cache)
+      .def_property_readonly("cow_min_tokens", &Scheduler::cow_min_tokens)
       .def("youngest_first", &Scheduler::youngest_first)
       .def("admit", &Scheduler::admit)
       .def("finish", &Scheduler::finish)

@@ -46,6 +46,8 @@ class GenerateResponse:
     prompt_eval_duration: int = 0
     eval_count: int = 0
     eval_duration: int = 0
+    # of prompt_eval_count (the full prompt length), the tokens served from the engine's prefix cache
+    prompt_cached_count: int = 0
 
     def __getitem__(self, k):
         return getattr(self, k)
@@ -249,7 +251,8 @@ class EngineService(Backend):
         return GenerateResponse(model=model, response=r.text, done_reason=r.done_reason, created_at=_now(),
                                 total_duration=r.total_duration_ns, load_duration=r.load_duration_ns,
                                 prompt_eval_count=r.prompt_tokens, prompt_eval_duration=r.prompt_eval_duration_ns,
-                                eval_count=r.eval_count, eval_duration=r.eval_duration_ns)
+                                eval_count=r.eval_count, eval_duration=r.eval_duration_ns,
+                                prompt_cached_count=r.cached_prompt_tokens)
 
     def generate(self, model, prompt, system="", options=None, raw=False) -> GenerateResponse:
         eng, req = self._submit(model, prompt, system, options, raw)
@@ -279,6 +282,7 @@ class EngineService(Backend):
         return {"ok": all(lp.alive() for lp in self._loops.values()),
                 "engines": {m: {"alive": lp.alive(), "running": lp.engine.sched.num_running,
                                 "waiting": lp.engine.sched.num_waiting, "kv_usage": lp.engine.sched.kv_usage,
+                                "prefix_cached_blocks": lp.engine.sched.cached_blocks,
                                 "restarts": lp.restarts, "rebuilds": self.rebuilds.get(m, 0),
                                 **lp.engine.stats} for m, lp in self._loops.items()}}
 

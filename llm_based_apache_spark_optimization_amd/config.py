@@ -50,6 +50,15 @@ class Settings:
     # request falls back to plain steps; < 0 = the runner's default)
     spec_tokens: int = dataclasses.field(default_factory=lambda: _env("SPEC_TOKENS", 0, int))
     spec_min_accept: float = dataclasses.field(default_factory=lambda: _env("SPEC_MIN_ACCEPT", -1.0, float))
+    # prefix cache (off by default): the KV blocks of full 64-token prompt blocks stay cached after their request and
+    # are shared with later requests whose prompt starts with the same tokens; prompts of every caller of one engine
+    # share KV then.  prefix_cow_min_tokens: the shortest common prefix with a cached block for which the block is
+    # forked (copied, the rest prefilled) rather than prefilled whole; 64 = never fork.  Default 8: the smallest p of
+    # the sweep 8 / 16 / 32 / 48 whose saved time to first token is >= 2x the block copy's device time on both models
+    # (7B: copy 21.6 us, 8 more suffix tokens cost 921 us; 3B: 17.3 us against 609 us; scripts/bench_prefix_cache.py,
+    # profiles/prefix_cache/cow_sweep_mi355x.jsonl)
+    prefix_cache: bool = dataclasses.field(default_factory=lambda: _env("PREFIX_CACHE", False, bool))
+    prefix_cow_min_tokens: int = dataclasses.field(default_factory=lambda: _env("PREFIX_COW_MIN_TOKENS", 8, int))
     tp: int = dataclasses.field(default_factory=lambda: _env("TP", 1, int))
     dp: int = dataclasses.field(default_factory=lambda: _env("DP", 1, int))
     max_batch: int = dataclasses.field(default_factory=lambda: _env("MAX_BATCH", 32, int))

@@ -57,6 +57,9 @@ class SamplingParams:
     # prompt-lookup speculative decoding, where the engine runs it (LLMEngine(spec_tokens > 0), greedy, batch 1);
     # the Ollama option extension "speculate": false opts a request out.  The tokens are the same either way.
     speculate: bool = True
+    # prefix cache, where the engine runs it (LLMEngine(prefix_cache=True)): llama.cpp's "cache_prompt": false opts a
+    # request out -- it neither reuses cached KV blocks nor publishes its own
+    cache_prompt: bool = True
 
     @property
     def needs_sampler(self) -> bool:
@@ -79,7 +82,8 @@ class SamplingParams:
                               repeat_penalty=float(opts.get("repeat_penalty", 1.0)),
                               repeat_last_n=int(opts.get("repeat_last_n", 64)),
                               num_ctx=int(opts["num_ctx"]) if opts.get("num_ctx") else None,
-                              num_keep=int(opts.get("num_keep", 4)), speculate=bool(opts.get("speculate", True)))
+                              num_keep=int(opts.get("num_keep", 4)), speculate=bool(opts.get("speculate", True)),
+                              cache_prompt=bool(opts.get("cache_prompt", True)))
 
 
 @dataclasses.dataclass
@@ -108,6 +112,8 @@ class Request:
     spec_steps: int = 0
     spec_accepted: int = 0
     spec_off: bool = False
+    # prefix cache: prompt tokens whose KV was found in the cache (summed over re-admissions of a preempted request)
+    cached_tokens: int = 0
 
     @property
     def ctx_ids(self) -> list:
@@ -126,12 +132,13 @@ class GenerationResult:
     prompt_eval_duration_ns: int
     eval_duration_ns: int
     done_reason: str
+    cached_prompt_tokens: int = 0  # prompt tokens served from the prefix cache instead of being prefilled
 
 
 class LLMEngine:
     def __init__(self, runner: ModelRunner, tokenizer=None, max_prefill_tokens: int = 16384, sync_every: int = 8,
                  name: Optional[str] = None, prefill_chunk: Optional[int] = None, kv_reserve_tokens: int = BLOCK,
-                 spec_tokens: int = 0):
+                 spec_tokens: int = 0, prefix_cache: bool = False, prefix_cow_min_tokens: Optional[int] = None):
         self.runner = runner
         if spec_tokens:  # speculative decoding for batch-1 greedy requests (the runner clamps it to what it supports)
             runner.spec_tokens = int(spec_tokens)
@@ -142,8 +149,15 @@ class LLMEngine:
         if tok_eos and sorted(tok_eos) != sorted(runner.eos_list):
             runner.set_eos(sorted(set(tok_eos) | set(e for e in runner.eos_list if e >= 0)))
         # kv_reserve_tokens: generated tokens reserved at admission (< 0: prompt + max_new up front, no growth)
+        # prefix_cache: KV blocks of full prompt blocks stay cached after their request and are shared with later
+        # requests whose prompt starts with the same tokens (runtime_core.h: the index, its safety invariant and the
+        # eviction rule).  Off by default; block ids, launches and statistics are then what they are without it.
+        self.prefix_cache = bool(prefix_cache)
+        if self.prefix_cache:  # a row finished by its prefill token must not rewrite a published block (runner.py)
+            runner.park_past_prompt = True
+        cow = {} if prefix_cow_min_tokens is None else {"cow_min_tokens": int(prefix_cow_min_tokens)}
         self.sched = native.Scheduler(runner.num_kv_blocks, BLOCK, runner.max_slots, max_prefill_tokens,
-                                      runner.max_blocks, kv_reserve_tokens)
+                                      runner.max_blocks, kv_reserve_tokens, prefix_cache=self.prefix_cache, **cow)
         # set by a preemption: no admissions while requests run and fewer than _admit_hold_blocks KV blocks are free
         # (the preempted request's re-admission plus one block of growth per running request), so the preempted
         # request is not re-admitted at once and evicted again by the same growth
@@ -167,7 +181,10 @@ class LLMEngine:
         self.load_time_s = 0.0
         self.stats = {"requests": 0, "prompt_tokens": 0, "generated_tokens": 0, "decode_steps": 0,
                       "prefill_s": 0.0, "decode_s": 0.0, "decode_device_s": 0.0, "aborted": 0, "preempted": 0,
-                      "kv_grown_blocks": 0, "peak_running": 0, "spec_steps": 0, "spec_drafted": 0, "spec_accepted": 0}
+                      "kv_grown_blocks": 0, "peak_running": 0, "spec_steps": 0, "spec_drafted": 0, "spec_accepted": 0,
+                      # prefix cache: admissions that looked the prompt up, those that found something, and the
+                      # prompt tokens not prefilled because of it (prompt_tokens counts the tokens that were)
+                      "prefix_queries": 0, "prefix_hits": 0, "prefix_cached_tokens": 0}
         self._spec_seen = (0, 0, 0)  # runner.spec_counts() as of the last decode run
         # per-decode-run device timing (hipEvents around the graph replays, read after the host sync the
         # run ends with anyway): lsa_decode_step_device_seconds{model} = GPU time per token step
@@ -206,7 +223,10 @@ class LLMEngine:
         req = Request(next(self._ids), list(map(int, prompt_ids)), p, time.perf_counter(),
                       stream=queue.Queue() if stream else None)
         with self._lock:
-            self.sched.add(req.rid, len(req.prompt_ids), p.max_tokens)
+            if self.prefix_cache:
+                self.sched.add(req.rid, len(req.prompt_ids), p.max_tokens, req.prompt_ids, bool(p.cache_prompt))
+            else:
+                self.sched.add(req.rid, len(req.prompt_ids), p.max_tokens)
             self._reqs[req.rid] = req
         return req
 
@@ -233,6 +253,20 @@ class LLMEngine:
                 req.admitted = req.admitted or t0
                 self._slot_owner[slot] = rid
                 sp = req.params
+                if self.prefix_cache and sp.cache_prompt:
+                    # the prefill starts past the cached tokens (they are not charged to prefill_chunk either); the
+                    # full prompt still goes to set_slots for the drafter's history and the repetition-penalty ring
+                    req.prefilled = hit = self.sched.cached_tokens(rid)
+                    req.cached_tokens += hit
+                    self.stats["prefix_queries"] += 1
+                    self.stats["prefix_hits"] += 1 if hit else 0
+                    self.stats["prefix_cached_tokens"] += hit
+                    REGISTRY.inc("lsa_prefix_cache_queries_total", 1, "admissions that looked the prompt up in the "
+                                 "prefix cache", model=self.name)
+                    REGISTRY.inc("lsa_prefix_cache_hits_total", 1 if hit else 0, "admissions that reused cached KV "
+                                 "blocks", model=self.name)
+                    REGISTRY.inc("lsa_prefix_cached_tokens_total", hit, "prompt tokens served from the prefix cache",
+                                 model=self.name)
                 # a re-admitted (preempted) request continues its random stream where it stopped: the sampler draws
                 # token g from the stream keyed by the seed at counter g + offset (ops/reference.py draw_seed,
                 # sampling.hip), and this incarnation's g restarts at 0 after len(resumed) tokens
@@ -244,6 +278,13 @@ class LLMEngine:
                                     defer_table=self.prefill_chunk is not None))
                 self._prefilling.append(req)
             r.set_slots(entries)  # one batched host -> device transfer for every admitted request
+            if self.prefix_cache and admitted:
+                # forks of partly matching cached blocks: one launch, ahead of the prefills on the same stream; the
+                # sources stay pinned in the scheduler until the copy is enqueued
+                copies = self.sched.take_copies()
+                if copies:
+                    r.copy_kv_blocks(copies)
+                self.sched.copies_done()
             if self._prefilling:
                 done_now = self._prefill_some()
                 t1 = time.perf_counter()
@@ -423,7 +464,10 @@ class LLMEngine:
         q.params = dataclasses.replace(q.params, max_tokens=q.params.max_tokens - n)
         self.runner.release_slot(q.slot)
         self._slot_owner.pop(q.slot, None)
-        self.sched.preempt(q.rid, len(q.ctx_ids), q.params.max_tokens)
+        if self.prefix_cache:  # with its tokens, so that the resumed request can hit its own blocks if they survive
+            self.sched.preempt(q.rid, len(q.ctx_ids), q.params.max_tokens, q.ctx_ids)
+        else:
+            self.sched.preempt(q.rid, len(q.ctx_ids), q.params.max_tokens)
         q.slot, q.gen_host, q.prefilled = -1, 0, 0
         q.preemptions += 1
         self.stats["preempted"] += 1
@@ -460,6 +504,9 @@ class LLMEngine:
                 if req.stream is not None:
                     req.stream.put(("done", None))
                 out.append(req)
+            if self.prefix_cache:  # the device state is suspect after a failed step: keep no KV from before it
+                self.sched.copies_done()
+                self.sched.reset_prefix_cache()
             self._reqs.clear()
             self._slot_owner.clear()
             self._prefilling.clear()
@@ -496,6 +543,9 @@ class LLMEngine:
             self.runner.prefill_chunk(partial)
         if final:
             self._prefill_packed(final, any_sample)
+        if self.prefix_cache:  # the prompt's last chunk is launched: its full blocks may be shared from now on
+            for q in done:
+                self.sched.publish(q.rid)
         return done
 
     def _prefill_packed(self, seqs, any_sample: bool) -> None:
@@ -537,7 +587,8 @@ class LLMEngine:
             text=text, token_ids=req.output_ids, prompt_tokens=len(req.prompt_ids), eval_count=len(req.output_ids),
             total_duration_ns=ns(req.finished_at - req.arrival), load_duration_ns=ns(self.load_time_s),
             prompt_eval_duration_ns=ns(req.first_token - req.admitted),
-            eval_duration_ns=ns(req.finished_at - req.first_token), done_reason="stop" if ended_eos else "length")
+            eval_duration_ns=ns(req.finished_at - req.first_token), done_reason="stop" if ended_eos else "length",
+            cached_prompt_tokens=req.cached_tokens)
 
     def text_of(self, token_ids: Sequence[int], req: Request) -> str:
         """The response text of ``token_ids`` exactly as ``result`` builds it (stop strings applied)."""

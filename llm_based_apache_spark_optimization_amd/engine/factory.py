@@ -18,12 +18,16 @@ def build_engine(model: str, device: Optional[str] = None, checkpoint: Optional[
                  max_prefill_tokens: int = 16384, kv_memory_fraction: float = 0.85,
                  warm_graphs: bool = False, prefill_chunk: Optional[int] = None,
                  kv_dtype: Optional[str] = None, max_new_cap: Optional[int] = None,
-                 kv_reserve_tokens: int = 64, spec_tokens: int = 0) -> LLMEngine:
+                 kv_reserve_tokens: int = 64, spec_tokens: int = 0, prefix_cache: bool = False,
+                 prefix_cow_min_tokens: Optional[int] = None) -> LLMEngine:
     """kv_dtype: paged KV cache dtype, "bf16" | "fp8" (None: LSA_KV_FP8, default bf16).
     max_new_cap: generated-token cap per request (None: the context window).
     kv_reserve_tokens: generated tokens whose KV is reserved at admission (the rest grows lazily; < 0 reserves
     prompt + max_new up front).
-    spec_tokens: tokens drafted per step by prompt-lookup speculative decoding for batch-1 greedy requests (0 = off)."""
+    spec_tokens: tokens drafted per step by prompt-lookup speculative decoding for batch-1 greedy requests (0 = off).
+    prefix_cache: keep the KV blocks of full prompt blocks after their request and share them with later requests
+    whose prompt starts with the same tokens (off by default); prefix_cow_min_tokens: the shortest common prefix
+    with a cached block that is worth forking it (None: the scheduler's default)."""
     if device is None:
         device = f"cuda:{torch.cuda.current_device()}" if torch.cuda.is_available() else "cpu"
     t0 = time.perf_counter()
@@ -39,7 +43,8 @@ def build_engine(model: str, device: Optional[str] = None, checkpoint: Optional[
                          num_kv_blocks=num_kv_blocks, kv_memory_fraction=kv_memory_fraction, kv_dtype=kv_dtype,
                          max_new_cap=max_new_cap, spec_tokens=spec_tokens)
     eng = LLMEngine(runner, tok, sync_every=sync_every, max_prefill_tokens=max_prefill_tokens, name=model,
-                    prefill_chunk=prefill_chunk or None, kv_reserve_tokens=kv_reserve_tokens, spec_tokens=spec_tokens)
+                    prefill_chunk=prefill_chunk or None, kv_reserve_tokens=kv_reserve_tokens, spec_tokens=spec_tokens,
+                    prefix_cache=prefix_cache, prefix_cow_min_tokens=prefix_cow_min_tokens)
     if torch.device(device).type == "cuda":
         if warm_graphs:
             runner.capture_all()

@@ -240,6 +240,11 @@ class ModelRunner:
         self.h_alt = torch.zeros(1, self.d, **f32)  # the residual stream's second buffer (h_out never aliases h)
         self.graphs: dict = {}
         self._pending_bt: dict = {}  # slot -> block-table row of a prompt still being prefilled in chunks
+        # Prefix cache (set by LLMEngine(prefix_cache=True)): a row that finishes with its prefill token parks at
+        # position prompt_len instead of prompt_len - 1.  A finished row keeps rewriting the KV row of its position
+        # while the decode graph replays, and prompt_len - 1 lies in a published (shared) block when the prompt fills
+        # its last block exactly; prompt_len is always in the request's own blocks (admission reserves it).
+        self.park_past_prompt = False
         if self.tp is not None and self.tp.size > 1 and self.on_gpu:
             self.tp.warmup()  # communicators (RCCL + the one-shot IPC all-reduce) before any launch
             if not self.tp.capturable():  # gloo without the IPC kernel (test boxes): eager decode steps
@@ -981,6 +986,13 @@ class ModelRunner:
             assert int(sl) not in self._pending_bt, "growing a slot whose prompt is still being prefilled"
         self.block_tables.index_copy_(0, idx.to(self.device, non_blocking=True), rows.to(self.device, non_blocking=True))
 
+    def copy_kv_blocks(self, pairs: Sequence[tuple]) -> None:
+        """Prefix cache: fork cached KV blocks, ``pairs`` = [(src, dst)] block ids of this runner's arena
+        (ops.kv_copy_blocks).  Runs eagerly on the engine's stream, which orders it before the prefill that writes
+        the rest of dst and attends to it, and before any later write of a src that is evicted meanwhile."""
+        if pairs:
+            ops.kv_copy_blocks(self.kv, self.kv_scale, pairs)
+
     def set_eos(self, ids: Sequence[int]) -> None:
         """Replace the stop-token set (same length keeps captured graphs valid; otherwise recapture)."""
         ids = list(ids) or [-1]
@@ -1083,7 +1095,7 @@ class ModelRunner:
         self.out_tokens.index_copy_(0, slot_t, out_t)
         self.gen_len.index_copy_(0, slot_t, gl)
         self.input_ids.index_copy_(0, slot_t, iid)
-        self.positions.index_copy_(0, slot_t, pp)
+        self.positions.index_copy_(0, slot_t, pp + fin if self.park_past_prompt else pp)
         self.finished.index_copy_(0, slot_t, fin)
 
     def _prefill_layers(self, T, ids, posd, tsd, bt, cud, ctxd, last, work, n, commit):

@@ -1481,6 +1481,29 @@ def attn_verify(q, kc, vc, block_table, pos0, H, Hkv, scale, out, workspace=None
     return out
 
 
+def kv_copy_blocks(kv: torch.Tensor, kv_scale: Optional[torch.Tensor], pairs) -> None:
+    """Prefix cache: copy whole KV blocks inside the arena, ``pairs`` = host list of (src, dst) block ids
+    (kernels/kv_copy.hip): for every layer, K and V, the [Hkv, 64, 128] tile of block src and its scale tile land in
+    block dst.  kv [L, 2, NB, Hkv, 64, 128] bf16 or e4m3 bytes, kv_scale [L, 2, NB, Hkv, 64] f32 or None.  The ids
+    are checked here, before anything is uploaded or launched: 0 < id < NB (block 0 is the idle rows' scratch),
+    src != dst, no dst listed twice and no dst that is also a src (the copies of one launch run in no order)."""
+    pairs = [(int(s), int(d)) for s, d in pairs]
+    if not pairs:
+        return
+    if kv.dim() != 6:
+        raise ValueError("kv must be the [L, 2, NB, Hkv, 64, 128] arena")
+    NB = kv.shape[2]
+    srcs, dsts = {s for s, _ in pairs}, [d for _, d in pairs]
+    if any(not (0 < s < NB and 0 < d < NB) or s == d for s, d in pairs):
+        raise ValueError(f"kv_copy_blocks: block ids must satisfy 0 < id < {NB} and src != dst: {pairs}")
+    if len(set(dsts)) != len(dsts) or srcs & set(dsts):
+        raise ValueError(f"kv_copy_blocks: a destination is listed twice or is also a source: {pairs}")
+    if not _gpu(kv):
+        return ref.kv_copy_blocks(kv, kv_scale, pairs)
+    host = torch.tensor(pairs, dtype=torch.int32).pin_memory()  # the ids travel in one pinned transfer
+    ext().kv_copy_blocks(kv, kv_scale, host.to(kv.device, non_blocking=True))
+
+
 def spec_draft(prompt_tok, prompt_len, out_tokens, gen_len, input_ids, positions, k, spec_ids, spec_pos, spec_draft_out,
                n_max: int = 3, n_min: int = 1, forced=None):
     """Prompt-lookup drafter, one row per entry of ``prompt_len`` (kernels/spec.hip).  forced [nf, k] int32 replaces

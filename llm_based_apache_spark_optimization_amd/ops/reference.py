@@ -203,6 +203,19 @@ def argmax_commit(logits, out_tokens, gen_len, input_ids, positions, finished, e
     commit(logits.float().argmax(-1), out_tokens, gen_len, input_ids, positions, finished, eos, limit, eos_on)
 
 
+# ----------------------------------------------------------------------------------- prefix cache
+def kv_copy_blocks(kv, kv_scale, pairs):
+    """Copy the whole KV block src to dst, with its scales, in every layer for K and V (csrc/kernels/kv_copy.hip);
+    kv [L, 2, NB, Hkv, 64, D], kv_scale [L, 2, NB, Hkv, 64] or None, pairs a validated list of (src, dst)."""
+    if not pairs:
+        return
+    src = torch.tensor([s for s, _ in pairs], dtype=torch.long, device=kv.device)
+    dst = torch.tensor([d for _, d in pairs], dtype=torch.long, device=kv.device)
+    kv.index_copy_(2, dst, kv.index_select(2, src))
+    if kv_scale is not None:
+        kv_scale.index_copy_(2, dst, kv_scale.index_select(2, src))
+
+
 # ----------------------------------------------------------------------------------- speculative decoding
 def attn_verify(q, kc, vc, block_table, pos0, H, Hkv, scale, out):
     """Attention of the T = q.shape[0] new tokens of ONE sequence (their K / V already appended): row t is a decode

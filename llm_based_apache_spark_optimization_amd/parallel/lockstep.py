@@ -31,7 +31,7 @@ log = logging.getLogger(__name__)
 
 # ModelRunner methods that launch kernels or mutate device-resident state
 MUTATORS = frozenset({"set_slot", "set_slots", "extend_tables", "release_slot", "prefill", "prefill_chunk", "decode", "set_eos", "capture",
-                      "capture_all"})
+                      "capture_all", "copy_kv_blocks"})
 
 
 class LeaderChannel:

@@ -74,9 +74,13 @@ class _PyBlockAllocator:
 
 
 class _PyScheduler:
-    """Pure-Python twin of csrc/runtime/runtime_core.h Scheduler (lazy KV reservation + preemption)."""
+    """Pure-Python twin of csrc/runtime/runtime_core.h Scheduler (lazy KV reservation + preemption + the prefix
+    cache: see the comment there for the index, its safety invariant and the eviction rule)."""
 
-    def __init__(self, num_blocks, block_size, max_slots, max_prefill_tokens, max_blocks_per_seq, reserve_tokens=64):
+    COW_MIN_TOKENS = 8  # Scheduler::kCowMinTokens (the measurement behind it is quoted there)
+
+    def __init__(self, num_blocks, block_size, max_slots, max_prefill_tokens, max_blocks_per_seq, reserve_tokens=64,
+                 prefix_cache=False, cow_min_tokens=COW_MIN_TOKENS):
         self._alloc = _PyBlockAllocator(num_blocks, block_size)
         self._max_slots, self._budget, self._maxb = max_slots, max_prefill_tokens, max_blocks_per_seq
         self._reserve = reserve_tokens
@@ -84,8 +88,15 @@ class _PyScheduler:
         self._waiting = collections.deque()
         self._reqs = {}
         self._admits = 0
+        # prefix cache: node id -> {parent, toks, block, ref, children (insertion order), tick}; 0 is the root
+        self._cache, self._cow_min = bool(prefix_cache), max(1, int(cow_min_tokens))
+        self._nodes = {0: {"parent": -1, "toks": (), "block": -1, "ref": 0, "children": [], "tick": 0}}
+        self._next_node = 1
+        self._evictable = 0
+        self._clock = 0
+        self._copies, self._pins = [], []
 
-    def add(self, rid, prompt_len, max_new):
+    def add(self, rid, prompt_len, max_new, tokens=(), cacheable=True):
         if rid in self._reqs:
             raise ValueError("duplicate request id")
         if prompt_len < 1 or max_new < 1:
@@ -95,31 +106,198 @@ class _PyScheduler:
             raise ValueError("request exceeds max model length")
         if need > self._alloc.num_blocks - 1:
             raise ValueError("request larger than the whole KV cache")
-        self._reqs[rid] = {"p": prompt_len, "n": max_new, "slot": -1, "blocks": [], "seq": -1}
+        cache = self._cache and cacheable
+        if cache and len(tokens) != prompt_len:
+            raise ValueError("tokens must hold prompt_len ids")
+        self._reqs[rid] = {"p": prompt_len, "n": max_new, "slot": -1, "blocks": [], "seq": -1,
+                           "tokens": [int(t) for t in tokens] if cache else [], "cacheable": cache,
+                           "published": False, "cached": 0, "nodes": []}
         self._waiting.append(rid)
 
     def _admit_blocks(self, r):
         gen = r["n"] if self._reserve < 0 else min(r["n"], self._reserve)
         return self._alloc.blocks_for(r["p"] + gen)
 
+    # ------------------------------------------------------------------------------ prefix cache
+    def _available(self):
+        return self._alloc.num_free + self._evictable
+
+    def _ref(self, n):
+        nd = self._nodes[n]
+        if nd["ref"] == 0:
+            self._evictable -= 1
+        nd["ref"] += 1
+
+    def _unref(self, n):
+        nd = self._nodes[n]
+        nd["ref"] -= 1
+        if nd["ref"] == 0:
+            self._evictable += 1
+
+    def _chain_of(self, n):
+        while n > 0:
+            yield n
+            n = self._nodes[n]["parent"]
+
+    def _find_child(self, parent, toks):
+        for c in self._nodes[parent]["children"]:
+            if self._nodes[c]["toks"] == toks:
+                return c
+        return -1
+
+    def _match(self, r):
+        """(chain, src, p): the longest chain of cached blocks that prefixes the prompt (at least the last prompt
+        token stays to be computed), then the best partial match among the last node's children (the fork)."""
+        bs, toks = self._alloc.block_size, r["tokens"]
+        chain, node = [], 0
+        for i in range((r["p"] - 1) // bs):
+            c = self._find_child(node, tuple(toks[i * bs:(i + 1) * bs]))
+            if c < 0:
+                break
+            chain.append(c)
+            node = c
+        base = len(chain) * bs
+        limit = min(bs - 1, r["p"] - 1 - base)
+        best, src = 0, -1
+        for c in self._nodes[node]["children"]:
+            t, p = self._nodes[c]["toks"], 0
+            while p < limit and t[p] == toks[base + p]:
+                p += 1
+            if p > best:
+                best, src = p, c
+        if best < self._cow_min:
+            best, src = 0, -1
+        return chain, src, best
+
+    def _evict_one(self):
+        best = -1
+        for n, nd in self._nodes.items():
+            if n == 0 or nd["ref"] != 0 or nd["children"]:
+                continue
+            if best < 0 or (nd["tick"], nd["block"]) < (self._nodes[best]["tick"], self._nodes[best]["block"]):
+                best = n
+        if best < 0:
+            return False
+        nd = self._nodes.pop(best)
+        self._nodes[nd["parent"]]["children"].remove(best)
+        self._alloc.release([nd["block"]])
+        self._evictable -= 1
+        return True
+
+    def _take(self, n):
+        while self._alloc.num_free < n:
+            if not self._evict_one():
+                raise RuntimeError("KV cache exhausted")
+        return self._alloc.alloc(n)
+
+    def _release_blocks(self, r):
+        priv = r["blocks"][len(r["nodes"]):]
+        if priv:
+            self._alloc.release(priv)
+        if r["nodes"]:
+            self._clock += 1
+            for n in r["nodes"]:
+                self._nodes[n]["tick"] = self._clock
+                self._unref(n)
+        r.update(blocks=[], nodes=[], cached=0, published=False)
+
+    def cached_tokens(self, rid):
+        return self._reqs[rid]["cached"]
+
+    def shared_blocks(self, rid):
+        return len(self._reqs[rid]["nodes"])
+
+    def take_copies(self):
+        out, self._copies = self._copies, []
+        return out
+
+    def copies_done(self):
+        for n in self._pins:
+            for a in list(self._chain_of(n)):
+                self._unref(a)
+        self._pins, self._copies = [], []
+
+    def publish(self, rid):
+        r = self._reqs[rid]
+        if not r["cacheable"] or r["slot"] < 0 or r["published"]:
+            return 0
+        r["published"] = True
+        bs = self._alloc.block_size
+        self._clock += 1
+        added = 0
+        for i in range(len(r["nodes"]), r["p"] // bs):
+            parent = r["nodes"][-1] if r["nodes"] else 0
+            toks = tuple(r["tokens"][i * bs:(i + 1) * bs])
+            if self._find_child(parent, toks) >= 0:
+                break
+            n, self._next_node = self._next_node, self._next_node + 1
+            self._nodes[n] = {"parent": parent, "toks": toks, "block": r["blocks"][i], "ref": 1, "children": [],
+                              "tick": self._clock}
+            self._nodes[parent]["children"].append(n)
+            r["nodes"].append(n)
+            added += 1
+        return added
+
+    def reset_prefix_cache(self):
+        n = 0
+        while self._evict_one():
+            n += 1
+        return n
+
+    @property
+    def cached_blocks(self):
+        return len(self._nodes) - 1
+
+    @property
+    def prefix_cache(self):
+        return self._cache
+
+    @property
+    def cow_min_tokens(self):
+        return self._cow_min
+
+    def prefix_nodes(self):
+        return sorted([nd["block"], nd["ref"], len(nd["children"]), nd["tick"],
+                       self._nodes[nd["parent"]]["block"] if nd["parent"] > 0 else -1]
+                      for n, nd in self._nodes.items() if n)
+
+    # ------------------------------------------------------------------------------ scheduling
     def admit(self):
         out, budget = [], self._budget
+        bs = self._alloc.block_size
         while self._waiting:
             r = self._reqs[self._waiting[0]]
-            if out and r["p"] > budget:
+            chain, src, p = self._match(r) if r["cacheable"] else ([], -1, 0)
+            cached = len(chain) * bs + p
+            if out and r["p"] - cached > budget:
                 break
-            need = self._admit_blocks(r)
-            if not self._alloc.can_alloc(need):
-                break
+            need = self._admit_blocks(r) - len(chain)
+            pinned = chain + (list(self._chain_of(src)) if src >= 0 else [])
+            for n in pinned:
+                self._ref(n)
             try:
                 slot = self._slots.index(-1)
             except ValueError:
+                slot = -1
+            if self._available() < need or slot < 0:
+                for n in pinned:
+                    self._unref(n)
                 break
             rid = self._waiting.popleft()
+            if r["cacheable"]:
+                self._clock += 1
+            for n in chain:
+                self._nodes[n]["tick"] = self._clock
+            priv = self._take(need)
+            if src >= 0:
+                self._nodes[src]["tick"] = self._clock
+                self._copies.append((self._nodes[src]["block"], priv[0]))
+                self._pins.append(src)
             self._admits += 1
-            r["blocks"], r["slot"], r["seq"] = self._alloc.alloc(need), slot, self._admits
+            r.update(nodes=list(chain), blocks=[self._nodes[n]["block"] for n in chain] + priv, cached=cached,
+                     slot=slot, seq=self._admits)
             self._slots[slot] = rid
-            budget -= r["p"]
+            budget -= r["p"] - cached
             out.append(rid)
         return out
 
@@ -131,20 +309,24 @@ class _PyScheduler:
         add = want - len(r["blocks"])
         if add <= 0:
             return 0
-        if not self._alloc.can_alloc(add):
+        if self._available() < add:
             return -1
-        r["blocks"] += self._alloc.alloc(add)
+        r["blocks"] += self._take(add)
         return add
 
-    def preempt(self, rid, prompt_len, max_new):
+    def preempt(self, rid, prompt_len, max_new, tokens=()):
         r = self._reqs[rid]
         if r["slot"] < 0:
             raise ValueError("preempt: request is not running")
         if prompt_len < 1 or max_new < 1 or self._alloc.blocks_for(prompt_len + max_new) > self._maxb:
             raise ValueError("preempt: bad resumed lengths")
+        if r["cacheable"] and len(tokens) != prompt_len:
+            raise ValueError("tokens must hold prompt_len ids")
         self._slots[r["slot"]] = -1
-        self._alloc.release(r["blocks"])
-        r.update(slot=-1, blocks=[], seq=-1, p=prompt_len, n=max_new)
+        self._release_blocks(r)
+        r.update(slot=-1, seq=-1, p=prompt_len, n=max_new)
+        if r["cacheable"]:
+            r["tokens"] = [int(t) for t in tokens]
         self._waiting.appendleft(rid)
 
     def youngest_first(self):
@@ -156,8 +338,7 @@ class _PyScheduler:
             return
         if r["slot"] >= 0:
             self._slots[r["slot"]] = -1
-        if r["blocks"]:
-            self._alloc.release(r["blocks"])
+        self._release_blocks(r)
         if rid in self._waiting:
             self._waiting.remove(rid)
 
@@ -190,11 +371,11 @@ class _PyScheduler:
 
     @property
     def kv_usage(self):
-        return 1.0 - self._alloc.num_free / (self._alloc.num_blocks - 1)
+        return 1.0 - self._available() / (self._alloc.num_blocks - 1)
 
     @property
     def free_blocks(self):
-        return self._alloc.num_free
+        return self._available()
 
     @property
     def reserve_tokens(self):

@@ -200,6 +200,8 @@ def export_backend_gauges(backend) -> None:
             REGISTRY.set("lsa_engine_running", e.get("running", 0), "running requests", model=m, **lbl)
             REGISTRY.set("lsa_engine_waiting", e.get("waiting", 0), "queued requests", model=m, **lbl)
             REGISTRY.set("lsa_engine_kv_usage", e.get("kv_usage", 0.0), "KV cache fraction in use", model=m, **lbl)
+            REGISTRY.set("lsa_engine_prefix_cached_blocks", e.get("prefix_cached_blocks", 0),
+                         "KV blocks held by the prefix cache's index", model=m, **lbl)
             REGISTRY.set("lsa_engine_alive", 1.0 if e.get("alive", True) else 0.0, "engine loop alive", model=m, **lbl)
             REGISTRY.set("lsa_engine_restarts", e.get("restarts", 0) + e.get("rebuilds", 0),
                          "engine recoveries (loop restarts + rebuilds)", model=m, **lbl)

@@ -30,7 +30,9 @@ def engine_factory(settings: Settings, tp_factory=None):
                            kv_memory_fraction=settings.kv_memory_fraction, warm_graphs=True, tp=tp,
                            prefill_chunk=settings.prefill_chunk, kv_dtype=settings.kv_dtype,
                            max_new_cap=settings.max_new_cap or None,
-                           kv_reserve_tokens=settings.kv_reserve_tokens, spec_tokens=settings.spec_tokens)
+                           kv_reserve_tokens=settings.kv_reserve_tokens, spec_tokens=settings.spec_tokens,
+                           prefix_cache=settings.prefix_cache,
+                           prefix_cow_min_tokens=settings.prefix_cow_min_tokens)
         if settings.spec_min_accept >= 0:
             eng.runner.spec_min_accept = settings.spec_min_accept
         return eng
