@@ -57,7 +57,7 @@ int lsa_argmax_commit(const float* logits, int B, int V, unsigned long long* par
                       const int* limit, const int* eos_on, hipStream_t s);
 int lsa_attn_verify(const void* q, const void* kc, const void* vc, const int* bt, int max_blocks, const int* pos0, int T,
                     int H, int Hkv, float scale, int chunk_blocks, int nsplit, int unsplit_max, void* out, float* opart,
-                    float* mlpart, int* counters, hipStream_t s);
+                    float* mlpart, int* counters, hipStream_t s, const float* ks = nullptr, const float* vs = nullptr);
 int lsa_kv_copy_blocks(void* kv, void* scale, const int* pairs, int npairs, int planes, int nb, long long tile_bytes,
                        long long scale_bytes, hipStream_t s);
 int lsa_spec_draft(const int* prompt_tok, int prompt_ld, const int* prompt_len, const int* out_tokens, int max_new,
@@ -903,10 +903,11 @@ void argmax_commit(const at::Tensor& logits, at::Tensor& part, at::Tensor& out_t
 // speculative decoding: attention of the T = k + 1 verify rows of one sequence (kernels/attention_verify.hip)
 void attn_verify(const at::Tensor& q, const at::Tensor& kc, const at::Tensor& vc, const at::Tensor& block_table,
                  const at::Tensor& pos0, int64_t H, int64_t Hkv, double scale, int64_t chunk_blocks, int64_t nsplit,
-                 int64_t unsplit_max, at::Tensor& out, at::Tensor& opart, at::Tensor& mlpart, at::Tensor& counters) {
+                 int64_t unsplit_max, at::Tensor& out, at::Tensor& opart, at::Tensor& mlpart, at::Tensor& counters,
+                 const c10::optional<at::Tensor>& ks = c10::nullopt, const c10::optional<at::Tensor>& vs = c10::nullopt) {
   need(q, at::kBFloat16, "q");
   need(out, at::kBFloat16, "out");
-  check_cache(kc, vc, c10::nullopt, c10::nullopt);
+  check_cache(kc, vc, ks, vs);  // bf16 cache without scales, e4m3 bytes with both
   need(pos0, at::kInt, "pos0");
   need(block_table, at::kInt, "block_table");
   TORCH_CHECK(q.dim() == 3 && q.size(1) == H && q.size(2) == 128 && q.is_contiguous(), "q: contiguous [T, H, 128]");
@@ -927,7 +928,7 @@ void attn_verify(const at::Tensor& q, const at::Tensor& kc, const at::Tensor& vc
   check(lsa_attn_verify(q.data_ptr(), kc.data_ptr(), vc.data_ptr(), block_table.data_ptr<int>(), block_table.numel(),
                         pos0.data_ptr<int>(), T, H, Hkv, (float)scale, chunk_blocks, nsplit, (int)unsplit_max,
                         out.data_ptr(), opart.data_ptr<float>(), mlpart.data_ptr<float>(), counters.data_ptr<int>(),
-                        cur_stream()),
+                        cur_stream(), ptr<const float>(ks), ptr<const float>(vs)),
         "attn_verify");
 }
 
@@ -1212,7 +1213,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("sample_commit", &sample_commit);
   m.def("attn_verify", &attn_verify, py::arg("q"), py::arg("kc"), py::arg("vc"), py::arg("block_table"),
         py::arg("pos0"), py::arg("H"), py::arg("Hkv"), py::arg("scale"), py::arg("chunk_blocks"), py::arg("nsplit"),
-        py::arg("unsplit_max"), py::arg("out"), py::arg("opart"), py::arg("mlpart"), py::arg("counters"));
+        py::arg("unsplit_max"), py::arg("out"), py::arg("opart"), py::arg("mlpart"), py::arg("counters"),
+        py::arg("ks") = py::none(), py::arg("vs") = py::none());
   m.def("spec_draft", &spec_draft, py::arg("prompt_tok"), py::arg("prompt_len"), py::arg("out_tokens"),
         py::arg("gen_len"), py::arg("input_ids"), py::arg("positions"), py::arg("k"), py::arg("n_max"), py::arg("n_min"),
         py::arg("forced"), py::arg("spec_ids"), py::arg("spec_pos"), py::arg("spec_draft"));

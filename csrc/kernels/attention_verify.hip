@@ -1,5 +1,5 @@
-// Verify attention of speculative decoding: the T = k + 1 new tokens of ONE sequence against the paged bf16 KV
-// cache (layout of attention.hip: [num_blocks, Hkv, 64 tokens, 128]), head_dim 128.
+// Verify attention of speculative decoding: the T = k + 1 new tokens of ONE sequence against the paged KV cache
+// (layout of attention.hip: [num_blocks, Hkv, 64 tokens, 128]; bf16, or -- KV8 -- the fp8 cache), head_dim 128.
 //
 //   attn_verify_kernel   split-KV like attn_decode_kernel, grid (Hkv, nsplit), 4 waves.  All R = T * G query rows
 //                        (row r = t * G + g: token t, head hk * G + g; R <= 16) of a kv head are the 16-wide side of
@@ -21,10 +21,24 @@
 //                        protocol of attn_decode_kernel; the ticket word is left zeroed).
 //                        Everything data-dependent (pos0, the block table) is read from device memory: a captured
 //                        graph replays.  Fixed reduction order: two runs are bitwise equal.
+//   attn_verify_kernel<true>   the same kernel over the fp8 cache (attn_decode_kernel<.., KV8>'s layout: 8 KiB of e4m3
+//                        bytes per (block, kv-head) tile in the token-pair order of common.h kv8_off, f32 scales
+//                        ksc / vsc [blocks, Hkv, 64] in token order).  Same grid, wave / key ownership, split combine
+//                        and reduction order; half the K / V bytes:
+//                          K   lane (g, r) loads the four 8-byte halves of key 16 w + r's chunks (dims 32 s + 8 g .. + 7)
+//                              and widens them exactly to bf16 (v_cvt_scalef32_pk_bf16_fp8 at scale 1) as the A operand;
+//                              the key's scale x the softmax scale multiplies the score (one float4 load per lane: the
+//                              scales of keys 16 w + 4 g .. + 3, the four scores the lane owns);
+//                          V   two 16-byte units per lane (token pair 8 w + 4 i + g, dims 8 r .. + 7), each half widened
+//                              to bf16 into the same XOR-swizzled LDS image; the value's scale is folded into p before P
+//                              is packed to bf16, the row sum l keeps the unscaled p.  A masked key (past a row's limit,
+//                              the pair partner of the last visible key included) contributes p = 0 and its scales are
+//                              never used.
 //
 // hipcc --offload-arch=gfx950 -O3 -Rpass-analysis=kernel-resource-usage: 164 VGPRs + 32 AGPRs, 44 SGPRs, scratch 0,
 // no spills, LDS 49668 bytes per workgroup, occupancy 2 waves per SIMD (the grid is Hkv x nsplit <= ~256 workgroups of
-// 4 waves: at most one workgroup per CU is resident anyway)
+// 4 waves: at most one workgroup per CU is resident anyway).  KV8: 134 VGPRs + 32 AGPRs, 50 SGPRs, scratch 0, no
+// spills, LDS 49668 bytes, occupancy 3.
 #include "common.h"
 
 #define LSA_NEG (-1.0e30f)
@@ -44,13 +58,21 @@ __device__ __forceinline__ int av_v_off(int r, int col) {
   return r * 128 + ((((col >> 3) ^ ((r & 7) << 1))) << 3) + (col & 7);
 }
 
+typedef uint32_t av_u32x2_t __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint2 av_ldg_nt8(const uint8_t* p) {
+  const av_u32x2_t v = __builtin_nontemporal_load(reinterpret_cast<const av_u32x2_t*>(p));
+  return make_uint2(v[0], v[1]);
+}
+
+template <bool KV8>
 __global__ __launch_bounds__(256) void attn_verify_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ kc,
                                                           const uint16_t* __restrict__ vc,
                                                           const int* __restrict__ bt, int max_blocks,
                                                           const int* __restrict__ pos0_p, int T, int G, int Hkv,
                                                           float scale_log2, int chunk_blocks, int nsplit, int unsplit_max,
                                                           uint16_t* __restrict__ out, float* __restrict__ opart,
-                                                          float* __restrict__ mlpart, int* __restrict__ counters) {
+                                                          float* __restrict__ mlpart, int* __restrict__ counters,
+                                                          const float* __restrict__ ksc, const float* __restrict__ vsc) {
   constexpr int D = 128;
   __shared__ __attribute__((aligned(16))) uint16_t Vs[64 * D];   // wave w writes and reads rows 16 w .. 16 w + 15 only
   __shared__ __attribute__((aligned(16))) float so[4][16][D];    // per-wave partial outputs
@@ -89,24 +111,57 @@ __global__ __launch_bounds__(256) void attn_verify_kernel(const uint16_t* __rest
   // register staging of the next block's K (A operand rows) and V (row-major chunks for the LDS image), issued
   // right after the current block's registers are consumed (block index clamped: no conditional refill)
   uint4 kr[4], vr[4];
+  // KV8: the lane's K chunks are the 8-byte halves of four token-pair units (kv8_off: key 16 w + r, dims 32 s + 8 g);
+  // a V unit carries dims 8 r .. 8 r + 7 of the token pair 8 w + 4 i + g; one float4 holds the scales of keys
+  // 16 w + 4 g .. + 3, the keys whose scores (and p) this lane owns
+  uint2 kr8[4];
+  uint4 vr8[2];
+  float4 ksr, vsr;
   auto fetch = [&](int blk) {
-    const size_t base = ((size_t)__builtin_amdgcn_readfirstlane(bt[blk]) * Hkv + hk) * 64 * D;
+    if constexpr (KV8) {
+      const size_t rowb = ((size_t)__builtin_amdgcn_readfirstlane(bt[blk]) * Hkv + hk) * 64;
+      const uint8_t* k8 = reinterpret_cast<const uint8_t*>(kc) + rowb * D;
+      const uint8_t* v8 = reinterpret_cast<const uint8_t*>(vc) + rowb * D;
 #pragma unroll
-    for (int s = 0; s < 4; ++s)
-      kr[s] = ldg_nt(reinterpret_cast<const uint4*>(kc + base + (16 * w + r) * D + 32 * s + 8 * g));
+      for (int s = 0; s < 4; ++s) kr8[s] = av_ldg_nt8(k8 + kv8_off(16 * w + r, 32 * s + 8 * g));
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
-      vr[i] = ldg_nt(reinterpret_cast<const uint4*>(vc + base + (16 * w + 4 * i + g) * D + 8 * r));
+      for (int i = 0; i < 2; ++i)
+        vr8[i] = ldg_nt(reinterpret_cast<const uint4*>(v8 + kv8_off(16 * w + 8 * i + 2 * g, 8 * r)));
+      ksr = *reinterpret_cast<const float4*>(ksc + rowb + 16 * w + 4 * g);
+      vsr = *reinterpret_cast<const float4*>(vsc + rowb + 16 * w + 4 * g);
+    } else {
+      const size_t base = ((size_t)__builtin_amdgcn_readfirstlane(bt[blk]) * Hkv + hk) * 64 * D;
+#pragma unroll
+      for (int s = 0; s < 4; ++s)
+        kr[s] = ldg_nt(reinterpret_cast<const uint4*>(kc + base + (16 * w + r) * D + 32 * s + 8 * g));
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        vr[i] = ldg_nt(reinterpret_cast<const uint4*>(vc + base + (16 * w + 4 * i + g) * D + 8 * r));
+    }
   };
   if (blk0 < blk1) fetch(blk0);
   const int qq = r >> 2, pp = r & 3;
   for (int blk = blk0; blk < blk1; ++blk) {
     __syncthreads();  // the previous block's transposed V reads are done
     uint4 kq[4];
+    float ksl[4], vsl[4];  // KV8: key scale x softmax scale, value scale of keys 16 w + 4 g + i
+    if constexpr (KV8) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      *reinterpret_cast<uint4*>(&Vs[av_v_off(16 * w + 4 * i + g, 8 * r)]) = vr[i];
-      kq[i] = kr[i];
+      for (int i = 0; i < 2; ++i) {  // both tokens of the pair widened exactly to bf16 rows of the same LDS image
+        const int row = 16 * w + 8 * i + 2 * g;
+        *reinterpret_cast<uint4*>(&Vs[av_v_off(row, 8 * r)]) = fp8x8_to_bf16x8(make_uint2(vr8[i].x, vr8[i].y));
+        *reinterpret_cast<uint4*>(&Vs[av_v_off(row + 1, 8 * r)]) = fp8x8_to_bf16x8(make_uint2(vr8[i].z, vr8[i].w));
+      }
+#pragma unroll
+      for (int s = 0; s < 4; ++s) kq[s] = fp8x8_to_bf16x8(kr8[s]);
+      ksl[0] = ksr.x * scale_log2; ksl[1] = ksr.y * scale_log2; ksl[2] = ksr.z * scale_log2; ksl[3] = ksr.w * scale_log2;
+      vsl[0] = vsr.x; vsl[1] = vsr.y; vsl[2] = vsr.z; vsl[3] = vsr.w;
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        *reinterpret_cast<uint4*>(&Vs[av_v_off(16 * w + 4 * i + g, 8 * r)]) = vr[i];
+        kq[i] = kr[i];
+      }
     }
     __syncthreads();
     fetch(min(blk + 1, blk1 - 1));
@@ -121,7 +176,8 @@ __global__ __launch_bounds__(256) void attn_verify_kernel(const uint16_t* __rest
     for (int i = 0; i < 4; ++i) {
       const int key = blk * 64 + 16 * w + 4 * g + i;
       ok[i] = key <= qpos;
-      st[i] = ok[i] ? st[i] * scale_log2 : LSA_NEG;
+      if constexpr (KV8) st[i] = ok[i] ? st[i] * ksl[i] : LSA_NEG;
+      else st[i] = ok[i] ? st[i] * scale_log2 : LSA_NEG;
       tmax = fmaxf(tmax, st[i]);
     }
     tmax = lsa_max_x32(lsa_max_x16(tmax));
@@ -144,8 +200,13 @@ __global__ __launch_bounds__(256) void attn_verify_kernel(const uint16_t* __rest
     // O[query 4 g + i][d 16 dt + r] += P V: A = P (k-slot 8 g + j <-> key 4 g + j, j < 4; slots j >= 4 zero),
     // B = V read transposed: lane (g, r) gets V[keys 4 g .. 4 g + 3][d = 16 dt + r]
     uint4 pa;
-    pa.x = pack2bf(p[0], p[1]);
-    pa.y = pack2bf(p[2], p[3]);
+    if constexpr (KV8) {  // V's row scale rides in p (l keeps the unscaled p); a masked key's scale is never used
+      pa.x = pack2bf(ok[0] ? p[0] * vsl[0] : 0.f, ok[1] ? p[1] * vsl[1] : 0.f);
+      pa.y = pack2bf(ok[2] ? p[2] * vsl[2] : 0.f, ok[3] ? p[3] * vsl[3] : 0.f);
+    } else {
+      pa.x = pack2bf(p[0], p[1]);
+      pa.y = pack2bf(p[2], p[3]);
+    }
     pa.z = 0u;
     pa.w = 0u;
 #pragma unroll
@@ -240,18 +301,26 @@ __global__ __launch_bounds__(256) void attn_verify_kernel(const uint16_t* __rest
 }
 
 // q [T, H, 128] bf16 (rotated); bt: the sequence's block-table row [max_blocks]; pos0: device int32, position of row 0;
+// ks / vs: the fp8 cache's scale arrays [blocks, Hkv, 64] f32 (kc / vc are then e4m3 bytes), null for the bf16 cache;
 // out [T, H * 128] bf16; workspace for T * H rows x nsplit partials and Hkv zeroed tickets (ops.verify_workspace)
 extern "C" int lsa_attn_verify(const void* q, const void* kc, const void* vc, const int* bt, int max_blocks,
                                const int* pos0, int T, int H, int Hkv, float scale, int chunk_blocks, int nsplit,
-                               int unsplit_max, void* out, float* opart, float* mlpart, int* counters, hipStream_t s) {
+                               int unsplit_max, void* out, float* opart, float* mlpart, int* counters, hipStream_t s,
+                               const float* ks = nullptr, const float* vs = nullptr) {
   if (Hkv <= 0 || H <= 0 || H % Hkv) return -1;
   const int G = H / Hkv;
   if (T < 1 || T > 8 || T * G > 16) return -2;
   if (nsplit < 1 || nsplit > 256 || chunk_blocks < 1) return -3;
   if (max_blocks < 1) return -4;
-  hipLaunchKernelGGL(attn_verify_kernel, dim3(Hkv, nsplit), dim3(256), 0, s, reinterpret_cast<const uint16_t*>(q),
-                     reinterpret_cast<const uint16_t*>(kc), reinterpret_cast<const uint16_t*>(vc), bt, max_blocks, pos0,
-                     T, G, Hkv, scale * 1.4426950408889634f, chunk_blocks, nsplit, unsplit_max,
-                     reinterpret_cast<uint16_t*>(out), opart, mlpart, counters);
+  if ((ks == nullptr) != (vs == nullptr)) return -5;  // the fp8 cache needs both scale arrays
+#define LSA_AVL(KV8)                                                                                                  \
+  hipLaunchKernelGGL((attn_verify_kernel<KV8>), dim3(Hkv, nsplit), dim3(256), 0, s,                                   \
+                     reinterpret_cast<const uint16_t*>(q), reinterpret_cast<const uint16_t*>(kc),                     \
+                     reinterpret_cast<const uint16_t*>(vc), bt, max_blocks, pos0, T, G, Hkv,                          \
+                     scale * 1.4426950408889634f, chunk_blocks, nsplit, unsplit_max, reinterpret_cast<uint16_t*>(out), \
+                     opart, mlpart, counters, ks, vs)
+  if (ks != nullptr) LSA_AVL(true);
+  else LSA_AVL(false);
+#undef LSA_AVL
   return (int)hipGetLastError();
 }

@@ -50,6 +50,10 @@ class Settings:
     # request falls back to plain steps; < 0 = the runner's default)
     spec_tokens: int = dataclasses.field(default_factory=lambda: _env("SPEC_TOKENS", 0, int))
     spec_min_accept: float = dataclasses.field(default_factory=lambda: _env("SPEC_MIN_ACCEPT", -1.0, float))
+    # speculate with fp8 / MXFP4 weights and the fp8 KV cache too (off: those engines take plain steps whatever
+    # spec_tokens says).  Opt-in because their verify rows run weight-only GEMMs while the plain batch-1 step may run
+    # e4m3 activations: a speculated request can leave the plain request's token sequence earlier than a near-tie
+    spec_quantized: bool = dataclasses.field(default_factory=lambda: _env("SPEC_QUANTIZED", False, bool))
     # prefix cache (off by default): the KV blocks of full 64-token prompt blocks stay cached after their request and
     # are shared with later requests whose prompt starts with the same tokens; prompts of every caller of one engine
     # share KV then.  prefix_cow_min_tokens: the shortest common prefix with a cached block for which the block is

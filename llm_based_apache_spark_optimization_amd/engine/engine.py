@@ -413,7 +413,7 @@ class LLMEngine:
 
     def _spec_run(self, reqs: list, n_steps: int, remaining: int) -> int:
         """Whether this decode run is a run of verify steps (speculative decoding): returns T = drafted tokens + 1, or
-        0 for the plain run.  Verify steps need the runner's support (TP = 1, bf16 weights and KV cache), exactly one
+        0 for the plain run.  Verify steps need the runner's support (``ModelRunner.spec_supported``), exactly one
         running request, greedy, in slot 0 (decode bucket 1), that has not opted out or been dropped by the acceptance
         guard; room for every position the run may write inside the model window; and the KV blocks of those
         positions without preempting anyone: the worst case is T committed tokens per step plus T - 1 rows of

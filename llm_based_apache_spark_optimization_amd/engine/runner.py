@@ -47,12 +47,16 @@ class ModelRunner:
                  num_kv_blocks: Optional[int] = None, kv_memory_fraction: float = 0.85,
                  max_new_cap: Optional[int] = None, tp=None, use_graphs: bool = True,
                  fuse_rope: Optional[bool] = None, seq_parallel: Optional[bool] = None, sp_min_tokens: Optional[int] = None,
-                 kv_dtype: Optional[str] = None, spec_tokens: int = 0, spec_ngram: tuple = (3, 1)):
+                 kv_dtype: Optional[str] = None, spec_tokens: int = 0, spec_ngram: tuple = (3, 1),
+                 spec_quantized: bool = False):
         self.w = weights
         # prompt-lookup speculative decoding (``_verify_step``): tokens drafted per step (0 = off) and the drafter's
         # (longest, shortest) n-gram.  Plain attributes: an experiment may set them on a built runner.
         self.spec_tokens = int(spec_tokens)
         self.spec_ngram = tuple(spec_ngram)
+        # opt-in: verify steps for fp8 / MXFP4 weights and the fp8 KV cache too (``spec_supported``).  Their verify rows
+        # run the weight-only GEMMs (bf16 activations), whatever the plain batch-1 step of the model runs.
+        self.spec_quantized = bool(spec_quantized)
         # acceptance guard of the engine: a request whose accepted-per-verify-step mean falls below this after 16
         # verify steps takes plain steps for the rest of its life.  Break-even = verify-step time / plain-step time - 1.
         # Measured on MI355X (scripts/bench_spec.py, profiles/spec/spec_decode_mi355x.jsonl; plain vs verify step, k = 3):
@@ -718,11 +722,22 @@ class ModelRunner:
         return max(k, 0)
 
     def spec_supported(self) -> bool:
-        """Whether this runner can run verify steps: TP = 1, bf16 weights, bf16 KV cache, at least one drafted token."""
+        """Whether this runner can run verify steps: TP = 1, at least one drafted token, and either bf16 weights with
+        the bf16 KV cache or -- ``spec_quantized`` -- bf16 / fp8 / MXFP4 weights with the bf16 or the fp8 cache."""
         tps = 1 if self.tp is None else self.tp.size
         bf16 = ("bf16", "dense")  # packed for the GPU / plain on the CPU
-        return (self.spec_tokens > 0 and tps == 1 and not self.kv_fp8 and self.w.layers[0].wqkv.kind in bf16
-                and self.w.lm_head.kind in bf16 and self.spec_k() >= 1)
+        # (a CPU engine keeps every weight dense; it is gated by the kind it was built for, like its GPU twin)
+        kinds = [getattr(w, "requested", None) or w.kind for w in (self.w.layers[0].wqkv, self.w.lm_head)]
+        if self.spec_quantized:
+            dtypes = all(k in bf16 + ("fp8", "mxfp4") for k in kinds)
+        else:
+            dtypes = not self.kv_fp8 and all(k in bf16 for k in kinds)
+        return self.spec_tokens > 0 and tps == 1 and dtypes and self.spec_k() >= 1
+
+    def spec_oracle_plan(self) -> dict:
+        """``oracle_plan`` of the verify rows: every projection weight-only (bf16 activations), no residual-reduce
+        quantisation -- whatever the plain batch-1 step of the same runner runs."""
+        return dict(qkv=False, gate_up=False, o=False, down=False, rr=False)
 
     def _spec_bufs(self) -> dict:
         """Device buffers of the verify step, sized for the largest T this runner can run (8 rows)."""
@@ -774,7 +789,14 @@ class ModelRunner:
         The stale rows p' .. p + T - 1 lie inside the next step's write range p' .. p' + T - 1, so the next step (or
         the next plain step, which writes p' before reading it) overwrites them before any query can see them: row t
         sees only keys <= p' + t.  A finished row keeps its position and rewrites the same T positions when the graph
-        replays; the engine reserves those positions (LLMEngine._spec_run)."""
+        replays; the engine reserves those positions (LLMEngine._spec_run).
+        With the fp8 cache a rejected row's e4m3 bytes and its f32 scale are both overwritten by that next step
+        (rope_append writes a row's bytes and its scale together), so the invariant holds for the pair (bytes, scale).
+        The 16-byte unit that a token pair shares (common.h kv8_off) is safe: each token writes only its own 8 bytes
+        of it, so rewriting a stale odd token never touches its committed even partner, and the other way round.
+
+        fp8 / MXFP4 weights: every verify row runs the weight-only GEMMs (W8A16 / W4A16) through ``ops.linear``, the
+        lm_head included; there are no e4m3 activations in a verify step."""
         w, d, T = self.w, self.d, self.spec_k() + 1
         sb = self._spec_bufs()
         n_max, n_min = self.spec_ngram
@@ -795,6 +817,9 @@ class ModelRunner:
         ssq = sb["ssq"]
         rn = lambda i: dict(rownorm=(ssq[i], self.eps)) if wn else {}  # noqa: E731
         lin = ops.linear if self.on_gpu else self._verify_linear_cpu
+        kvs = self._kv_scales
+        # the CPU twin of the residual-reduce step's SiLU GEMM takes its RMS row scale from the residual row itself
+        rr_cpu = wn and not self.on_gpu and self.rr_decode and not self.rr_a8
         for l, lw in enumerate(w.layers):
             if l == 0 and wn:
                 ops.add_rmsnorm(h, lw.attn_norm, self.eps, xn, ids=ids, emb=w.embed, rows=T, ss_out=ssq.view(-1),
@@ -808,16 +833,16 @@ class ModelRunner:
             pre = {} if (self.on_gpu or l) else dict(pre=True)
             lin(xn, lw.wqkv, "f32", out=qkv_parts, splitk=sk_q, **rn(2 * l), **pre)
             kc, vc = self.kv[l, 0], self.kv[l, 1]
-            ops.rope_append(qkv_parts, pos, sb["seq0"][:T], bt, self.cos, self.sin, q, kc, vc, self.H, self.Hkv)
+            ops.rope_append(qkv_parts, pos, sb["seq0"][:T], bt, self.cos, self.sin, q, kc, vc, self.H, self.Hkv,
+                            kv_scales=kvs(l))
             ops.attn_verify(q, kc, vc, bt, pos[:1], self.H, self.Hkv, self.scale, attn, workspace=sb["attn_ws"],
-                            plan=plan)
+                            plan=plan, kv_scales=kvs(l))
             lin(attn, lw.wo, "f32", out=o_parts, splitk=sk_o)
             if wn:
                 ops.res_add_ss(h, o_parts, xn, T, ssq[2 * l + 1])
             else:
                 ops.add_rmsnorm(h, lw.mlp_norm, self.eps, xn, parts=o_parts, rows=T)
-            lin(xn, lw.w_gate_up, "silu", out=act, **(dict(rownorm=(h, self.eps)) if (wn and not self.on_gpu)
-                                                      else rn(2 * l + 1)))
+            lin(xn, lw.w_gate_up, "silu", out=act, **(dict(rownorm=(h, self.eps)) if rr_cpu else rn(2 * l + 1)))
             lin(act, lw.w_down, "f32", out=d_parts, splitk=sk_d)
         ops.add_rmsnorm(h, w.final_norm, self.eps, xn, parts=d_parts, rows=T)
         logits = sb["logits"][:T]
@@ -831,7 +856,9 @@ class ModelRunner:
         kernels scale the GEMM's output rows; ``ops.linear``'s CPU twin scales its bf16 input rows instead).  With the
         residual-reduce plain step (``rr_decode``): the product of the raw bf16 row, then the RMS row scale -- from the
         Q24 row sum for an f32 epilogue (as ``attn_decode(rownorm=)`` applies it to the slabs), from the f32 residual
-        row itself for the SiLU epilogue (as ``linear_rr`` does; ``rownorm[0]`` is then the residual stream)."""
+        row itself for the SiLU epilogue (as ``linear_rr`` does; ``rownorm[0]`` is then the residual stream).
+        Quantised weights: on the CPU their plain step runs neither e4m3 activations nor the residual-reduce step, so
+        every projection is the plain ``ops.linear`` call of that row."""
         post = rownorm is not None and self.rr_decode and not self.rr_a8
         for i in range(x.shape[0]):
             row = x[i:i + 1]
@@ -860,7 +887,8 @@ class ModelRunner:
     def decode_spec(self, steps: int, max_ctx: Optional[int] = None) -> None:
         """Run ``steps`` verify steps of the request in slot 0 (the analogue of ``decode`` at bucket 1); ``max_ctx``
         bounds pos0 + T during the run (picks the split plan's tier)."""
-        assert self.spec_supported(), "speculative decoding: TP = 1, bf16 weights and KV cache, spec_tokens > 0"
+        assert self.spec_supported(), ("speculative decoding: TP = 1, spec_tokens > 0, bf16 weights and KV cache "
+                                       "(or spec_quantized)")
         plan = tuple(self.ctx_plan(1, max_ctx))
         if not self.use_graphs:
             for _ in range(steps):

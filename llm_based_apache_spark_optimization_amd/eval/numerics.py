@@ -150,6 +150,21 @@ def numerics_class(runner, decode_batch: int) -> str:
     return "w8a8" if a8 or runner.kv_fp8 else "w8a16"
 
 
+def spec_numerics_class(runner) -> str:
+    """The threshold row of speculative decoding's verify rows: every projection weight-only
+    (``ModelRunner.spec_oracle_plan``), so what ``numerics_class`` returns for a runner with no e4m3-activation
+    projection -- MXFP4 and bf16 weights "bf16", fp8 weights "w8a8" with the fp8 cache, else "w8a16"."""
+    if runner.w.layers[0].wqkv.kind != "fp8":
+        return "bf16"
+    return "w8a8" if runner.kv_fp8 else "w8a16"
+
+
+def spec_quantised(runner) -> bool:
+    """Whether the runner's plain batch-1 step and its verify step may be different numerics classes (fp8 / MXFP4
+    weights, or the fp8 cache): a recording's plain-step tokens are then not compared under the verify plan."""
+    return runner.kv_fp8 or runner.w.layers[0].wqkv.kind in ("fp8", "mxfp4")
+
+
 def teacher_forced_check(eng, prompts: Sequence[Sequence[int]], n_steps: int = 64, check_rows: Sequence[int] = (0,),
                          weights=None, prefill_rows: Optional[int] = None) -> dict:
     """Decode ``prompts`` as one batch for ``n_steps`` steps, compare rows ``check_rows`` against the oracle."""
@@ -158,11 +173,15 @@ def teacher_forced_check(eng, prompts: Sequence[Sequence[int]], n_steps: int = 6
 
 
 def check_recorded(eng, prompts, toks, elog, n_steps: int, check_rows: Sequence[int] = (0,), weights=None,
-                   prefill_rows: Optional[int] = None) -> dict:
+                   prefill_rows: Optional[int] = None, spec_steps=None) -> dict:
     """Compare recorded decode logits (``record_decode_logits``) of rows ``check_rows`` with the oracle.
 
     ``weights``: the unsharded weights for the oracle (TP engines hold one shard; default the engine's own).
-    ``prefill_rows``: rows of the packed prefill (fp8: > 64 -> W8A8 prefill, emulated by the oracle)."""
+    ``prefill_rows``: rows of the packed prefill (fp8: > 64 -> W8A8 prefill, emulated by the oracle).
+    ``spec_steps``: the step records of ``record_spec_logits`` (one prompt): the oracle plan and the threshold class
+    are then the verify rows' (``ModelRunner.spec_oracle_plan``, ``spec_numerics_class``), and on a quantised runner
+    (``spec_quantised``) the tokens a plain step committed are left out; ``plain_tokens_skipped`` counts them.  bf16
+    weights with the bf16 cache: the same plan, class and tokens as without it."""
     from .. import ops
     from ..models.llama import reference_forward
 
@@ -171,7 +190,16 @@ def check_recorded(eng, prompts, toks, elog, n_steps: int, check_rows: Sequence[
     w = weights if weights is not None else r.w
     fp8 = w.layers[0].wqkv.kind == "fp8"
     rows = prefill_rows if prefill_rows is not None else sum(len(p) for p in prompts)
-    plan = r.oracle_plan(B)
+    plan = r.oracle_plan(B) if spec_steps is None else r.spec_oracle_plan()
+    keep, skipped = None, 0
+    if spec_steps is not None and spec_quantised(r):
+        assert len(prompts) == 1, "verify steps serve one request"
+        keep = torch.zeros(n_steps, dtype=torch.bool)
+        for s_ in spec_steps:  # logits row j - 1 chose token j
+            lo, hi = max(s_["first"], 1), min(s_["first"] + s_["committed"], n_steps + 1)
+            if hi > lo:
+                keep[lo - 1:hi - 1] = bool(s_["spec"])
+                skipped += 0 if s_["spec"] else hi - lo
     ehid = None
     if isinstance(elog, tuple):
         elog, ehid = elog
@@ -182,22 +210,25 @@ def check_recorded(eng, prompts, toks, elog, n_steps: int, check_rows: Sequence[
         lg, xo = reference_forward(w, p + list(toks[i][:n_steps]), act_quant_rows=aq, decode_a8=plan,
                                    kv_fp8=r.kv_fp8, return_hidden=True)
         c = compare(elog[i], lg[len(p):len(p) + n_steps])
-        kls.append(c["kl"])
-        t1s.append(c["top1"])
-        t5s.append(c["top5"])
+        sel = (lambda v: v) if keep is None else (lambda v: v[keep.to(v.device)])  # noqa: E731
+        kls.append(sel(c["kl"]))
+        t1s.append(sel(c["top1"]))
+        t5s.append(sel(c["top5"]))
         if ehid is not None:
             ch = compare_hidden(ehid[i], xo[len(p):len(p) + n_steps])
-            pks.append(ch["probe_kl"])
-            rels.append(ch["rel"])
+            pks.append(sel(ch["probe_kl"]))
+            rels.append(sel(ch["rel"]))
         del lg, xo
     kl, t1, t5 = torch.cat(kls), torch.cat(t1s), torch.cat(t5s)
-    cls = numerics_class(r, B)
+    cls = numerics_class(r, B) if spec_steps is None else spec_numerics_class(r)
     kl_layer, t5_min, t1_min = THRESHOLDS[cls]
     nl = len(r.w.layers)
     kl_max = round(kl_layer * nl, 6)
     res = {"tokens_checked": int(kl.numel()), "decode_batch": len(prompts), "class": cls,
            "mean_kl": round(float(kl.mean()), 6), "max_kl": round(float(kl.max()), 6),
            "top1_agree": round(float(t1.mean()), 4), "top5_overlap": round(float(t5.mean()), 4)}
+    if spec_steps is not None:
+        res["plain_tokens_skipped"] = skipped
     if ehid is None:
         res["ok"] = bool(res["mean_kl"] < kl_max and res["top5_overlap"] >= t5_min
                          and (t1_min is None or res["top1_agree"] >= t1_min))
@@ -271,10 +302,10 @@ def record_spec_logits(eng, prompt: Sequence[int], n_tokens: int, hidden: Option
 
 
 def teacher_forced_check_spec(eng, prompt: Sequence[int], n_tokens: int = 64, weights=None) -> dict:
-    """``teacher_forced_check`` of the verify steps: every committed token's verify-row logits against the same oracle
-    under the same thresholds (``check_recorded``)."""
+    """``teacher_forced_check`` of the verify steps: every token a verify step committed, its verify-row logits against
+    the oracle under the verify rows' plan and threshold class (``check_recorded(spec_steps=)``)."""
     toks, elog, steps = record_spec_logits(eng, prompt, n_tokens)
-    res = check_recorded(eng, [list(prompt)], [toks], elog, n_tokens, (0,), weights)
+    res = check_recorded(eng, [list(prompt)], [toks], elog, n_tokens, (0,), weights, spec_steps=steps)
     res["verify_steps"] = sum(1 for s_ in steps if s_["spec"])
     return res
 

@@ -200,12 +200,13 @@ class PackedWeight:
     kind: str  # "dense" (CPU reference) | "bf16" (fragment layout) | "fp8" | "mxfp4"
     data: torch.Tensor
     scale: Optional[torch.Tensor] = None
+    requested: Optional[str] = None  # "dense" only: the kind the weight was packed for (the CPU keeps every kind dense)
 
     @staticmethod
     def from_dense(w: torch.Tensor, kind: str = "bf16") -> "PackedWeight":
         N, K = w.shape
         if not w.is_cuda:
-            return PackedWeight(N, K, "dense", w.to(torch.bfloat16).contiguous())
+            return PackedWeight(N, K, "dense", w.to(torch.bfloat16).contiguous(), None, kind)
         if kind == "fp8":
             q, s = quantize_fp8(w)
             return PackedWeight(N, K, "fp8", q, s.contiguous())
@@ -1462,22 +1463,24 @@ def verify_workspace(T: int, H: int, Hkv: int, nsplit: int, device) -> tuple:
     return decode_workspace(T, H, Hkv, nsplit, device)
 
 
-def attn_verify(q, kc, vc, block_table, pos0, H, Hkv, scale, out, workspace=None, plan=None):
+def attn_verify(q, kc, vc, block_table, pos0, H, Hkv, scale, out, workspace=None, plan=None, kv_scales=None):
     """Speculative-decoding verify attention: q [T, H, 128] (rotated) are the T new tokens of ONE sequence whose block
     table row is ``block_table``, at positions pos0 .. pos0 + T - 1 (``pos0``: int32 tensor, read on the device); their
-    K / V are already in the bf16 cache (``rope_append``).  Row t sees keys j <= pos0 + t.  out [T, H * 128] bf16.
+    K / V are already in the cache (``rope_append``): bf16, or -- ``kv_scales`` = (ks, vs) -- the fp8 cache's e4m3
+    bytes with their per-(token, kv-head) scales.  Row t sees keys j <= pos0 + t.  out [T, H * 128] bf16.
     T <= 8 and T * H / Hkv <= 16."""
     T = q.shape[0]
     if not _gpu(q):
-        return ref.attn_verify(q, kc, vc, block_table, pos0, H, Hkv, scale, out)
+        return ref.attn_verify(q, kc, vc, block_table, pos0, H, Hkv, scale, out, kv_scales)
     plan = plan if plan is not None else verify_split_plan(Hkv, block_table.numel() * 64)
     chunk, nsplit = plan[0], plan[1]
     unsplit_max = plan[2] if len(plan) > 2 else 4
     if workspace is None:
         workspace = verify_workspace(T, H, Hkv, nsplit, q.device)
     opart, mlpart, counters = workspace
+    ks, vs = kv_scales if kv_scales is not None else (None, None)
     ext().attn_verify(q, kc, vc, block_table, pos0, H, Hkv, scale, chunk, nsplit, unsplit_max, out, opart, mlpart,
-                      counters)
+                      counters, ks, vs)
     return out
 
 

@@ -217,14 +217,14 @@ def kv_copy_blocks(kv, kv_scale, pairs):
 
 
 # ----------------------------------------------------------------------------------- speculative decoding
-def attn_verify(q, kc, vc, block_table, pos0, H, Hkv, scale, out):
+def attn_verify(q, kc, vc, block_table, pos0, H, Hkv, scale, out, kv_scales=None):
     """Attention of the T = q.shape[0] new tokens of ONE sequence (their K / V already appended): row t is a decode
-    query at position pos0 + t, so it sees keys j <= pos0 + t."""
+    query at position pos0 + t, so it sees keys j <= pos0 + t.  ``kv_scales``: the fp8 cache's (ks, vs)."""
     T = q.shape[0]
     p0 = int(pos0.reshape(-1)[0])
     pos = torch.arange(p0, p0 + T, dtype=torch.int32, device=q.device)
     bt = block_table.reshape(1, -1).expand(T, -1)
-    return attn_decode(q, kc, vc, bt, pos, H, Hkv, scale, out.view(T, H, -1))
+    return attn_decode(q, kc, vc, bt, pos, H, Hkv, scale, out.view(T, H, -1), kv_scales)
 
 
 def spec_draft(prompt_tok, prompt_len, out_tokens, gen_len, input_ids, positions, k, n_max, n_min, forced,

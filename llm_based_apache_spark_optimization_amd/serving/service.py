@@ -31,7 +31,7 @@ def engine_factory(settings: Settings, tp_factory=None):
                            prefill_chunk=settings.prefill_chunk, kv_dtype=settings.kv_dtype,
                            max_new_cap=settings.max_new_cap or None,
                            kv_reserve_tokens=settings.kv_reserve_tokens, spec_tokens=settings.spec_tokens,
-                           prefix_cache=settings.prefix_cache,
+                           spec_quantized=settings.spec_quantized, prefix_cache=settings.prefix_cache,
                            prefix_cow_min_tokens=settings.prefix_cow_min_tokens)
         if settings.spec_min_accept >= 0:
             eng.runner.spec_min_accept = settings.spec_min_accept

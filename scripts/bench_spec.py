@@ -1,16 +1,19 @@
 """Speculative decoding on MI355X: what a verify step costs and what it can gain.
 
   kernel   attn_verify (T rows of one sequence, one pass over the cache) against attn_decode over a bucket of T rows
-           (T sequences' worth of cache reads) and against single-token attn_decode; achieved KV bytes/s.
+           (T sequences' worth of cache reads) and against single-token attn_decode; achieved KV bytes/s.  The same
+           shapes over the fp8 KV cache (e4m3 rows + per-row scales) beside the bf16 cache.
   step     device time of a verify step (k drafted tokens) against the plain batch-1 step on the same engine, with
            planted all-wrong drafts so both arms decode the same tokens; break-even acceptance = ratio - 1.
   e2e      tokens/s of a request at planted acceptance 0, about half, and all: the envelope.  (Random-init weights
            give no meaningful natural acceptance; real acceptance needs a checkpoint, LSA_CHECKPOINT_DIR.)
 
 Every graph is warmed, times are device events, the arms alternate within one process.  Appends JSON lines to
-profiles/spec/spec_decode_mi355x.jsonl.  Needs a GPU.
+profiles/spec/spec_decode_mi355x.jsonl, or -- with quantised weights or the fp8 cache (``spec_quantized`` engines) --
+to profiles/spec/spec_decode_quant_mi355x.jsonl (--out overrides).  Needs a GPU.
 
-  python scripts/bench_spec.py [--layers N] [--skip kernel,step,e2e] [--reps 5]
+  python scripts/bench_spec.py [--layers N] [--skip kernel,step,e2e] [--reps 5] [--dtype bf16|fp8|mxfp4]
+                               [--kv-dtype bf16|fp8] [--models duckdb-nsql,llama3.2] [--out FILE]
 """
 from __future__ import annotations
 
@@ -30,8 +33,10 @@ from llm_based_apache_spark_optimization_amd import ops  # noqa: E402
 from llm_based_apache_spark_optimization_amd.engine import LLMEngine, ModelRunner, SamplingParams  # noqa: E402
 from llm_based_apache_spark_optimization_amd.models import get_spec  # noqa: E402
 from llm_based_apache_spark_optimization_amd.models.llama import init_random  # noqa: E402
+from llm_based_apache_spark_optimization_amd.ops import reference as ref  # noqa: E402
 
 OUT = os.path.join(ROOT, "profiles", "spec", "spec_decode_mi355x.jsonl")
+OUT_QUANT = os.path.join(ROOT, "profiles", "spec", "spec_decode_quant_mi355x.jsonl")
 
 
 def emit(rec: dict) -> None:
@@ -72,6 +77,10 @@ def bench_kernel(dev, reps: int) -> None:
                 g = torch.Generator().manual_seed(ctx + T)
                 kc = (torch.randn(T * mb + 1, Hkv, 64, D, generator=g) * 0.5).to(torch.bfloat16).to(dev)
                 vc = (torch.randn(T * mb + 1, Hkv, 64, D, generator=g) * 0.5).to(torch.bfloat16).to(dev)
+                # the same rows in the fp8 cache: e4m3 bytes in the token-pair order + per-(token, kv-head) scales
+                (k8, ks), (v8, vs) = ref.quant_kv_rows(kc.float()), ref.quant_kv_rows(vc.float())
+                k8, v8 = ref.kv8_physical(k8).contiguous(), ref.kv8_physical(v8).contiguous()
+                ks, vs = ks.contiguous(), vs.contiguous()
                 bts = (torch.arange(T * mb, dtype=torch.int32) + 1).view(T, mb).to(dev)  # T disjoint sequences
                 q = (torch.randn(T, H, D, generator=g) * 0.7).to(torch.bfloat16).to(dev)
                 out = torch.zeros(T, H * D, dtype=torch.bfloat16, device=dev)
@@ -84,6 +93,8 @@ def bench_kernel(dev, reps: int) -> None:
                 arms = {
                     "verify": lambda: ops.attn_verify(q, kc, vc, bts[:1], pos0, H, Hkv, D ** -0.5, out, workspace=ws,
                                                       plan=plan),
+                    "verify_fp8": lambda: ops.attn_verify(q, k8, v8, bts[:1], pos0, H, Hkv, D ** -0.5, out,
+                                                          workspace=ws, plan=plan, kv_scales=(ks, vs)),
                     "decode_T_rows": lambda: ops.attn_decode(q, kc, vc, bts, posT, H, Hkv, D ** -0.5, out.view(T, H, D),
                                                              workspace=wsT, plan=planT),
                     "decode_1_row": lambda: ops.attn_decode(q[:1], kc, vc, bts[:1], posT[:1], H, Hkv, D ** -0.5,
@@ -98,7 +109,9 @@ def bench_kernel(dev, reps: int) -> None:
                 emit(dict(bench="kernel", model=name, H=H, Hkv=Hkv, ctx=ctx, T=T, us=med,
                           verify_over_decode1=round(med["verify"] / med["decode_1_row"], 3),
                           verify_over_decodeT=round(med["verify"] / med["decode_T_rows"], 3),
-                          verify_kv_GBps=round(kv_bytes / med["verify"] / 1e3, 1)))
+                          verify_kv_GBps=round(kv_bytes / med["verify"] / 1e3, 1),
+                          verify_fp8_over_bf16=round(med["verify_fp8"] / med["verify"], 3),
+                          verify_fp8_kv_GBps=round(kv_bytes * (D + 4) / (2 * D) / med["verify_fp8"] / 1e3, 1)))
 
 
 def forced(toks, kind: str, k: int, V: int) -> torch.Tensor:
@@ -116,13 +129,17 @@ def forced(toks, kind: str, k: int, V: int) -> torch.Tensor:
     return torch.tensor(rows, dtype=torch.int32)
 
 
-def bench_engine(dev, layers, reps: int, skip) -> None:
+def bench_engine(dev, layers, reps: int, skip, dtype: str = "bf16", kv_dtype: str = "bf16", models=()) -> None:
     for base, plen, new in (("duckdb-nsql", 128, 128), ("llama3.2", 2048, 128)):
+        if models and base not in models:
+            continue
         spec = get_spec(base)
         if layers:
             spec = dataclasses.replace(spec, n_layers=layers, name=f"{base}-{layers}l")
-        w = init_random(spec, dev, seed=5)
-        r = ModelRunner(w, max_slots=2, max_model_len=plen + new + 64, num_kv_blocks=2 * ((plen + new) // 64 + 3))
+        w = init_random(spec, dev, seed=5, kind=dtype)
+        # quantised weights / the fp8 cache: the verify rows run the weight-only GEMMs (opt-in, spec_quantized)
+        r = ModelRunner(w, max_slots=2, max_model_len=plen + new + 64, num_kv_blocks=2 * ((plen + new) // 64 + 3),
+                        kv_dtype=kv_dtype, spec_quantized=(dtype, kv_dtype) != ("bf16", "bf16"))
         eng = LLMEngine(r, name=spec.name)
         g = torch.Generator().manual_seed(7)
         ids = [1] + torch.randint(3, 30000, (plen - 1,), generator=g).tolist()
@@ -154,7 +171,8 @@ def bench_engine(dev, layers, reps: int, skip) -> None:
             p = statistics.median(plain)
             for k in ks:
                 v = statistics.median(ver[k])
-                emit(dict(bench="step", model=spec.name, layers=spec.n_layers, prompt=plen, new=new, k=k,
+                emit(dict(bench="step", model=spec.name, dtype=dtype, kv_dtype=kv_dtype, a8_plan_b1=list(r.a8_plan(1)),
+                          rr_a8=bool(r.rr_decode and r.rr_a8), layers=spec.n_layers, prompt=plen, new=new, k=k,
                           plain_step_ms=round(p * 1e3, 4), verify_step_ms=round(v * 1e3, 4),
                           break_even_accept=round(v / p - 1, 3), tokens_equal=out == toks))
         if "e2e" not in skip:
@@ -168,7 +186,8 @@ def bench_engine(dev, layers, reps: int, skip) -> None:
                     out, _, ns, tps = run(3, kind, toks)
                     res.setdefault(kind, []).append(tps)
                     res[kind + "_steps"] = ns
-            emit(dict(bench="e2e", model=spec.name, layers=spec.n_layers, prompt=plen, new=new, k=3,
+            emit(dict(bench="e2e", model=spec.name, dtype=dtype, kv_dtype=kv_dtype, layers=spec.n_layers, prompt=plen,
+                      new=new, k=3,
                       decode_tok_s={k: round(statistics.median(v), 1) for k, v in res.items() if not k.endswith("_steps")},
                       verify_steps={k[:-6]: v for k, v in res.items() if k.endswith("_steps")}))
         del eng, r, w
@@ -180,7 +199,13 @@ def main() -> None:
     ap.add_argument("--layers", type=int, default=0, help="truncate the models to this many layers (0 = full depth)")
     ap.add_argument("--skip", default="", help="comma list of kernel,step,e2e")
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--dtype", default="bf16", choices=("bf16", "fp8", "mxfp4"), help="weight format of the engines")
+    ap.add_argument("--kv-dtype", default="bf16", choices=("bf16", "fp8"), help="KV cache dtype of the engines")
+    ap.add_argument("--models", default="", help="comma list of duckdb-nsql,llama3.2 (default both)")
+    ap.add_argument("--out", default="", help="JSON-lines file to append to")
     a = ap.parse_args()
+    global OUT
+    OUT = a.out or (OUT if (a.dtype, a.kv_dtype) == ("bf16", "bf16") else OUT_QUANT)
     if not torch.cuda.is_available():
         raise SystemExit("bench_spec.py needs a GPU")
     ops.ext()
@@ -189,7 +214,8 @@ def main() -> None:
     if "kernel" not in skip:
         bench_kernel(dev, a.reps)
     if not {"step", "e2e"} <= skip:
-        bench_engine(dev, a.layers, a.reps, skip)
+        bench_engine(dev, a.layers, a.reps, skip, a.dtype, a.kv_dtype,
+                     tuple(m for m in a.models.split(",") if m))
 
 
 if __name__ == "__main__":
