@@ -63,6 +63,10 @@ int lsa_kv_copy_blocks(void* kv, void* scale, const int* pairs, int npairs, int 
 int lsa_spec_draft(const int* prompt_tok, int prompt_ld, const int* prompt_len, const int* out_tokens, int max_new,
                    const int* gen_len, const int* input_ids, const int* positions, int rows, int k, int n_max, int n_min,
                    const int* forced, int nf, int* spec_ids, int* spec_pos, int* spec_draft, hipStream_t s);
+int lsa_dfa_mask(float* logits, int B, int V, const int* tok_off, const uint8_t* tok_blob, const uint8_t* cls,
+                 const uint16_t* trans, const uint8_t* accept, const int* g_dim, const int* g_on, int* g_state,
+                 const int* g_base, const int* rows, const int* gen_len, const int* input_ids, const int* finished,
+                 const int* eos, int neos, hipStream_t s);
 int lsa_spec_commit(const float* logits, int T, int V, unsigned long long* part, const int* draft, long long* stats,
                     int* out_tokens, int max_new, int* gen_len, int* input_ids, int* positions, int* finished,
                     const int* eos, int neos, const int* limit, const int* eos_on, hipStream_t s);
@@ -986,6 +990,52 @@ void spec_commit(const at::Tensor& logits, at::Tensor& part, const at::Tensor& d
         "spec_commit");
 }
 
+// regex-constrained decoding: -inf into every logit whose token would kill the row's DFA (kernels/guided.hip).
+// Table rows are indexed by rows[b] when given (prefill tail: the sequence's slot), else by b.
+void dfa_mask(at::Tensor& logits, const at::Tensor& tok_off, const at::Tensor& tok_blob, const at::Tensor& cls,
+              const at::Tensor& trans, const at::Tensor& accept, const at::Tensor& g_dim, const at::Tensor& g_on,
+              at::Tensor& g_state, const at::Tensor& g_base, const c10::optional<at::Tensor>& rows,
+              const at::Tensor& gen_len, const at::Tensor& input_ids, const at::Tensor& finished,
+              const at::Tensor& eos) {
+  need(logits, at::kFloat, "logits");
+  TORCH_CHECK(logits.dim() == 2 && logits.is_contiguous() && logits.size(0) >= 1 && logits.size(0) <= 65535 &&
+                  logits.size(1) >= 1 && logits.numel() < 0x7fffffffLL, "logits: contiguous [1 <= B <= 65535, V]");
+  const int64_t B = logits.size(0), V = logits.size(1);
+  need(tok_off, at::kInt, "tok_off");
+  need(tok_blob, at::kByte, "tok_blob");
+  need(cls, at::kByte, "cls");
+  need(trans, at::kShort, "trans");
+  need(accept, at::kByte, "accept");
+  TORCH_CHECK(tok_off.is_contiguous() && tok_off.numel() == V + 1 && tok_blob.is_contiguous() && tok_blob.numel() >= 1,
+              "dfa_mask: tok_off [V + 1], tok_blob non-empty");
+  TORCH_CHECK(cls.dim() == 2 && cls.size(1) == 256 && cls.is_contiguous(), "cls: contiguous [Bmax, 256]");
+  const int64_t Bmax = cls.size(0);
+  TORCH_CHECK(trans.dim() == 2 && trans.size(0) == Bmax && trans.size(1) == 32768 && trans.is_contiguous() &&
+                  accept.dim() == 2 && accept.size(0) == Bmax && accept.size(1) == 32768 && accept.is_contiguous(),
+              "trans / accept: contiguous [Bmax, 32768]");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(trans.data_ptr()) % 16 == 0, "trans must be 16-byte aligned");
+  const at::Tensor& g_state_c = g_state;
+  for (const at::Tensor* t : {&g_dim, &g_on, &g_state_c, &g_base, &gen_len, &input_ids, &finished, &eos}) {
+    need(*t, at::kInt, "dfa_mask state operand");
+    TORCH_CHECK(t->is_contiguous(), "dfa_mask state operands must be contiguous");
+  }
+  TORCH_CHECK(g_dim.numel() == 2 * Bmax && g_state.numel() == 2 * Bmax && g_on.numel() == Bmax && g_base.numel() == Bmax,
+              "dfa_mask: g_dim / g_state [Bmax, 2], g_on / g_base [Bmax]");
+  TORCH_CHECK(gen_len.numel() >= B && input_ids.numel() >= B && finished.numel() >= B, "dfa_mask: state rows");
+  if (rows.has_value()) {
+    need(*rows, at::kInt, "rows");
+    TORCH_CHECK(rows->is_contiguous() && rows->numel() >= B, "rows: contiguous [B]");
+  } else {
+    TORCH_CHECK(B <= Bmax, "dfa_mask: more logits rows than table rows");
+  }
+  check(lsa_dfa_mask(logits.data_ptr<float>(), B, V, tok_off.data_ptr<int>(), tok_blob.data_ptr<uint8_t>(),
+                     cls.data_ptr<uint8_t>(), reinterpret_cast<const uint16_t*>(trans.data_ptr<int16_t>()),
+                     accept.data_ptr<uint8_t>(), g_dim.data_ptr<int>(), g_on.data_ptr<int>(), g_state.data_ptr<int>(),
+                     g_base.data_ptr<int>(), ptr<const int>(rows), gen_len.data_ptr<int>(), input_ids.data_ptr<int>(),
+                     finished.data_ptr<int>(), eos.data_ptr<int>(), eos.numel(), cur_stream()),
+        "dfa_mask");
+}
+
 void sample_commit(at::Tensor& logits, at::Tensor& part, at::Tensor& cand, const c10::optional<at::Tensor>& hist,
                    const c10::optional<at::Tensor>& penalty, const c10::optional<at::Tensor>& last_n,
                    const at::Tensor& temperature, const at::Tensor& top_k,
@@ -1219,6 +1269,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("gen_len"), py::arg("input_ids"), py::arg("positions"), py::arg("k"), py::arg("n_max"), py::arg("n_min"),
         py::arg("forced"), py::arg("spec_ids"), py::arg("spec_pos"), py::arg("spec_draft"));
   m.def("spec_commit", &spec_commit);
+  m.def("dfa_mask", &dfa_mask, py::arg("logits"), py::arg("tok_off"), py::arg("tok_blob"), py::arg("cls"),
+        py::arg("trans"), py::arg("accept"), py::arg("g_dim"), py::arg("g_on"), py::arg("g_state"), py::arg("g_base"),
+        py::arg("rows"), py::arg("gen_len"), py::arg("input_ids"), py::arg("finished"), py::arg("eos"));
   m.def("fp8_dequant", &fp8_dequant);
   m.def("quant_rows_fp8", &quant_rows_fp8);
   m.def("fp8_gemm_t256", &fp8_gemm_t256, py::arg("x8"), py::arg("sx"), py::arg("wq"), py::arg("sw"), py::arg("N"),

@@ -63,6 +63,11 @@ class Settings:
     # profiles/prefix_cache/cow_sweep_mi355x.jsonl)
     prefix_cache: bool = dataclasses.field(default_factory=lambda: _env("PREFIX_CACHE", False, bool))
     prefix_cow_min_tokens: int = dataclasses.field(default_factory=lambda: _env("PREFIX_COW_MIN_TOKENS", 8, int))
+    # regex-constrained decoding (off by default): requests may carry the option "regex"; the answer is then a full
+    # match of the pattern (engine/guided.py).  sql_guided (needs guided): /nl2sql constrains the NL->SQL model to
+    # prompts.SQL_STATEMENT_REGEX -- one SELECT / WITH statement that ends at its first ';'
+    guided: bool = dataclasses.field(default_factory=lambda: _env("GUIDED", False, bool))
+    sql_guided: bool = dataclasses.field(default_factory=lambda: _env("SQL_GUIDED", False, bool))
     tp: int = dataclasses.field(default_factory=lambda: _env("TP", 1, int))
     dp: int = dataclasses.field(default_factory=lambda: _env("DP", 1, int))
     max_batch: int = dataclasses.field(default_factory=lambda: _env("MAX_BATCH", 32, int))

@@ -26,11 +26,12 @@ from typing import Callable, Iterator, Optional, Sequence
 import torch
 
 from ..models.templates import STOP_STRINGS, apply_stops, render
-from ..models.tokenizer import tokenizer_for
+from ..models.tokenizer import token_bytes, tokenizer_for
 from ..ops.reference import pack_seed
 from ..runtime import native
 from ..utils import tracing
 from ..utils.metrics import REGISTRY, TOKEN_BUCKETS
+from .guided import GuidedRequestError, compile_regex
 from .runner import BLOCK, ModelRunner
 
 
@@ -60,6 +61,11 @@ class SamplingParams:
     # prefix cache, where the engine runs it (LLMEngine(prefix_cache=True)): llama.cpp's "cache_prompt": false opts a
     # request out -- it neither reuses cached KV blocks nor publishes its own
     cache_prompt: bool = True
+    # regex-constrained decoding, where the engine runs it (LLMEngine(guided=True)): the Ollama option extension
+    # "regex".  The generated text -- its UTF-8 bytes -- is a full match of the pattern (engine/guided.py: the supported
+    # syntax) when the request ends by EOS; EOS is allowed only then.  A request that ends at its length limit is
+    # returned as it stands, possibly short of a match.  Not with ignore_eos; a constrained request never speculates.
+    regex: Optional[str] = None
 
     @property
     def needs_sampler(self) -> bool:
@@ -83,7 +89,8 @@ class SamplingParams:
                               repeat_last_n=int(opts.get("repeat_last_n", 64)),
                               num_ctx=int(opts["num_ctx"]) if opts.get("num_ctx") else None,
                               num_keep=int(opts.get("num_keep", 4)), speculate=bool(opts.get("speculate", True)),
-                              cache_prompt=bool(opts.get("cache_prompt", True)))
+                              cache_prompt=bool(opts.get("cache_prompt", True)),
+                              regex=(str(opts["regex"]) if opts.get("regex") else None))
 
 
 @dataclasses.dataclass
@@ -114,6 +121,8 @@ class Request:
     spec_off: bool = False
     # prefix cache: prompt tokens whose KV was found in the cache (summed over re-admissions of a preempted request)
     cached_tokens: int = 0
+    # regex-constrained decoding: the compiled pattern (engine/guided.py Dfa) of params.regex
+    dfa: Optional[object] = None
 
     @property
     def ctx_ids(self) -> list:
@@ -138,7 +147,8 @@ class GenerationResult:
 class LLMEngine:
     def __init__(self, runner: ModelRunner, tokenizer=None, max_prefill_tokens: int = 16384, sync_every: int = 8,
                  name: Optional[str] = None, prefill_chunk: Optional[int] = None, kv_reserve_tokens: int = BLOCK,
-                 spec_tokens: int = 0, prefix_cache: bool = False, prefix_cow_min_tokens: Optional[int] = None):
+                 spec_tokens: int = 0, prefix_cache: bool = False, prefix_cow_min_tokens: Optional[int] = None,
+                 guided: bool = False):
         self.runner = runner
         if spec_tokens:  # speculative decoding for batch-1 greedy requests (the runner clamps it to what it supports)
             runner.spec_tokens = int(spec_tokens)
@@ -186,6 +196,16 @@ class LLMEngine:
                       # prompt tokens not prefilled because of it (prompt_tokens counts the tokens that were)
                       "prefix_queries": 0, "prefix_hits": 0, "prefix_cached_tokens": 0}
         self._spec_seen = (0, 0, 0)  # runner.spec_counts() as of the last decode run
+        # regex-constrained decoding (SamplingParams.regex): the tokenizer's byte table goes to the device once and the
+        # runner allocates its per-slot DFA tables; off (the default) nothing is allocated, launched or counted
+        self.guided = bool(guided) or bool(getattr(runner, "guided", False))
+        self._tok_bytes = None
+        if self.guided:
+            off, blob = token_bytes(self.tok, self.spec.vocab_size)
+            self._tok_bytes = (off.tolist(), blob.tobytes())
+            if not getattr(runner, "guided", False):
+                runner.enable_guided(off, blob)
+            self.stats.update(guided_requests=0, guided_steps=0)
         # per-decode-run device timing (hipEvents around the graph replays, read after the host sync the
         # run ends with anyway): lsa_decode_step_device_seconds{model} = GPU time per token step
         self.device_timing = runner.on_gpu
@@ -220,8 +240,19 @@ class LLMEngine:
         if room < 1:
             raise ValueError("prompt longer than the model context")
         p = dataclasses.replace(params, max_tokens=max(1, min(params.max_tokens, room, self.runner.max_new_cap)))
+        dfa = None
+        if p.regex is not None:  # compiled here, so that a bad pattern fails the request, not the engine loop
+            if not self.guided:
+                raise GuidedRequestError("this engine was built without regex-constrained decoding (guided=True / "
+                                         "LSA_GUIDED=1 enables it)")
+            if p.ignore_eos:
+                raise GuidedRequestError("regex cannot be combined with ignore_eos: a constrained request ends by EOS")
+            dfa = compile_regex(p.regex)
         req = Request(next(self._ids), list(map(int, prompt_ids)), p, time.perf_counter(),
-                      stream=queue.Queue() if stream else None)
+                      stream=queue.Queue() if stream else None, dfa=dfa)
+        if dfa is not None:
+            self.stats["guided_requests"] += 1
+            REGISTRY.inc("lsa_guided_requests_total", 1, "requests with a regex constraint", model=self.name)
         with self._lock:
             if self.prefix_cache:
                 self.sched.add(req.rid, len(req.prompt_ids), p.max_tokens, req.prompt_ids, bool(p.cache_prompt))
@@ -276,6 +307,8 @@ class LLMEngine:
                                     eos_on=not sp.ignore_eos, repeat_penalty=sp.repeat_penalty,
                                     repeat_last_n=sp.repeat_last_n, prompt_ids=req.ctx_ids,
                                     defer_table=self.prefill_chunk is not None))
+                if req.dfa is not None:  # a re-admitted request resumes in the state its generated tokens reached
+                    entries[-1].update(dfa=req.dfa, dfa_state=req.dfa.walk(req.dfa.start, self._bytes_of(req.resumed)))
                 self._prefilling.append(req)
             r.set_slots(entries)  # one batched host -> device transfer for every admitted request
             if self.prefix_cache and admitted:
@@ -300,6 +333,7 @@ class LLMEngine:
             if not running:
                 return []
             sample = any(self._reqs[rid].params.needs_sampler for rid in running)
+            guided = self.guided and any(self._reqs[rid].dfa is not None for rid in running)
             # steps until the earliest request can hit its length limit; with EOS possible, at most
             # sync_every steps between host checks
             reqs = [self._reqs[rid] for rid in running]
@@ -334,13 +368,19 @@ class LLMEngine:
             if spec_T:
                 r.decode_spec(n_steps, max_ctx=max_ctx)
             else:
-                r.decode(B, n_steps, sample, max_ctx=max_ctx)
+                if guided:  # the graph variant with the mask launch, only while a running row is constrained
+                    r.decode(B, n_steps, sample, max_ctx=max_ctx, guided=True)
+                else:
+                    r.decode(B, n_steps, sample, max_ctx=max_ctx)
             if ev is not None:
                 ev[1].record()
         fin, gl, _ = r.read_rows([q.slot for q in reqs])
         with self._lock:
             self.stats["decode_s"] += time.perf_counter() - t0
             self.stats["decode_steps"] += n_steps
+            if guided and n_steps and not spec_T:
+                self.stats["guided_steps"] += n_steps
+                REGISTRY.inc("lsa_guided_steps_total", n_steps, "decode steps run with the regex mask", model=self.name)
             if spec_T and n_steps:
                 self._spec_account(reqs[0])
             if ev is not None:
@@ -425,7 +465,7 @@ class LLMEngine:
         q = reqs[0]
         sp = q.params
         if (q.slot != 0 or self.sched.highest_slot != 0 or self.sched.num_running != 1 or sp.needs_sampler
-                or not sp.speculate or q.spec_off):
+                or not sp.speculate or q.spec_off or q.dfa is not None):
             return 0
         T = r.spec_k() + 1
         steps = min(n_steps, -(-remaining // T))
@@ -438,6 +478,11 @@ class LLMEngine:
             self.stats["kv_grown_blocks"] += got
             r.extend_tables([(q.slot, self.sched.block_table(q.rid))])
         return T
+
+    def _bytes_of(self, ids: Sequence[int]) -> bytes:
+        """The bytes the token ids decode to (the table regex-constrained decoding walks on the device)."""
+        off, blob = self._tok_bytes
+        return b"".join(blob[off[t]:off[t + 1]] for t in ids if 0 <= t < len(off) - 1)
 
     def _spec_account(self, q: Request) -> None:
         """Fold the runner's verify-step counters into the engine's and the request's; apply the acceptance guard: a

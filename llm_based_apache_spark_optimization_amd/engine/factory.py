@@ -19,7 +19,8 @@ def build_engine(model: str, device: Optional[str] = None, checkpoint: Optional[
                  warm_graphs: bool = False, prefill_chunk: Optional[int] = None,
                  kv_dtype: Optional[str] = None, max_new_cap: Optional[int] = None,
                  kv_reserve_tokens: int = 64, spec_tokens: int = 0, prefix_cache: bool = False,
-                 prefix_cow_min_tokens: Optional[int] = None, spec_quantized: bool = False) -> LLMEngine:
+                 prefix_cow_min_tokens: Optional[int] = None, spec_quantized: bool = False,
+                 guided: bool = False) -> LLMEngine:
     """kv_dtype: paged KV cache dtype, "bf16" | "fp8" (None: LSA_KV_FP8, default bf16).
     max_new_cap: generated-token cap per request (None: the context window).
     kv_reserve_tokens: generated tokens whose KV is reserved at admission (the rest grows lazily; < 0 reserves
@@ -29,7 +30,9 @@ def build_engine(model: str, device: Optional[str] = None, checkpoint: Optional[
     their verify rows run the weight-only GEMMs, a different numerics class from a W8A8 / W4A8 plain batch-1 step.
     prefix_cache: keep the KV blocks of full prompt blocks after their request and share them with later requests
     whose prompt starts with the same tokens (off by default); prefix_cow_min_tokens: the shortest common prefix
-    with a cached block that is worth forking it (None: the scheduler's default)."""
+    with a cached block that is worth forking it (None: the scheduler's default).
+    guided: regex-constrained decoding for requests that carry ``SamplingParams.regex`` (off by default: such a
+    request is then rejected); allocates the per-slot DFA tables and captures a guided variant of each decode graph."""
     if device is None:
         device = f"cuda:{torch.cuda.current_device()}" if torch.cuda.is_available() else "cpu"
     t0 = time.perf_counter()
@@ -46,7 +49,7 @@ def build_engine(model: str, device: Optional[str] = None, checkpoint: Optional[
                          max_new_cap=max_new_cap, spec_tokens=spec_tokens, spec_quantized=spec_quantized)
     eng = LLMEngine(runner, tok, sync_every=sync_every, max_prefill_tokens=max_prefill_tokens, name=model,
                     prefill_chunk=prefill_chunk or None, kv_reserve_tokens=kv_reserve_tokens, spec_tokens=spec_tokens,
-                    prefix_cache=prefix_cache, prefix_cow_min_tokens=prefix_cow_min_tokens)
+                    prefix_cache=prefix_cache, prefix_cow_min_tokens=prefix_cow_min_tokens, guided=guided)
     if torch.device(device).type == "cuda":
         if warm_graphs:
             runner.capture_all()

@@ -249,6 +249,9 @@ class ModelRunner:
         # while the decode graph replays, and prompt_len - 1 lies in a published (shared) block when the prompt fills
         # its last block exactly; prompt_len is always in the request's own blocks (admission reserves it).
         self.park_past_prompt = False
+        # regex-constrained decoding (``enable_guided``): off = no buffer, launch or graph differs
+        self.guided = False
+        self._g_host_on: set = set()  # slots whose current request carries a constraint (host mirror of g_on)
         if self.tp is not None and self.tp.size > 1 and self.on_gpu:
             self.tp.warmup()  # communicators (RCCL + the one-shot IPC all-reduce) before any launch
             if not self.tp.capturable():  # gloo without the IPC kernel (test boxes): eager decode steps
@@ -368,12 +371,12 @@ class ModelRunner:
         tier = min(tier, self.max_model_len)
         return tuple(ops.decode_split_plan(B, self.Hkv, tier))
 
-    def _decode_step(self, B: int, sample: bool, plan: Optional[tuple] = None) -> None:
+    def _decode_step(self, B: int, sample: bool, plan: Optional[tuple] = None, guided: bool = False) -> None:
         a8, a8m, a8o, a8d = self.a8_plan(B)  # qkv / gate_up / o / down W8A8 (W4A8)
         if B == 1 and self.rr_decode and (self.rr_a8 or not (a8 or a8m or a8o)):
-            return self._decode_step_rr(sample, plan)
+            return self._decode_step_rr(sample, plan, guided)
         if self.fused_norm and B <= self.fused_norm_max_batch and not (a8 or a8m or a8o):
-            return self._decode_step_fused(B, sample, plan)
+            return self._decode_step_fused(B, sample, plan, guided)
         w, d = self.w, self.d
         ids, pos, bt = self.input_ids[:B], self.positions[:B], self.block_tables[:B]
         h = self.h[:B]
@@ -457,9 +460,9 @@ class ModelRunner:
             else:
                 lin(act, lw.w_down, "f32", out=d_parts, splitk=sk_d)
         ops.add_rmsnorm(h, w.final_norm, self.eps, xn, parts=self._reduce_parts(d_parts), rows=B, xf=xf)
-        self._decode_tail(B, sample, xn, xf)
+        self._decode_tail(B, sample, xn, xf, guided)
 
-    def _decode_step_fused(self, B: int, sample: bool, plan: Optional[tuple] = None) -> None:
+    def _decode_step_fused(self, B: int, sample: bool, plan: Optional[tuple] = None, guided: bool = False) -> None:
         """Norm-free decode step (TP = 1): 5 launches per layer instead of 7.
 
           embed (+ row sum of squares)  ->  per layer:
@@ -509,9 +512,9 @@ class ModelRunner:
             lin(xn, lw.w_gate_up, "silu", out=act, rownorm=(ssq[2 * l + 1], self.eps))
             lin(act, lw.w_down, "res", out=d_parts, splitk=sk_d, res=(h, xn, ssq[2 * l + 2], tk), **rc)
         ops.add_rmsnorm(h, w.final_norm, self.eps, xn, rows=B, xf=xf, write_h=False)
-        self._decode_tail(B, sample, xn, xf)
+        self._decode_tail(B, sample, xn, xf, guided)
 
-    def _decode_step_rr(self, sample: bool, plan: Optional[tuple] = None) -> None:
+    def _decode_step_rr(self, sample: bool, plan: Optional[tuple] = None, guided: bool = False) -> None:
         """Batch-1 decode step with the residual adds folded into the GEMM prologues (TP = 1, bf16, gammas folded):
         5 launches per layer.
 
@@ -585,10 +588,12 @@ class ModelRunner:
             cur = 1 - cur
             ops.linear(act, lw.w_down, "f32", out=d_parts, splitk=sk_d)
         ops.add_rmsnorm(hs[cur], w.final_norm, self.eps, xn, parts=d_parts, rows=1, write_h=False)
-        self._decode_tail(B, sample, xn, False)
+        self._decode_tail(B, sample, xn, False, guided)
 
-    def _decode_tail(self, B: int, sample: bool, xn, xf: bool) -> None:
+    def _decode_tail(self, B: int, sample: bool, xn, xf: bool, guided: bool = False) -> None:
         logits = self._lm_head(xn, B, xf)
+        if guided:  # -inf into every token that would kill a constrained row's DFA; the commits below run unchanged
+            self._dfa_mask(logits, self.gen_len[:B], self.input_ids[:B], self.finished[:B])
         st = (self.out_tokens[:B], self.gen_len[:B], self.input_ids[:B], self.positions[:B], self.finished[:B])
         if sample:
             ops.sample_commit(logits, self.hist[:B], self.penalty[:B], self.temperature[:B], self.top_k[:B],
@@ -618,11 +623,18 @@ class ModelRunner:
             b *= 2
         return min(b, self.max_slots) if n <= self.max_slots else self.max_slots
 
-    def capture(self, B: int, sample: bool, plan: Optional[tuple] = None) -> None:
+    @staticmethod
+    def graph_key(B: int, sample: bool, plan: tuple, guided: bool = False) -> tuple:
+        """Key of a decode graph: (B, sample, plan), and (B, sample, plan, True) for its guided variant (the same step
+        with the ``dfa_mask`` launch between the lm_head and the commit)."""
+        return (B, sample, plan, True) if guided else (B, sample, plan)
+
+    def capture(self, B: int, sample: bool, plan: Optional[tuple] = None, guided: bool = False) -> None:
         """Capture the decode-step graph of (bucket, sampling mode, split plan).  (Several steps per graph were
         measured no faster -- no idle time at graph boundaries, profiles/decode_b32_normfree_spg_ab_mi355x.txt.)"""
         plan = tuple(plan or self.ctx_plan(B))
-        key = (B, sample, plan)
+        assert self.guided or not guided, "guided decode graphs need enable_guided()"
+        key = self.graph_key(B, sample, plan, guided)
         if key in self.graphs:
             return
         if self.tp is not None and self.tp.size > 1:
@@ -633,7 +645,7 @@ class ModelRunner:
         with torch.cuda.stream(s):
             # state must not change during capture: kernels are recorded, not executed
             with torch.cuda.graph(g, stream=s):
-                self._decode_step(B, sample, plan)
+                self._decode_step(B, sample, plan, guided)
         torch.cuda.current_stream(self.device).wait_stream(s)
         self.graphs[key] = g
 
@@ -694,18 +706,22 @@ class ModelRunner:
             for sm in sample_modes:
                 for p in self.plans(b):
                     self.capture(b, sm, p)
+                    if self.guided:
+                        self.capture(b, sm, p, guided=True)
         torch.cuda.synchronize(self.device)
 
-    def decode(self, B: int, steps: int, sample: bool = False, max_ctx: Optional[int] = None) -> None:
+    def decode(self, B: int, steps: int, sample: bool = False, max_ctx: Optional[int] = None,
+               guided: bool = False) -> None:
         """Run ``steps`` decode steps over slot rows [0, B) (B a bucket size); ``max_ctx`` bounds every
-        row's context length during the run (picks the graph planned for that tier)."""
+        row's context length during the run (picks the graph planned for that tier).  ``guided``: the variant with
+        the regex mask, for runs in which a row is constrained."""
         plan = tuple(self.ctx_plan(B, max_ctx))
         if not self.use_graphs:
             for _ in range(steps):
-                self._decode_step(B, sample, plan)
+                self._decode_step(B, sample, plan, guided)
             return
-        self.capture(B, sample, plan)
-        g = self.graphs[(B, sample, plan)]
+        self.capture(B, sample, plan, guided)
+        g = self.graphs[self.graph_key(B, sample, plan, guided)]
         for _ in range(steps):
             g.replay()
 
@@ -917,6 +933,65 @@ class ModelRunner:
         a, b, c = self._spec["stats"].tolist()
         return int(a), int(b), int(c)
 
+    # ------------------------------------------------------------------------------------ regex-constrained decoding
+    def enable_guided(self, tok_off, tok_blob) -> None:
+        """Allocate the device side of regex-constrained decoding: the tokenizer's byte table (CSR: ``tok_off`` int32
+        [>= V + 1], ``tok_blob`` uint8; numpy or torch, uploaded once) and one DFA table row per slot -- cls 256 B,
+        trans 64 KiB, accept 32 KiB -- plus g_on, the two state slots, g_base and the (S, C) dims (ops.dfa_mask)."""
+        off = torch.as_tensor(tok_off).to(torch.int64).reshape(-1)
+        blob = torch.as_tensor(tok_blob).to(torch.uint8).reshape(-1)
+        V = self.V
+        if off.numel() < V + 1:  # ids the tokenizer does not know decode to nothing
+            off = torch.cat([off, off[-1:].expand(V + 1 - off.numel())])
+        off = off[: V + 1]
+        if int(off[0]) != 0 or bool((off[1:] < off[:-1]).any()) or int(off[-1]) > blob.numel():
+            raise ValueError("token byte table: offsets must start at 0, not decrease, and end inside the blob")
+        if blob.numel() == 0:
+            blob = torch.zeros(1, dtype=torch.uint8)
+        dev, S = self.device, self.max_slots
+        i32 = dict(dtype=torch.int32, device=dev)
+        self.g_tok_off = off.to(torch.int32).to(dev)
+        self.g_tok_blob = blob.to(dev)
+        self.g_cls = torch.zeros(S, 256, dtype=torch.uint8, device=dev)
+        self.g_trans = torch.full((S, ref.DFA_MAX_TABLE), -1, dtype=torch.int16, device=dev)
+        self.g_accept = torch.zeros(S, ref.DFA_MAX_TABLE, dtype=torch.uint8, device=dev)
+        self.g_dim = torch.zeros(S, 2, **i32)
+        self.g_on = torch.zeros(S, **i32)
+        self.g_state = torch.zeros(S, 2, **i32)
+        self.g_base = torch.zeros(S, **i32)
+        self.guided = True
+        self.graphs.clear()
+
+    def _dfa_mask(self, logits, gen_len, input_ids, finished, rows=None) -> None:
+        ops.dfa_mask(logits, self.g_tok_off, self.g_tok_blob, self.g_cls, self.g_trans, self.g_accept, self.g_dim,
+                     self.g_on, self.g_state, self.g_base, gen_len, input_ids, finished, self.eos, rows=rows)
+
+    def _set_guided(self, entries: Sequence[dict], idx: torch.Tensor) -> None:
+        """The constraint part of ``set_slots``: g_on, both state slots (= the request's start state), g_base (the
+        row's gen_len at admission, which restarts at 0) and the dims of every admitted slot in one transfer, then the
+        tables of the constrained ones."""
+        n = len(entries)
+        meta = torch.zeros(n, 6, dtype=torch.int32)  # on | state, state | base | S, C
+        for i, e in enumerate(entries):
+            dfa = e.get("dfa")
+            sl = int(e["slot"])
+            if dfa is None:
+                self._g_host_on.discard(sl)
+                continue
+            self._g_host_on.add(sl)
+            st = int(e.get("dfa_state", dfa.start))
+            meta[i] = torch.tensor([1, st, st, 0, dfa.n_states, dfa.n_classes], dtype=torch.int32)
+            sc = dfa.n_states * dfa.n_classes
+            assert sc <= ref.DFA_MAX_TABLE and dfa.n_classes <= 256
+            self.g_cls[sl].copy_(torch.from_numpy(dfa.cls))
+            self.g_trans[sl, :sc].copy_(torch.from_numpy(dfa.trans.view("int16")))
+            self.g_accept[sl, : dfa.n_states].copy_(torch.from_numpy(dfa.accept))
+        mv = (meta.pin_memory() if self.on_gpu else meta).to(self.device, non_blocking=True)
+        self.g_on.index_copy_(0, idx, mv[:, 0])
+        self.g_state.index_copy_(0, idx, mv[:, 1:3])
+        self.g_base.index_copy_(0, idx, mv[:, 3])
+        self.g_dim.index_copy_(0, idx, mv[:, 4:6])
+
     # ------------------------------------------------------------------------------------ slots
     def set_slot(self, slot: int, blocks: Sequence[int], limit: int, temperature: float = 0.0, top_k: int = 40,
                  top_p: float = 0.9, seed: int = 0, eos_on: bool = True, repeat_penalty: float = 1.0,
@@ -990,6 +1065,10 @@ class ModelRunner:
         self.top_p.index_copy_(0, idx, fv[:, 1])
         self.penalty.index_copy_(0, idx, fv[:, 2])
         self.seeds.index_copy_(0, idx, sv)
+        if self.guided:
+            self._set_guided(entries, idx)
+        elif any(e.get("dfa") is not None for e in entries):
+            raise RuntimeError("a request carries a regex but the runner was built without guided decoding")
         if hist is not None:
             hv = hist.pin_memory() if self.on_gpu else hist
             hsel = torch.tensor([i for i, e in enumerate(entries) if float(e.get("repeat_penalty", 1.0)) != 1.0],
@@ -1033,6 +1112,7 @@ class ModelRunner:
 
     def release_slot(self, slot: int) -> None:
         self._pending_bt.pop(slot, None)
+        self._g_host_on.discard(slot)
         self.finished[slot] = 1
         self.positions[slot] = 0
         self.gen_len[slot] = 0
@@ -1110,6 +1190,10 @@ class ModelRunner:
         fin = torch.zeros(n, **i32)
         lim = self.limit.index_select(0, slot_t)
         eon = self.eos_on.index_select(0, slot_t)
+        if self.guided and any(sl in self._g_host_on for sl in slots):
+            # the first generated token obeys the constraint too: gl = 0 = g_base, so each row reads the start state
+            # the admission wrote; the table rows are the sequences' slots
+            self._dfa_mask(logits, gl, iid, fin, rows=slot_t.to(torch.int32))
         if sample_any:
             hist = self.hist.index_select(0, slot_t)
             ops.sample_commit(logits, hist, self.penalty.index_select(0, slot_t),

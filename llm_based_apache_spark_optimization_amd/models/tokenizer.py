@@ -10,7 +10,9 @@
 """
 from __future__ import annotations
 
+import json
 import os
+import re
 from typing import Optional, Sequence
 
 from .spec import ModelSpec
@@ -114,3 +116,85 @@ def tokenizer_for(spec: ModelSpec, path: Optional[str] = None):
         if eot is not None:
             tok.eos_ids = tuple(sorted(set(tok.eos_ids) | {eot}))
     return tok
+
+
+# ----------------------------------------------------------------------------------- token byte table
+def _gpt2_unicode_to_byte() -> dict:
+    """Inverse of the GPT-2 byte -> printable-unicode map that byte-level BPE vocabularies are written in."""
+    keep = list(range(ord("!"), ord("~") + 1)) + list(range(0xA1, 0xAD)) + list(range(0xAE, 0x100))
+    table, n = {}, 0
+    for b in range(256):
+        if b in keep:
+            table[chr(b)] = b
+        else:
+            table[chr(256 + n)] = b
+            n += 1
+    return table
+
+
+_BYTE_PIECE = re.compile(r"^<0x([0-9A-Fa-f]{2})>$")
+
+
+def _sp_piece_bytes(piece: str) -> bytes:
+    """SentencePiece rule: ``<0xNN>`` is one byte, ``\u2581`` a space."""
+    m = _BYTE_PIECE.match(piece)
+    if m:
+        return bytes([int(m.group(1), 16)])
+    return piece.replace("\u2581", " ").encode("utf-8")
+
+
+def _has_type(node, name: str) -> bool:
+    if isinstance(node, dict):
+        return node.get("type") == name or any(_has_type(v, name) for v in node.values())
+    if isinstance(node, list):
+        return any(_has_type(v, name) for v in node)
+    return False
+
+
+def token_bytes(tokenizer, vocab_size: Optional[int] = None):
+    """The bytes every vocabulary id decodes to, in CSR form: ``(offsets int32 [V + 1], blob uint8 [offsets[V]])``
+    (numpy).  Special, added, control and unknown ids map to zero bytes.  ``vocab_size`` (the model's, which may
+    exceed the tokenizer's) pads the table with zero-byte ids.  What regex-constrained decoding walks its DFA over."""
+    import numpy as np
+
+    pieces: dict = {}
+    if isinstance(tokenizer, ByteTokenizer):
+        n = tokenizer.vocab_size
+        for b in range(256):
+            if tokenizer.offset + b < n:
+                pieces[tokenizer.offset + b] = bytes([b])
+    elif getattr(tokenizer, "_tk", None) is not None:
+        tk = tokenizer._tk
+        cfg = json.loads(tk.to_str())
+        byte_level = _has_type(cfg.get("pre_tokenizer"), "ByteLevel") or _has_type(cfg.get("decoder"), "ByteLevel")
+        u2b = _gpt2_unicode_to_byte() if byte_level else None
+        added = set(tk.get_added_tokens_decoder())
+        vocab = tk.get_vocab(with_added_tokens=True)
+        n = max(vocab.values(), default=-1) + 1
+        for piece, i in vocab.items():
+            if i in added:
+                continue
+            if u2b is not None:
+                if all(ch in u2b for ch in piece):
+                    pieces[i] = bytes(u2b[ch] for ch in piece)
+            else:
+                pieces[i] = _sp_piece_bytes(piece)
+    elif getattr(tokenizer, "_sp", None) is not None:
+        sp = tokenizer._sp
+        n = sp.get_piece_size()
+        for i in range(n):
+            if sp.is_control(i) or sp.is_unknown(i) or sp.is_unused(i):
+                continue
+            pieces[i] = _sp_piece_bytes(sp.id_to_piece(i))
+    else:
+        raise TypeError(f"token_bytes: unsupported tokenizer {type(tokenizer).__name__}")
+    for e in (getattr(tokenizer, "bos_id", None), *getattr(tokenizer, "eos_ids", ())):
+        pieces.pop(e, None)
+    V = max(n, int(vocab_size or 0))
+    lens = np.zeros(V + 1, dtype=np.int64)
+    for i, b in pieces.items():
+        lens[i + 1] = len(b)
+    offsets = np.cumsum(lens).astype(np.int32)
+    blob = np.frombuffer(b"".join(pieces[i] for i in sorted(pieces)), dtype=np.uint8).copy()
+    assert int(offsets[-1]) == blob.shape[0]
+    return offsets, blob

@@ -1531,3 +1531,18 @@ def spec_commit(logits, draft, stats, out_tokens, gen_len, input_ids, positions,
     if part is None:
         part = torch.empty(T * ((V + 4095) // 4096), device=logits.device, dtype=torch.int64)
     ext().spec_commit(logits, part, draft, stats, out_tokens, gen_len, input_ids, positions, finished, eos, limit, eos_on)
+
+
+# ----------------------------------------------------------------------------------- regex-constrained decoding
+def dfa_mask(logits, tok_off, tok_blob, cls, trans, accept, g_dim, g_on, g_state, g_base, gen_len, input_ids,
+             finished, eos, rows=None):
+    """Regex-constrained decoding (kernels/guided.hip): every logit of ``logits`` [B, V] whose token would leave the
+    row's byte DFA without a possible match becomes -inf, in place; the EOS ids stay exactly in an accepting state.
+    The DFA state is advanced lazily from ``input_ids`` / ``gen_len`` into ``g_state`` (two slots per row), so the
+    commit kernels run unchanged after it.  ``rows`` int32 [B] maps logits rows to table rows (default: identity).
+    Operands and the exact rule: ``ops.reference.dfa_mask``."""
+    if not _gpu(logits):
+        return ref.dfa_mask(logits, tok_off, tok_blob, cls, trans, accept, g_dim, g_on, g_state, g_base, gen_len,
+                            input_ids, finished, eos, rows)
+    ext().dfa_mask(logits, tok_off, tok_blob, cls, trans, accept, g_dim, g_on, g_state, g_base, rows, gen_len,
+                   input_ids, finished, eos)

@@ -203,6 +203,69 @@ def argmax_commit(logits, out_tokens, gen_len, input_ids, positions, finished, e
     commit(logits.float().argmax(-1), out_tokens, gen_len, input_ids, positions, finished, eos, limit, eos_on)
 
 
+# ----------------------------------------------------------------------------------- regex-constrained decoding
+DFA_DEAD = 0xFFFF
+DFA_MAX_TABLE = 32768
+DFA_MAX_TOKEN_BYTES = 32
+
+
+def dfa_mask(logits, tok_off, tok_blob, cls, trans, accept, g_dim, g_on, g_state, g_base, gen_len, input_ids,
+             finished, eos, rows=None):
+    """Host twin of csrc/kernels/guided.hip.  Per row b of ``logits`` [B, V] (table row r = rows[b], or b):
+
+    * nothing happens when ``g_on[r] == 0`` or ``finished[b]``;
+    * the DFA state after n = gen_len[b] tokens is ``cur = g_state[r, n & 1]`` when n == g_base[r] (written at
+      admission), else the walk of input_ids[b]'s bytes from ``g_state[r, (n - 1) & 1]``, stored to slot n & 1;
+    * token t stays when its 1..32 bytes walk from ``cur`` to a state other than DEAD; an id of ``eos`` stays when
+      ``accept[r, cur]`` (or when cur is DEAD: the row can only stop); every other logit becomes -inf.
+
+    Tables: tok_off int32 [V + 1] / tok_blob uint8 (CSR token bytes), cls uint8 [Bmax, 256], trans int16 [Bmax, 32768]
+    (the u16 table's bits), accept uint8 [Bmax, 32768], g_dim int32 [Bmax, 2] = (S, C), g_state int32 [Bmax, 2]."""
+    B, V = logits.shape
+    off = tok_off.to(torch.int64).cpu()
+    lens = off[1:V + 1] - off[:V]
+    blob = tok_blob.cpu().to(torch.int64)
+    nb = max(1, blob.numel())
+    eos_ids = [int(e) for e in eos.reshape(-1).tolist() if 0 <= int(e) < V]
+    for b in range(B):
+        r = b if rows is None else int(rows[b])
+        if int(g_on[r]) == 0 or int(finished[b]) != 0:
+            continue
+        S, C = int(g_dim[r, 0]), int(g_dim[r, 1])
+        SC = min(max(S * C, 0), DFA_MAX_TABLE)
+        tr = trans[r].cpu().to(torch.int64) & 0xFFFF
+        cl = cls[r].cpu().to(torch.int64)
+
+        def step(s, byte):  # vectorised over tokens; s == DEAD stays DEAD
+            idx = s * C + cl[byte]
+            ok = (s != DFA_DEAD) & (idx < SC)
+            return torch.where(ok, tr[idx.clamp(0, DFA_MAX_TABLE - 1)], torch.full_like(s, DFA_DEAD))
+
+        n, base = int(gen_len[b]), int(g_base[r])
+        if n == base or n <= 0:
+            cur = int(g_state[r, n & 1]) & 0xFFFF
+        else:
+            t = int(input_ids[b])
+            cur = DFA_DEAD
+            if 0 <= t < V and 1 <= int(lens[t]) <= DFA_MAX_TOKEN_BYTES:
+                s = torch.tensor([int(g_state[r, (n - 1) & 1]) & 0xFFFF])
+                for i in range(int(lens[t])):
+                    s = step(s, blob[int(off[t]) + i].reshape(1))
+                cur = int(s)
+            g_state[r, n & 1] = cur
+        ok_len = (lens >= 1) & (lens <= DFA_MAX_TOKEN_BYTES)
+        s = torch.full((V,), cur, dtype=torch.int64)
+        for i in range(int(lens[ok_len].max()) if bool(ok_len.any()) else 0):
+            act = ok_len & (lens > i)
+            byte = blob[(off[:V] + i).clamp(max=nb - 1)] if blob.numel() else torch.zeros(V, dtype=torch.int64)
+            s = torch.where(act, step(s, byte), s)
+        allowed = ok_len & (s != DFA_DEAD)
+        eos_ok = cur == DFA_DEAD or (cur < S and int(accept[r, cur]) != 0)
+        for e in eos_ids:
+            allowed[e] = eos_ok
+        logits[b, ~allowed.to(logits.device)] = float("-inf")
+
+
 # ----------------------------------------------------------------------------------- prefix cache
 def kv_copy_blocks(kv, kv_scale, pairs):
     """Copy the whole KV block src to dst, with its scales, in every layer for K and V (csrc/kernels/kv_copy.hip);

@@ -23,6 +23,12 @@ def nl2sql_system(table_schema: str) -> str:
     return f"Table name is temp_view. The structure of the table is:\n{table_schema}"
 
 
+# Regex constraint of the NL->SQL answer (Settings.sql_guided; syntax: engine/guided.py): one statement that starts with
+# SELECT or WITH in either case, holds no backtick (Markdown fences) and no ';' inside, and ends at its first ';'.
+# Nothing can follow that ';' in the pattern, so the only token the engine allows after it is EOS.
+SQL_STATEMENT_REGEX = r"(?i)(select|with)\s[^;`]*;"
+
+
 def explain_prompt(error_message: str) -> str:
     return (
         f"The following Spark error occurred:\n\n"

@@ -31,6 +31,7 @@ from pydantic import BaseModel
 
 from .. import prompts
 from ..client import EngineUnavailable
+from ..engine.guided import GuidedRequestError
 from ..utils.metrics import REGISTRY, record_generation
 from ..utils.tracing import new_request_id
 from .pipeline import resolve_input
@@ -76,6 +77,12 @@ def create_app(ctx: Optional[AppContext] = None) -> FastAPI:
         # a dead engine answers at once (SURVEY.md §5 failure detection) instead of after the request timeout
         REGISTRY.inc("lsa_requests_total", 1, "requests", route=request.url.path.strip("/"), outcome="unavailable")
         return JSONResponse(status_code=503, content={"error": "engine unavailable", "detail": str(exc)})
+
+    @app.exception_handler(GuidedRequestError)
+    def bad_regex(request: Request, exc: GuidedRequestError):
+        # a pattern the engine cannot serve (unsupported syntax, too large, guided decoding off) is the caller's error
+        REGISTRY.inc("lsa_requests_total", 1, "requests", route=request.url.path.strip("/"), outcome="bad_regex")
+        return JSONResponse(status_code=400, content={"error": "invalid regex constraint", "detail": str(exc)})
 
     @app.post("/process-data/")
     def modify_string(data: InputString):

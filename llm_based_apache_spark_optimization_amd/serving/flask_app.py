@@ -29,6 +29,7 @@ from werkzeug.utils import secure_filename
 
 from .. import prompts
 from ..client import EngineUnavailable
+from ..engine.guided import GuidedRequestError
 from ..utils.metrics import REGISTRY
 from ..utils.tracing import new_request_id
 from .pipeline import ST_UPLOAD, unique_path
@@ -47,6 +48,10 @@ def create_app(ctx: Optional[AppContext] = None) -> Flask:
     @app.errorhandler(EngineUnavailable)
     def engine_down(exc):  # a dead engine answers at once instead of after the request timeout
         return jsonify({"error": "engine unavailable", "detail": str(exc)}), 503
+
+    @app.errorhandler(GuidedRequestError)
+    def bad_regex(exc):  # a regex constraint the engine cannot serve is the caller's error
+        return jsonify({"error": "invalid regex constraint", "detail": str(exc)}), 400
 
     @app.after_request
     def cors(resp):  # the reference enabled CORS for every origin (Flask/app.py:13)

@@ -119,9 +119,16 @@ class Pipeline:
         self.history = history
         self.settings = settings
         self.status = status or StatusBoard()
+        if (getattr(settings, "sql_guided", False) and getattr(settings, "engine", "") == "hip"
+                and not getattr(settings, "guided", False)):
+            raise ValueError("sql_guided needs guided (LSA_GUIDED=1): the engines must be built with regex-constrained "
+                             "decoding")
 
     # ------------------------------------------------------------------------------- LLM calls
     def nl2sql(self, table_schema: str, question: str, options: Optional[dict] = None, rid: str = ""):
+        if getattr(self.settings, "sql_guided", False) and not (options or {}).get("regex"):
+            # constrain the answer to one SELECT / WITH statement that stops at its ';' (the prompt is unchanged)
+            options = dict(options or {}, regex=prompts.SQL_STATEMENT_REGEX)
         with span("nl2sql", rid):
             res = self.backend.generate(self.settings.nl2sql_model, question,
                                         system=prompts.nl2sql_system(table_schema), options=options)

@@ -1,0 +1,203 @@
+"""Regex-constrained decoding on MI355X: what the device-side token mask costs.
+
+  kernel   ops.dfa_mask standalone (device us, captured-graph replays) at V = 32,000 and 128,256, B = 1 and 32, for
+           prompts.SQL_STATEMENT_REGEX (nearly every token stays alive, so every token is walked to its end) and for a
+           pattern at the table-size limit (S * C = 32768: the whole 64 KiB table is staged, most tokens die on their
+           first byte), beside ops.argmax_commit over the same logits (argmax_partial_kernel + the commit: one read
+           of the same rows).  The vocabulary is synthetic with the length profile of a BPE vocabulary: the 256
+           single bytes, then space-prefixed words of 2..12 bytes.
+  step     device time of a decode step replayed from the guided graph against the plain graph of the same engine, on
+           the same rows: duckdb-nsql-7B at batch 1 and batch 32 (128-token prompts), Llama-3.2-3B at batch 1 with a
+           2k-token prompt (the explain shape).  Every row carries the SQL pattern; 16-step runs in the order guided,
+           plain, plain, guided (the context grows with every run; the order cancels it), means of 2 x --reps runs
+           each.  The plain graph commits tokens the DFA never saw, so every guided run restarts the rows' lazy
+           advance inside the statement, as a re-admission would.
+
+Appends JSON lines to profiles/guided/guided_mask_mi355x.jsonl (--out overrides).  Needs a GPU.
+
+  python scripts/bench_guided.py [--layers N] [--skip kernel,step] [--reps 5] [--out FILE]
+"""
+from __future__ import annotations
+
+import argparse
+import dataclasses
+import json
+import os
+import random
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from llm_based_apache_spark_optimization_amd import ops, prompts  # noqa: E402
+from llm_based_apache_spark_optimization_amd.engine import LLMEngine, ModelRunner, SamplingParams  # noqa: E402
+from llm_based_apache_spark_optimization_amd.engine.guided import MAX_TABLE, compile_regex  # noqa: E402
+from llm_based_apache_spark_optimization_amd.models import get_spec  # noqa: E402
+from llm_based_apache_spark_optimization_amd.models.llama import init_random  # noqa: E402
+
+OUT = os.path.join(ROOT, "profiles", "guided", "guided_mask_mi355x.jsonl")
+LIMIT_PATTERN = r"(abcdefghijklmnopqrstuvwxyz01234){33}"  # 1024 states x 32 classes
+
+
+def emit(rec: dict) -> None:
+    os.makedirs(os.path.dirname(OUT), exist_ok=True)
+    with open(OUT, "a") as f:
+        f.write(json.dumps(rec) + "\n")
+    print(json.dumps(rec), flush=True)
+
+
+def time_graph(fn, iters: int = 30) -> float:
+    """us per call of fn, replayed from a captured graph of 10 calls (device events)."""
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        fn()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, stream=s):
+            for _ in range(10):
+                fn()
+    torch.cuda.current_stream().wait_stream(s)
+    g.replay()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        g.replay()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) * 1e3 / (iters * 10)
+
+
+def synthetic_vocab(V: int, seed: int = 0):
+    """(offsets int32 [V + 1], blob uint8) of a BPE-like vocabulary: ids 0..2 empty (specials), 256 single bytes,
+    then words of 2..12 bytes (mean ~6), half of them space-prefixed."""
+    rng = random.Random(seed)
+    letters = b"etaoinsrhldcumfpgwybvkxjqzETAOINSRHLDCUM0123456789_(),.*=<>'\""
+    words = [b"", b"", b""] + [bytes([b]) for b in range(256)]
+    while len(words) < V:
+        n = min(12, max(2, int(rng.gauss(6, 2.5))))
+        w = bytes(rng.choice(letters) for _ in range(n))
+        words.append(b" " + w[:-1] if rng.random() < 0.5 else w)
+    lens = [len(w) for w in words]
+    off = torch.cumsum(torch.tensor([0] + lens, dtype=torch.int64), 0).to(torch.int32)
+    blob = torch.frombuffer(bytearray(b"".join(words)), dtype=torch.uint8).clone()
+    return off, blob
+
+
+def tables(dfa, slots: int, dev, state: int):
+    cls = torch.zeros(slots, 256, dtype=torch.uint8)
+    trans = torch.full((slots, MAX_TABLE), -1, dtype=torch.int16)
+    accept = torch.zeros(slots, MAX_TABLE, dtype=torch.uint8)
+    sc = dfa.n_states * dfa.n_classes
+    cls[:] = torch.from_numpy(dfa.cls)
+    trans[:, :sc] = torch.from_numpy(dfa.trans.view("int16"))
+    accept[:, : dfa.n_states] = torch.from_numpy(dfa.accept)
+    dim = torch.tensor([[dfa.n_states, dfa.n_classes]] * slots, dtype=torch.int32)
+    st = torch.full((slots, 2), state, dtype=torch.int32)
+    return [t.to(dev) for t in (cls, trans, accept, dim, torch.ones(slots, dtype=torch.int32), st,
+                                torch.zeros(slots, dtype=torch.int32))]
+
+
+def bench_kernel(dev) -> None:
+    sql = compile_regex(prompts.SQL_STATEMENT_REGEX)
+    lim = compile_regex(LIMIT_PATTERN)
+    cases = (("sql", sql, sql.walk(sql.start, b"SELECT ")), ("limit", lim, lim.walk(lim.start, b"abc")))
+    for V in (32000, 128256):
+        off, blob = synthetic_vocab(V)
+        off, blob = off.to(dev), blob.to(dev)
+        for B in (1, 32):
+            i32 = dict(dtype=torch.int32, device=dev)
+            logits = torch.randn(B, V, device=dev)
+            z = torch.zeros(B, **i32)
+            eos = torch.tensor([2], **i32)
+            out_tokens = torch.zeros(B, 8, **i32)
+            part = torch.zeros(B * ((V + 4095) // 4096), dtype=torch.int64, device=dev)
+            st = [out_tokens, torch.zeros(B, **i32), torch.zeros(B, **i32), torch.zeros(B, **i32), torch.ones(B, **i32)]
+            t_arg = time_graph(lambda: ops.argmax_commit(logits, *st, eos, part=part))
+            for name, dfa, state in cases:
+                cls, trans, accept, dim, on, gst, base = tables(dfa, B, dev, state)
+                work = logits.clone()
+                t = time_graph(lambda: ops.dfa_mask(work, off, blob, cls, trans, accept, dim, on, gst, base, z, z, z,
+                                                    eos))
+                alive = int(torch.isfinite(work).sum()) // B
+                emit(dict(bench="kernel", V=V, B=B, pattern=name, states=dfa.n_states, classes=dfa.n_classes,
+                          table_bytes=2 * dfa.n_states * dfa.n_classes, blob_bytes=int(blob.numel()),
+                          tokens_alive_per_row=alive, dfa_mask_us=round(t, 2), argmax_commit_us=round(t_arg, 2),
+                          ratio=round(t / t_arg, 2)))
+
+
+def bench_step(dev, layers: int, reps: int) -> None:
+    for base, B, plen in (("duckdb-nsql", 1, 128), ("duckdb-nsql", 32, 128), ("llama3.2", 1, 2048)):
+        spec = get_spec(base)
+        if layers:
+            spec = dataclasses.replace(spec, n_layers=layers, name=f"{base}-{layers}l")
+        w = init_random(spec, dev, seed=5, kind="bf16")
+        new, run = 1024, 16
+        r = ModelRunner(w, max_slots=B, max_model_len=plen + new + 64, num_kv_blocks=B * ((plen + new) // 64 + 2) + 1)
+        r.enable_guided(*synthetic_vocab(spec.vocab_size))
+        eng = LLMEngine(r, name=spec.name, kv_reserve_tokens=-1, guided=True)  # every KV block reserved at admission
+        g = torch.Generator().manual_seed(7)
+        sp = SamplingParams(max_tokens=new, regex=prompts.SQL_STATEMENT_REGEX)
+        for _ in range(B):
+            eng.add_request([1] + torch.randint(3, spec.vocab_size, (plen - 1,), generator=g).tolist(), sp)
+        eng.step()  # prefill (the first token obeys the pattern) + one guided decode run
+        ctx = plen + new
+
+        def timed(guided: bool) -> float:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            r.decode(B, run, False, max_ctx=ctx, guided=guided)
+            e1.record()
+            torch.cuda.synchronize()
+            return e0.elapsed_time(e1) / run
+
+        dfa = compile_regex(prompts.SQL_STATEMENT_REGEX)
+        inside = dfa.walk(dfa.start, b"SELECT ")  # the state inside the statement: nearly every token stays alive
+
+        def rebase() -> None:
+            """The plain graph commits tokens the DFA never saw: restart every row's lazy advance inside the statement,
+            at its current gen_len (what a re-admission writes)."""
+            r.g_base[:B].copy_(r.gen_len[:B])
+            r.g_state[:B].fill_(inside)
+
+        rebase(), timed(True), timed(False)
+        gd, pl = [], []
+        for _ in range(reps):  # guided, plain, plain, guided: the context grows by 16 per run, the order cancels it
+            for guided in (True, False, False, True):
+                if guided:
+                    rebase()
+                (gd if guided else pl).append(timed(guided))
+        live = B - int(r.finished[:B].sum())
+        gm, pm = statistics.mean(gd), statistics.mean(pl)
+        emit(dict(bench="step", model=spec.name, layers=spec.n_layers, B=B, prompt=plen, vocab=spec.vocab_size,
+                  rows_live_after_guided_runs=live, plain_step_ms=round(pm, 4), guided_step_ms=round(gm, 4),
+                  mask_cost_us=round((gm - pm) * 1e3, 1), ratio=round(gm / pm, 4)))
+        eng.abort_all("bench over")
+        del eng, r, w
+        torch.cuda.empty_cache()
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--layers", type=int, default=0, help="truncate the models to this many layers (0 = full depth)")
+    ap.add_argument("--skip", default="", help="comma list of kernel,step")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--out", default="", help="JSON-lines file to append to")
+    a = ap.parse_args()
+    global OUT
+    OUT = a.out or OUT
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_guided.py needs a GPU")
+    ops.ext()
+    dev = torch.device("cuda:0")
+    skip = set(a.skip.split(",")) if a.skip else set()
+    if "kernel" not in skip:
+        bench_kernel(dev)
+    if "step" not in skip:
+        bench_step(dev, a.layers, a.reps)
+
+
+if __name__ == "__main__":
+    main()
