@@ -67,6 +67,12 @@ int lsa_dfa_mask(float* logits, int B, int V, const int* tok_off, const uint8_t*
                  const uint16_t* trans, const uint8_t* accept, const int* g_dim, const int* g_on, int* g_state,
                  const int* g_base, const int* rows, const int* gen_len, const int* input_ids, const int* finished,
                  const int* eos, int neos, hipStream_t s);
+int lsa_dfa_mask_verify(float* logits, int T, int V, const int* tok_off, const uint8_t* tok_blob, const uint8_t* cls,
+                        const uint16_t* trans, const uint8_t* accept, const int* g_dim, const int* g_on, int* g_state,
+                        const int* g_base, int r, const int* gen_len, const int* input_ids, const int* finished,
+                        const int* eos, int neos, const int* draft, int* g_spec, hipStream_t s);
+int lsa_dfa_spec_advance(const int* g_on, int* g_state, const int* g_spec, const int* gen_len, int r, int k,
+                         hipStream_t s);
 int lsa_spec_commit(const float* logits, int T, int V, unsigned long long* part, const int* draft, long long* stats,
                     int* out_tokens, int max_new, int* gen_len, int* input_ids, int* positions, int* finished,
                     const int* eos, int neos, const int* limit, const int* eos_on, hipStream_t s);
@@ -1036,6 +1042,68 @@ void dfa_mask(at::Tensor& logits, const at::Tensor& tok_off, const at::Tensor& t
         "dfa_mask");
 }
 
+// Speculative decoding of a constrained request: the mask of the T = k + 1 verify rows of the sequence in state row 0
+// (table row r); row t is masked in the DFA state after the input token and drafts 1..t.  g_spec int32 [>= 9]:
+// gen_len at the launch, then the T states (kernels/guided.hip dfa_mask_verify_kernel).
+void dfa_mask_verify(at::Tensor& logits, const at::Tensor& tok_off, const at::Tensor& tok_blob, const at::Tensor& cls,
+                     const at::Tensor& trans, const at::Tensor& accept, const at::Tensor& g_dim, const at::Tensor& g_on,
+                     at::Tensor& g_state, const at::Tensor& g_base, int64_t r, const at::Tensor& gen_len,
+                     const at::Tensor& input_ids, const at::Tensor& finished, const at::Tensor& eos,
+                     const at::Tensor& draft, at::Tensor& g_spec) {
+  need(logits, at::kFloat, "logits");
+  TORCH_CHECK(logits.dim() == 2 && logits.is_contiguous() && logits.size(0) >= 2 && logits.size(0) <= 8 &&
+                  logits.size(1) >= 1 && logits.numel() < 0x7fffffffLL, "logits: contiguous [2 <= T <= 8, V >= 1]");
+  const int64_t T = logits.size(0), V = logits.size(1);
+  need(tok_off, at::kInt, "tok_off");
+  need(tok_blob, at::kByte, "tok_blob");
+  need(cls, at::kByte, "cls");
+  need(trans, at::kShort, "trans");
+  need(accept, at::kByte, "accept");
+  TORCH_CHECK(tok_off.is_contiguous() && tok_off.numel() == V + 1 && tok_blob.is_contiguous() && tok_blob.numel() >= 1,
+              "dfa_mask_verify: tok_off [V + 1], tok_blob non-empty");
+  TORCH_CHECK(cls.dim() == 2 && cls.size(1) == 256 && cls.is_contiguous(), "cls: contiguous [Bmax, 256]");
+  const int64_t Bmax = cls.size(0);
+  TORCH_CHECK(trans.dim() == 2 && trans.size(0) == Bmax && trans.size(1) == 32768 && trans.is_contiguous() &&
+                  accept.dim() == 2 && accept.size(0) == Bmax && accept.size(1) == 32768 && accept.is_contiguous(),
+              "trans / accept: contiguous [Bmax, 32768]");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(trans.data_ptr()) % 16 == 0, "trans must be 16-byte aligned");
+  const at::Tensor &g_state_c = g_state, &g_spec_c = g_spec;
+  for (const at::Tensor* t : {&g_dim, &g_on, &g_state_c, &g_base, &gen_len, &input_ids, &finished, &eos, &draft,
+                              &g_spec_c}) {
+    need(*t, at::kInt, "dfa_mask_verify state operand");
+    TORCH_CHECK(t->is_contiguous(), "dfa_mask_verify state operands must be contiguous");
+  }
+  TORCH_CHECK(g_dim.numel() == 2 * Bmax && g_state.numel() == 2 * Bmax && g_on.numel() == Bmax && g_base.numel() == Bmax,
+              "dfa_mask_verify: g_dim / g_state [Bmax, 2], g_on / g_base [Bmax]");
+  TORCH_CHECK(r >= 0 && r < Bmax, "dfa_mask_verify: table row out of range");
+  TORCH_CHECK(gen_len.numel() >= 1 && input_ids.numel() >= 1 && finished.numel() >= 1, "dfa_mask_verify: state row 0");
+  TORCH_CHECK(draft.numel() >= T - 1 && g_spec.numel() >= 9, "dfa_mask_verify: draft [T - 1], g_spec [1 + 8]");
+  check(lsa_dfa_mask_verify(logits.data_ptr<float>(), T, V, tok_off.data_ptr<int>(), tok_blob.data_ptr<uint8_t>(),
+                            cls.data_ptr<uint8_t>(), reinterpret_cast<const uint16_t*>(trans.data_ptr<int16_t>()),
+                            accept.data_ptr<uint8_t>(), g_dim.data_ptr<int>(), g_on.data_ptr<int>(),
+                            g_state.data_ptr<int>(), g_base.data_ptr<int>(), (int)r, gen_len.data_ptr<int>(),
+                            input_ids.data_ptr<int>(), finished.data_ptr<int>(), eos.data_ptr<int>(), eos.numel(),
+                            draft.data_ptr<int>(), g_spec.data_ptr<int>(), cur_stream()),
+        "dfa_mask_verify");
+}
+
+// After spec_commit: the state after the accepted drafts (g_spec) into the slot the next mask launch advances from.
+void dfa_spec_advance(const at::Tensor& g_on, at::Tensor& g_state, const at::Tensor& g_spec, const at::Tensor& gen_len,
+                      int64_t r, int64_t k) {
+  const at::Tensor& g_state_c = g_state;
+  for (const at::Tensor* t : {&g_on, &g_state_c, &g_spec, &gen_len}) {
+    need(*t, at::kInt, "dfa_spec_advance operand");
+    TORCH_CHECK(t->is_contiguous(), "dfa_spec_advance operands must be contiguous");
+  }
+  TORCH_CHECK(k >= 1 && k <= 7, "dfa_spec_advance: 1 <= k <= 7");
+  TORCH_CHECK(r >= 0 && r < g_on.numel() && g_state.numel() == 2 * g_on.numel(),
+              "dfa_spec_advance: g_on [Bmax], g_state [Bmax, 2], 0 <= r < Bmax");
+  TORCH_CHECK(g_spec.numel() >= 9 && gen_len.numel() >= 1, "dfa_spec_advance: g_spec [1 + 8], gen_len row 0");
+  check(lsa_dfa_spec_advance(g_on.data_ptr<int>(), g_state.data_ptr<int>(), g_spec.data_ptr<int>(),
+                             gen_len.data_ptr<int>(), (int)r, (int)k, cur_stream()),
+        "dfa_spec_advance");
+}
+
 void sample_commit(at::Tensor& logits, at::Tensor& part, at::Tensor& cand, const c10::optional<at::Tensor>& hist,
                    const c10::optional<at::Tensor>& penalty, const c10::optional<at::Tensor>& last_n,
                    const at::Tensor& temperature, const at::Tensor& top_k,
@@ -1272,6 +1340,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("dfa_mask", &dfa_mask, py::arg("logits"), py::arg("tok_off"), py::arg("tok_blob"), py::arg("cls"),
         py::arg("trans"), py::arg("accept"), py::arg("g_dim"), py::arg("g_on"), py::arg("g_state"), py::arg("g_base"),
         py::arg("rows"), py::arg("gen_len"), py::arg("input_ids"), py::arg("finished"), py::arg("eos"));
+  m.def("dfa_mask_verify", &dfa_mask_verify, py::arg("logits"), py::arg("tok_off"), py::arg("tok_blob"), py::arg("cls"),
+        py::arg("trans"), py::arg("accept"), py::arg("g_dim"), py::arg("g_on"), py::arg("g_state"), py::arg("g_base"),
+        py::arg("r"), py::arg("gen_len"), py::arg("input_ids"), py::arg("finished"), py::arg("eos"), py::arg("draft"),
+        py::arg("g_spec"));
+  m.def("dfa_spec_advance", &dfa_spec_advance, py::arg("g_on"), py::arg("g_state"), py::arg("g_spec"),
+        py::arg("gen_len"), py::arg("r"), py::arg("k"));
   m.def("fp8_dequant", &fp8_dequant);
   m.def("quant_rows_fp8", &quant_rows_fp8);
   m.def("fp8_gemm_t256", &fp8_gemm_t256, py::arg("x8"), py::arg("sx"), py::arg("wq"), py::arg("sw"), py::arg("N"),

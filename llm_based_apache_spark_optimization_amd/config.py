@@ -68,6 +68,9 @@ class Settings:
     # prompts.SQL_STATEMENT_REGEX -- one SELECT / WITH statement that ends at its first ';'
     guided: bool = dataclasses.field(default_factory=lambda: _env("GUIDED", False, bool))
     sql_guided: bool = dataclasses.field(default_factory=lambda: _env("SQL_GUIDED", False, bool))
+    # constrained requests speculate too (off: a request with a regex takes plain guided steps whatever spec_tokens
+    # says).  Needs guided and spec_tokens; the tokens are those of the plain guided steps
+    spec_guided: bool = dataclasses.field(default_factory=lambda: _env("SPEC_GUIDED", False, bool))
     tp: int = dataclasses.field(default_factory=lambda: _env("TP", 1, int))
     dp: int = dataclasses.field(default_factory=lambda: _env("DP", 1, int))
     max_batch: int = dataclasses.field(default_factory=lambda: _env("MAX_BATCH", 32, int))

@@ -64,7 +64,8 @@ class SamplingParams:
     # regex-constrained decoding, where the engine runs it (LLMEngine(guided=True)): the Ollama option extension
     # "regex".  The generated text -- its UTF-8 bytes -- is a full match of the pattern (engine/guided.py: the supported
     # syntax) when the request ends by EOS; EOS is allowed only then.  A request that ends at its length limit is
-    # returned as it stands, possibly short of a match.  Not with ignore_eos; a constrained request never speculates.
+    # returned as it stands, possibly short of a match.  Not with ignore_eos.  A constrained request speculates only
+    # on an engine built with spec_guided (LSA_SPEC_GUIDED=1); its tokens are those of its plain guided steps.
     regex: Optional[str] = None
 
     @property
@@ -366,7 +367,10 @@ class LLMEngine:
                 ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
                 ev[0].record()
             if spec_T:
-                r.decode_spec(n_steps, max_ctx=max_ctx)
+                if guided:  # spec_guided: the verify graph with the mask of the T verify rows
+                    r.decode_spec(n_steps, max_ctx=max_ctx, guided=True)
+                else:
+                    r.decode_spec(n_steps, max_ctx=max_ctx)
             else:
                 if guided:  # the graph variant with the mask launch, only while a running row is constrained
                     r.decode(B, n_steps, sample, max_ctx=max_ctx, guided=True)
@@ -378,7 +382,7 @@ class LLMEngine:
         with self._lock:
             self.stats["decode_s"] += time.perf_counter() - t0
             self.stats["decode_steps"] += n_steps
-            if guided and n_steps and not spec_T:
+            if guided and n_steps:  # plain masked steps and (spec_guided) masked verify steps
                 self.stats["guided_steps"] += n_steps
                 REGISTRY.inc("lsa_guided_steps_total", n_steps, "decode steps run with the regex mask", model=self.name)
             if spec_T and n_steps:
@@ -465,8 +469,10 @@ class LLMEngine:
         q = reqs[0]
         sp = q.params
         if (q.slot != 0 or self.sched.highest_slot != 0 or self.sched.num_running != 1 or sp.needs_sampler
-                or not sp.speculate or q.spec_off or q.dfa is not None):
+                or not sp.speculate or q.spec_off):
             return 0
+        if q.dfa is not None and not (getattr(r, "spec_guided", False) and getattr(r, "guided", False)):
+            return 0  # a constrained request speculates only with the opt-in (the guided verify graph)
         T = r.spec_k() + 1
         steps = min(n_steps, -(-remaining // T))
         if len(q.ctx_ids) + q.gen_host + steps * T + T > r.max_model_len:

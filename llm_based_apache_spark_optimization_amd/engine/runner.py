@@ -48,7 +48,7 @@ class ModelRunner:
                  max_new_cap: Optional[int] = None, tp=None, use_graphs: bool = True,
                  fuse_rope: Optional[bool] = None, seq_parallel: Optional[bool] = None, sp_min_tokens: Optional[int] = None,
                  kv_dtype: Optional[str] = None, spec_tokens: int = 0, spec_ngram: tuple = (3, 1),
-                 spec_quantized: bool = False):
+                 spec_quantized: bool = False, spec_guided: bool = False):
         self.w = weights
         # prompt-lookup speculative decoding (``_verify_step``): tokens drafted per step (0 = off) and the drafter's
         # (longest, shortest) n-gram.  Plain attributes: an experiment may set them on a built runner.
@@ -57,6 +57,9 @@ class ModelRunner:
         # opt-in: verify steps for fp8 / MXFP4 weights and the fp8 KV cache too (``spec_supported``).  Their verify rows
         # run the weight-only GEMMs (bf16 activations), whatever the plain batch-1 step of the model runs.
         self.spec_quantized = bool(spec_quantized)
+        # opt-in: verify steps for regex-constrained requests too (``_verify_step(guided=True)``: the mask of the T
+        # verify rows and the DFA state's hand-over inside the verify graph).  Inert without ``enable_guided``.
+        self.spec_guided = bool(spec_guided)
         # acceptance guard of the engine: a request whose accepted-per-verify-step mean falls below this after 16
         # verify steps takes plain steps for the rest of its life.  Break-even = verify-step time / plain-step time - 1.
         # Measured on MI355X (scripts/bench_spec.py, profiles/spec/spec_decode_mi355x.jsonl; plain vs verify step, k = 3):
@@ -792,7 +795,7 @@ class ModelRunner:
         buf.copy_(table.to(torch.int32))
         self._spec_forced = buf
 
-    def _verify_step(self, plan: Optional[tuple] = None) -> None:
+    def _verify_step(self, plan: Optional[tuple] = None, guided: bool = False) -> None:
         """One speculative-decoding step of the request in slot 0: a forward pass over T = k + 1 rows -- the row's input
         token and k drafted tokens at positions p .. p + T - 1 -- and the in-order commit of the tokens greedy decoding
         would have produced (``ops.spec_commit``): between 1 and T per step, the same sequence as plain steps.
@@ -812,7 +815,12 @@ class ModelRunner:
         of it, so rewriting a stale odd token never touches its committed even partner, and the other way round.
 
         fp8 / MXFP4 weights: every verify row runs the weight-only GEMMs (W8A16 / W4A16) through ``ops.linear``, the
-        lm_head included; there are no e4m3 activations in a verify step."""
+        lm_head included; there are no e4m3 activations in a verify step.
+
+        ``guided`` (a constrained request, ``spec_guided``): ``dfa_mask_verify`` between the lm_head and spec_commit masks
+        row t in the DFA state after the input token and drafts 1..t, so the commit accepts a draft only where the plain
+        guided step would have chosen it; ``dfa_spec_advance`` after the commit leaves the state after the accepted
+        drafts where the next mask launch -- verify or plain -- advances from."""
         w, d, T = self.w, self.d, self.spec_k() + 1
         sb = self._spec_bufs()
         n_max, n_min = self.spec_ngram
@@ -863,8 +871,14 @@ class ModelRunner:
         ops.add_rmsnorm(h, w.final_norm, self.eps, xn, parts=d_parts, rows=T)
         logits = sb["logits"][:T]
         lin(xn, w.lm_head, "f32", out=logits, splitk=1)
+        if guided:
+            ops.dfa_mask_verify(logits, self.g_tok_off, self.g_tok_blob, self.g_cls, self.g_trans, self.g_accept,
+                                self.g_dim, self.g_on, self.g_state, self.g_base, st[1], st[2], st[4], self.eos,
+                                sb["draft"][:T - 1], self.g_spec)
         ops.spec_commit(logits, sb["draft"][:T - 1], sb["stats"], *st, self.eos, self.limit[:1], self.eos_on[:1],
                         part=sb["amax_part"] if self.on_gpu else None)
+        if guided:
+            ops.dfa_spec_advance(self.g_on, self.g_state, self.g_spec, st[1], T - 1)
 
     def _verify_linear_cpu(self, x, wt, epi, out, splitk=1, rownorm=None, pre=False):
         """CPU twin of the verify step's GEMMs, one row at a time with the rounding points of the plain batch-1 step's
@@ -900,17 +914,21 @@ class ModelRunner:
         """[k] int32: the drafts of the last verify step (-1 = none)."""
         return self._spec_bufs()["draft"][: self.spec_k()]
 
-    def decode_spec(self, steps: int, max_ctx: Optional[int] = None) -> None:
+    def decode_spec(self, steps: int, max_ctx: Optional[int] = None, guided: bool = False) -> None:
         """Run ``steps`` verify steps of the request in slot 0 (the analogue of ``decode`` at bucket 1); ``max_ctx``
-        bounds pos0 + T during the run (picks the split plan's tier)."""
+        bounds pos0 + T during the run (picks the split plan's tier).  ``guided``: the variant with the regex mask of
+        the verify rows, for a constrained request (its graph key is the unguided one with a trailing True)."""
         assert self.spec_supported(), ("speculative decoding: TP = 1, spec_tokens > 0, bf16 weights and KV cache "
                                        "(or spec_quantized)")
+        assert not guided or (self.guided and self.spec_guided), "guided verify steps need enable_guided() and spec_guided"
         plan = tuple(self.ctx_plan(1, max_ctx))
         if not self.use_graphs:
             for _ in range(steps):
-                self._verify_step(plan)
+                self._verify_step(plan, guided)
             return
         key = ("spec", self.spec_k() + 1, plan, 0 if self._spec_forced is None else self._spec_forced.data_ptr())
+        if guided:
+            key += (True,)
         if key not in self.graphs:
             self._spec_bufs()
             s = torch.cuda.Stream(device=self.device)
@@ -918,7 +936,7 @@ class ModelRunner:
             g = torch.cuda.CUDAGraph()
             with torch.cuda.stream(s):
                 with torch.cuda.graph(g, stream=s):
-                    self._verify_step(plan)
+                    self._verify_step(plan, guided)
             torch.cuda.current_stream(self.device).wait_stream(s)
             self.graphs[key] = g
         g = self.graphs[key]
@@ -937,7 +955,8 @@ class ModelRunner:
     def enable_guided(self, tok_off, tok_blob) -> None:
         """Allocate the device side of regex-constrained decoding: the tokenizer's byte table (CSR: ``tok_off`` int32
         [>= V + 1], ``tok_blob`` uint8; numpy or torch, uploaded once) and one DFA table row per slot -- cls 256 B,
-        trans 64 KiB, accept 32 KiB -- plus g_on, the two state slots, g_base and the (S, C) dims (ops.dfa_mask)."""
+        trans 64 KiB, accept 32 KiB -- plus g_on, the two state slots, g_base and the (S, C) dims (ops.dfa_mask), and
+        g_spec: gen_len and the states of the T <= 8 verify rows of a guided verify step (ops.dfa_mask_verify)."""
         off = torch.as_tensor(tok_off).to(torch.int64).reshape(-1)
         blob = torch.as_tensor(tok_blob).to(torch.uint8).reshape(-1)
         V = self.V
@@ -959,6 +978,7 @@ class ModelRunner:
         self.g_on = torch.zeros(S, **i32)
         self.g_state = torch.zeros(S, 2, **i32)
         self.g_base = torch.zeros(S, **i32)
+        self.g_spec = torch.zeros(1 + 8, **i32)
         self.guided = True
         self.graphs.clear()
 

@@ -1546,3 +1546,28 @@ def dfa_mask(logits, tok_off, tok_blob, cls, trans, accept, g_dim, g_on, g_state
                             input_ids, finished, eos, rows)
     ext().dfa_mask(logits, tok_off, tok_blob, cls, trans, accept, g_dim, g_on, g_state, g_base, rows, gen_len,
                    input_ids, finished, eos)
+
+
+def dfa_mask_verify(logits, tok_off, tok_blob, cls, trans, accept, g_dim, g_on, g_state, g_base, gen_len, input_ids,
+                    finished, eos, draft, g_spec, r: int = 0):
+    """The regex mask of a verify step (kernels/guided.hip dfa_mask_verify_kernel): ``logits`` [T, V] are the T = k + 1
+    verify rows of the sequence in state row 0 (table row ``r``), ``draft`` [k] int32 what ``spec_draft`` wrote.  Row t
+    is masked as ``dfa_mask`` masks a row whose state is the one after the input token and drafts 1..t (DEAD from the
+    first draft that is -1, unknown, of 0 or > 32 bytes, or kills the walk).  ``g_spec`` int32 [1 + 8] receives gen_len
+    and the T states for ``dfa_spec_advance``.  The exact rule: ``ops.reference.dfa_mask_verify``."""
+    if not 2 <= logits.shape[0] <= 8:
+        raise ValueError("dfa_mask_verify: 2 <= T <= 8 verify rows")
+    if not _gpu(logits):
+        return ref.dfa_mask_verify(logits, tok_off, tok_blob, cls, trans, accept, g_dim, g_on, g_state, g_base, gen_len,
+                                   input_ids, finished, eos, draft, g_spec, r)
+    ext().dfa_mask_verify(logits, tok_off, tok_blob, cls, trans, accept, g_dim, g_on, g_state, g_base, int(r), gen_len,
+                          input_ids, finished, eos, draft, g_spec)
+
+
+def dfa_spec_advance(g_on, g_state, g_spec, gen_len, k: int, r: int = 0):
+    """After ``spec_commit`` (one wave): with a = gen_len[0] - g_spec[0] - 1 accepted drafts, 0 <= a <= k, the state
+    g_spec[1 + a] goes to g_state[r, (gen_len[0] - 1) & 1] -- where the next mask launch, verify or plain, advances
+    from."""
+    if not _gpu(g_state):
+        return ref.dfa_spec_advance(g_on, g_state, g_spec, gen_len, k, r)
+    ext().dfa_spec_advance(g_on, g_state, g_spec, gen_len, int(r), int(k))

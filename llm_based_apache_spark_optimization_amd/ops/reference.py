@@ -222,48 +222,109 @@ def dfa_mask(logits, tok_off, tok_blob, cls, trans, accept, g_dim, g_on, g_state
     Tables: tok_off int32 [V + 1] / tok_blob uint8 (CSR token bytes), cls uint8 [Bmax, 256], trans int16 [Bmax, 32768]
     (the u16 table's bits), accept uint8 [Bmax, 32768], g_dim int32 [Bmax, 2] = (S, C), g_state int32 [Bmax, 2]."""
     B, V = logits.shape
-    off = tok_off.to(torch.int64).cpu()
-    lens = off[1:V + 1] - off[:V]
-    blob = tok_blob.cpu().to(torch.int64)
-    nb = max(1, blob.numel())
-    eos_ids = [int(e) for e in eos.reshape(-1).tolist() if 0 <= int(e) < V]
+    tk = _dfa_tokens(V, tok_off, tok_blob, eos)
     for b in range(B):
         r = b if rows is None else int(rows[b])
         if int(g_on[r]) == 0 or int(finished[b]) != 0:
             continue
-        S, C = int(g_dim[r, 0]), int(g_dim[r, 1])
-        SC = min(max(S * C, 0), DFA_MAX_TABLE)
-        tr = trans[r].cpu().to(torch.int64) & 0xFFFF
-        cl = cls[r].cpu().to(torch.int64)
+        tab = _DfaRow(r, cls, trans, accept, g_dim)
+        cur = _dfa_lazy_advance(tab, tk, g_state, g_base, int(gen_len[b]), int(input_ids[b]))
+        _dfa_mask_row(logits[b], tab, tk, cur)
 
-        def step(s, byte):  # vectorised over tokens; s == DEAD stays DEAD
-            idx = s * C + cl[byte]
-            ok = (s != DFA_DEAD) & (idx < SC)
-            return torch.where(ok, tr[idx.clamp(0, DFA_MAX_TABLE - 1)], torch.full_like(s, DFA_DEAD))
 
-        n, base = int(gen_len[b]), int(g_base[r])
-        if n == base or n <= 0:
-            cur = int(g_state[r, n & 1]) & 0xFFFF
-        else:
-            t = int(input_ids[b])
-            cur = DFA_DEAD
-            if 0 <= t < V and 1 <= int(lens[t]) <= DFA_MAX_TOKEN_BYTES:
-                s = torch.tensor([int(g_state[r, (n - 1) & 1]) & 0xFFFF])
-                for i in range(int(lens[t])):
-                    s = step(s, blob[int(off[t]) + i].reshape(1))
-                cur = int(s)
-            g_state[r, n & 1] = cur
-        ok_len = (lens >= 1) & (lens <= DFA_MAX_TOKEN_BYTES)
-        s = torch.full((V,), cur, dtype=torch.int64)
-        for i in range(int(lens[ok_len].max()) if bool(ok_len.any()) else 0):
-            act = ok_len & (lens > i)
-            byte = blob[(off[:V] + i).clamp(max=nb - 1)] if blob.numel() else torch.zeros(V, dtype=torch.int64)
-            s = torch.where(act, step(s, byte), s)
-        allowed = ok_len & (s != DFA_DEAD)
-        eos_ok = cur == DFA_DEAD or (cur < S and int(accept[r, cur]) != 0)
-        for e in eos_ids:
-            allowed[e] = eos_ok
-        logits[b, ~allowed.to(logits.device)] = float("-inf")
+def _dfa_tokens(V, tok_off, tok_blob, eos):
+    """(V, off, lens, blob, eos ids) of the CSR token byte table, on the host."""
+    off = tok_off.to(torch.int64).cpu()
+    lens = off[1:V + 1] - off[:V]
+    blob = tok_blob.cpu().to(torch.int64)
+    eos_ids = [int(e) for e in eos.reshape(-1).tolist() if 0 <= int(e) < V]
+    return V, off, lens, blob, eos_ids
+
+
+class _DfaRow:
+    """Table row r: ``step`` is one transition, vectorised over tokens; s == DEAD stays DEAD."""
+
+    def __init__(self, r, cls, trans, accept, g_dim):
+        self.r, self.accept = r, accept
+        self.S, self.C = int(g_dim[r, 0]), int(g_dim[r, 1])
+        self.SC = min(max(self.S * self.C, 0), DFA_MAX_TABLE)
+        self.tr = trans[r].cpu().to(torch.int64) & 0xFFFF
+        self.cl = cls[r].cpu().to(torch.int64)
+
+    def step(self, s, byte):
+        idx = s * self.C + self.cl[byte]
+        ok = (s != DFA_DEAD) & (idx < self.SC)
+        return torch.where(ok, self.tr[idx.clamp(0, DFA_MAX_TABLE - 1)], torch.full_like(s, DFA_DEAD))
+
+    def walk_token(self, tk, s, t):
+        """The state after token t's bytes from state s; DEAD for an id outside [0, V) or of 0 / more than 32 bytes."""
+        V, off, lens, blob, _ = tk
+        if not (0 <= t < V and 1 <= int(lens[t]) <= DFA_MAX_TOKEN_BYTES):
+            return DFA_DEAD
+        s = torch.tensor([int(s) & 0xFFFF])
+        for i in range(int(lens[t])):
+            s = self.step(s, blob[int(off[t]) + i].reshape(1))
+        return int(s)
+
+
+def _dfa_lazy_advance(tab, tk, g_state, g_base, n, t):
+    """cur after n generated tokens: slot n & 1 at the base, else the walk of token t from slot (n - 1) & 1, stored."""
+    r = tab.r
+    if n == int(g_base[r]) or n <= 0:
+        return int(g_state[r, n & 1]) & 0xFFFF
+    cur = tab.walk_token(tk, int(g_state[r, (n - 1) & 1]), t)
+    g_state[r, n & 1] = cur
+    return cur
+
+
+def _dfa_mask_row(row, tab, tk, cur):
+    """-inf into every logit of ``row`` [V] that the state ``cur`` rules out."""
+    V, off, lens, blob, eos_ids = tk
+    nb = max(1, blob.numel())
+    ok_len = (lens >= 1) & (lens <= DFA_MAX_TOKEN_BYTES)
+    s = torch.full((V,), cur, dtype=torch.int64)
+    for i in range(int(lens[ok_len].max()) if bool(ok_len.any()) else 0):
+        act = ok_len & (lens > i)
+        byte = blob[(off[:V] + i).clamp(max=nb - 1)] if blob.numel() else torch.zeros(V, dtype=torch.int64)
+        s = torch.where(act, tab.step(s, byte), s)
+    allowed = ok_len & (s != DFA_DEAD)
+    eos_ok = cur == DFA_DEAD or (cur < tab.S and int(tab.accept[tab.r, cur]) != 0)
+    for e in eos_ids:
+        allowed[e] = eos_ok
+    row[~allowed.to(row.device)] = float("-inf")
+
+
+def dfa_mask_verify(logits, tok_off, tok_blob, cls, trans, accept, g_dim, g_on, g_state, g_base, gen_len, input_ids,
+                    finished, eos, draft, g_spec, r=0):
+    """Host twin of dfa_mask_verify_kernel: ``logits`` [T, V] are the verify rows of the sequence in state row 0 (table
+    row r).  Nothing happens when ``g_on[r] == 0`` or ``finished[0]``.  s_0 is ``dfa_mask``'s lazily advanced state
+    (stored to slot n & 1 away from the base); s_t = walk(s_{t-1}, bytes(draft[t - 1])), DEAD -- and every later state
+    with it -- when the draft is -1, outside [0, V), of 0 or more than 32 bytes, or kills the walk.  Row t is masked as
+    ``dfa_mask`` masks a row in state s_t.  g_spec[0] = n = gen_len[0], g_spec[1 + t] = s_t."""
+    T, V = logits.shape
+    if int(g_on[r]) == 0 or int(finished[0]) != 0:
+        return
+    tk = _dfa_tokens(V, tok_off, tok_blob, eos)
+    tab = _DfaRow(r, cls, trans, accept, g_dim)
+    n = int(gen_len[0])
+    cur = _dfa_lazy_advance(tab, tk, g_state, g_base, n, int(input_ids[0]))
+    g_spec[0] = n
+    for t in range(T):
+        if t:
+            cur = tab.walk_token(tk, cur, int(draft[t - 1])) if cur != DFA_DEAD else DFA_DEAD
+        g_spec[1 + t] = cur
+        _dfa_mask_row(logits[t], tab, tk, cur)
+
+
+def dfa_spec_advance(g_on, g_state, g_spec, gen_len, k, r=0):
+    """Host twin of dfa_spec_advance_kernel (after ``spec_commit``): a = gen_len[0] - g_spec[0] - 1 accepted drafts;
+    with g_on[r] set and 0 <= a <= k, g_state[r, (gen_len[0] - 1) & 1] = g_spec[1 + a]."""
+    if int(g_on[r]) == 0:
+        return
+    n1 = int(gen_len[0])
+    a = n1 - int(g_spec[0]) - 1
+    if 0 <= a <= k:
+        g_state[r, (n1 - 1) & 1] = int(g_spec[1 + a]) & 0xFFFF
 
 
 # ----------------------------------------------------------------------------------- prefix cache

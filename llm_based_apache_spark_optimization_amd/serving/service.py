@@ -32,7 +32,8 @@ def engine_factory(settings: Settings, tp_factory=None):
                            max_new_cap=settings.max_new_cap or None,
                            kv_reserve_tokens=settings.kv_reserve_tokens, spec_tokens=settings.spec_tokens,
                            spec_quantized=settings.spec_quantized, prefix_cache=settings.prefix_cache,
-                           prefix_cow_min_tokens=settings.prefix_cow_min_tokens, guided=settings.guided)
+                           prefix_cow_min_tokens=settings.prefix_cow_min_tokens, guided=settings.guided,
+                           spec_guided=settings.spec_guided)
         if settings.spec_min_accept >= 0:
             eng.runner.spec_min_accept = settings.spec_min_accept
         return eng

@@ -13,9 +13,21 @@
            each.  The plain graph commits tokens the DFA never saw, so every guided run restarts the rows' lazy
            advance inside the statement, as a re-admission would.
 
+With --spec: speculative decoding of constrained requests (``spec_guided``) instead, appended to
+profiles/spec/spec_guided_mi355x.jsonl:
+
+  kernel   ops.dfa_mask_verify over the T verify rows (T = 2 / 4 / 8 at V = 32,000, T = 2 / 4 / 5 at V = 128,256) beside
+           the unchanged ops.dfa_mask at B = T on the same logits, every row in the state the verify row is in (the
+           baseline: the new kernel adds only the draft walk), for both patterns, with drafts the pattern allows.
+  step     one constrained request per model and k, planted drafts that the pattern allows (rows 1..k are masked in
+           live states; the random-init model accepts next to none, so every arm commits about one token per step):
+           the guided verify step against the unguided verify step (what the mask of T rows and the hand-over cost),
+           and against the plain guided step (what a constrained request pays today): the break-even accepted drafts
+           per step of a constrained request = guided verify / plain guided - 1.  16-step runs in a mirrored order.
+
 Appends JSON lines to profiles/guided/guided_mask_mi355x.jsonl (--out overrides).  Needs a GPU.
 
-  python scripts/bench_guided.py [--layers N] [--skip kernel,step] [--reps 5] [--out FILE]
+  python scripts/bench_guided.py [--spec] [--layers N] [--skip kernel,step] [--reps 5] [--out FILE]
 """
 from __future__ import annotations
 
@@ -34,11 +46,12 @@ sys.path.insert(0, ROOT)
 
 from llm_based_apache_spark_optimization_amd import ops, prompts  # noqa: E402
 from llm_based_apache_spark_optimization_amd.engine import LLMEngine, ModelRunner, SamplingParams  # noqa: E402
-from llm_based_apache_spark_optimization_amd.engine.guided import MAX_TABLE, compile_regex  # noqa: E402
+from llm_based_apache_spark_optimization_amd.engine.guided import DEAD, MAX_TABLE, compile_regex  # noqa: E402
 from llm_based_apache_spark_optimization_amd.models import get_spec  # noqa: E402
 from llm_based_apache_spark_optimization_amd.models.llama import init_random  # noqa: E402
 
 OUT = os.path.join(ROOT, "profiles", "guided", "guided_mask_mi355x.jsonl")
+OUT_SPEC = os.path.join(ROOT, "profiles", "spec", "spec_guided_mi355x.jsonl")
 LIMIT_PATTERN = r"(abcdefghijklmnopqrstuvwxyz01234){33}"  # 1024 states x 32 classes
 
 
@@ -179,20 +192,153 @@ def bench_step(dev, layers: int, reps: int) -> None:
         torch.cuda.empty_cache()
 
 
+def legal_drafts(dfa, state: int, off, blob, k: int) -> list:
+    """k token ids (of >= 4 bytes where one exists) that the pattern allows one after the other from ``state``."""
+    offs, data = off.tolist(), bytes(blob.tolist())
+    out = []
+    for i in range(k):
+        best = None
+        for t in range(259 + 97 * i, len(offs) - 1):  # past the specials and the single bytes, another word per draft
+            w = data[offs[t]:offs[t + 1]]
+            if 4 <= len(w) <= 32 and dfa.walk(state, w) != DEAD:
+                best = t
+                break
+        if best is None:  # a pattern that takes no word: the single byte it does take
+            best = next(t for t in range(3, 259) if dfa.walk(state, data[offs[t]:offs[t + 1]]) != DEAD)
+        out.append(best)
+        state = dfa.walk(state, data[offs[best]:offs[best + 1]])
+    return out
+
+
+def bench_spec_kernel(dev, reps: int) -> None:
+    sql = compile_regex(prompts.SQL_STATEMENT_REGEX)
+    lim = compile_regex(LIMIT_PATTERN)
+    pats = (("sql", sql, sql.walk(sql.start, b"SELECT ")), ("limit", lim, lim.walk(lim.start, b"abc")))
+    for V, Ts in ((32000, (2, 4, 8)), (128256, (2, 4, 5))):
+        off_h, blob_h = synthetic_vocab(V)
+        off, blob = off_h.to(dev), blob_h.to(dev)
+        i32 = dict(dtype=torch.int32, device=dev)
+        eos = torch.tensor([2], **i32)
+        for name, dfa, state in pats:
+            for T in Ts:
+                drafts = legal_drafts(dfa, state, off_h, blob_h, T - 1)
+                states = [state]
+                for t in drafts:
+                    states.append(dfa.walk(states[-1], bytes(blob_h[off_h[t]:off_h[t + 1]].tolist())))
+                assert DEAD not in states
+                cls, trans, accept, dim, on, gst, base = tables(dfa, T, dev, state)
+                gst.copy_(torch.tensor([[s, s] for s in states], **i32))  # row t of the baseline sits in state s_t
+                z = torch.zeros(T, **i32)
+                logits = torch.randn(T, V, device=dev)
+                wv, wm = logits.clone(), logits.clone()
+                dr, g_spec = torch.tensor(drafts, **i32), torch.zeros(9, **i32)
+                gst0 = torch.full((T, 2), state, **i32)
+                arms = {
+                    "dfa_mask_verify": lambda: ops.dfa_mask_verify(wv, off, blob, cls, trans, accept, dim, on, gst0, base,
+                                                                   z, z, z, eos, dr, g_spec),
+                    "dfa_mask_B_T": lambda: ops.dfa_mask(wm, off, blob, cls, trans, accept, dim, on, gst, base, z, z, z,
+                                                         eos),
+                }
+                us = {k: [] for k in arms}
+                for _ in range(reps):  # alternate the arms
+                    for k, fn in arms.items():
+                        us[k].append(time_graph(fn))
+                assert torch.equal(wv, wm) and g_spec[1:1 + T].tolist() == states  # the same mask, by both kernels
+                med = {k: round(statistics.median(v), 2) for k, v in us.items()}
+                emit(dict(bench="spec_kernel", V=V, T=T, pattern=name, states=dfa.n_states, classes=dfa.n_classes,
+                          draft_bytes=[int(off_h[t + 1] - off_h[t]) for t in drafts],
+                          tokens_alive_per_row=int(torch.isfinite(wv).sum()) // T, us=med,
+                          draft_walk_us=round(med["dfa_mask_verify"] - med["dfa_mask_B_T"], 2),
+                          ratio=round(med["dfa_mask_verify"] / med["dfa_mask_B_T"], 3)))
+
+
+def bench_spec_step(dev, layers: int, reps: int) -> None:
+    dfa = compile_regex(prompts.SQL_STATEMENT_REGEX)
+    inside = dfa.walk(dfa.start, b"SELECT ")
+    for base, plen, ks in (("duckdb-nsql", 128, (1, 3, 7)), ("llama3.2", 2048, (1, 3, 4))):
+        spec = get_spec(base)
+        if layers:
+            spec = dataclasses.replace(spec, n_layers=layers, name=f"{base}-{layers}l")
+        w = init_random(spec, dev, seed=5, kind="bf16")
+        new, run = 1024, 16
+        r = ModelRunner(w, max_slots=2, max_model_len=plen + new + 64, num_kv_blocks=(plen + new) // 64 + 4,
+                        spec_tokens=max(ks), spec_guided=True)
+        off_h, blob_h = synthetic_vocab(spec.vocab_size)
+        r.enable_guided(off_h, blob_h)
+        eng = LLMEngine(r, name=spec.name, kv_reserve_tokens=-1, guided=True)
+        g = torch.Generator().manual_seed(7)
+        ids = [1] + torch.randint(3, spec.vocab_size, (plen - 1,), generator=g).tolist()
+        ctx = plen + new
+        for k in ks:
+            r.spec_tokens = k
+            assert r.spec_k() == k, (k, r.spec_k())
+            r.set_spec_forced(torch.tensor([legal_drafts(dfa, inside, off_h, blob_h, k)], dtype=torch.int32))
+            eng.add_request(ids, SamplingParams(max_tokens=new, regex=prompts.SQL_STATEMENT_REGEX))
+            eng.step()  # prefill + one run of guided verify steps
+            assert eng.stats["spec_steps"] > 0
+
+            def rebase() -> None:
+                """The unguided arms commit tokens the DFA never saw: restart the lazy advance inside the statement."""
+                r.g_base[:1].copy_(r.gen_len[:1])
+                r.g_state[:1].fill_(inside)
+
+            def timed(arm: str) -> float:
+                if arm in ("guided_verify", "guided"):
+                    rebase()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                if arm.endswith("verify"):
+                    r.decode_spec(run, max_ctx=ctx, guided=arm == "guided_verify")
+                else:
+                    r.decode(1, run, False, max_ctx=ctx, guided=arm == "guided")
+                e1.record()
+                torch.cuda.synchronize()
+                return e0.elapsed_time(e1) / run
+
+            order = ("guided_verify", "verify", "guided", "plain")
+            for arm in order:
+                timed(arm)  # warms the four graphs
+            ms = {arm: [] for arm in order}
+            n0 = int(r.gen_len[0])
+            for _ in range(reps):  # mirrored: the context grows with every run, the order cancels it
+                for arm in order + order[::-1]:
+                    ms[arm].append(timed(arm))
+            steps = reps * 8 * run
+            m = {arm: statistics.mean(v) for arm, v in ms.items()}
+            emit(dict(bench="spec_step", model=spec.name, layers=spec.n_layers, prompt=plen, vocab=spec.vocab_size, k=k,
+                      T=k + 1, row_live_after=1 - int(r.finished[0]), steps=steps, tokens=int(r.gen_len[0]) - n0,
+                      plain_step_ms=round(m["plain"], 4), guided_step_ms=round(m["guided"], 4),
+                      verify_step_ms=round(m["verify"], 4), guided_verify_step_ms=round(m["guided_verify"], 4),
+                      mask_verify_cost_us=round((m["guided_verify"] - m["verify"]) * 1e3, 1),
+                      mask_plain_cost_us=round((m["guided"] - m["plain"]) * 1e3, 1),
+                      break_even_unconstrained=round(m["verify"] / m["plain"] - 1, 3),
+                      break_even_constrained=round(m["guided_verify"] / m["guided"] - 1, 3)))
+            eng.abort_all("bench over")
+        del eng, r, w
+        torch.cuda.empty_cache()
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--layers", type=int, default=0, help="truncate the models to this many layers (0 = full depth)")
     ap.add_argument("--skip", default="", help="comma list of kernel,step")
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--spec", action="store_true", help="measure spec_guided (verify-row mask, guided verify step)")
     ap.add_argument("--out", default="", help="JSON-lines file to append to")
     a = ap.parse_args()
     global OUT
-    OUT = a.out or OUT
+    OUT = a.out or (OUT_SPEC if a.spec else OUT)
     if not torch.cuda.is_available():
         raise SystemExit("bench_guided.py needs a GPU")
     ops.ext()
     dev = torch.device("cuda:0")
     skip = set(a.skip.split(",")) if a.skip else set()
+    if a.spec:
+        if "kernel" not in skip:
+            bench_spec_kernel(dev, a.reps)
+        if "step" not in skip:
+            bench_spec_step(dev, a.layers, a.reps)
+        return
     if "kernel" not in skip:
         bench_kernel(dev)
     if "step" not in skip:
