@@ -218,7 +218,7 @@ __global__ __launch_bounds__(1024) void sample_commit_kernel(const unsigned long
     // draw g of a request: the request's seed is the stream KEY (scrambled, so seeds 0, 1, 2, ... give unrelated
     // streams) and the draw index the counter; seeds[b] packs the key (low 40 bits) with a counter offset (high 24
     // bits: the tokens a preempted request already generated, so its re-admission continues the same stream
-    // whatever slot it lands in).  ops/reference.py draw_seed is the host twin.
+    // whatever slot it lands in).  ops/reference.py device_uniform is the exact host twin (sample_pick of the pick).
     const unsigned long long sv = seeds[b];
     const float u = uniform01(lsa_key_mix(sv & 0xFFFFFFFFFFull), (sv >> 40) + (unsigned long long)st.gen_len[b]);
     // first kept index whose cumulative mass exceeds u (fallback: last kept index)
@@ -305,18 +305,20 @@ extern "C" int lsa_sample_commit(float* logits, int B, int V, unsigned long long
                                  int* out_tokens, int max_new, int* gen_len, int* input_ids, int* positions,
                                  int* finished, const int* eos, int neos, const int* limit, const int* eos_on,
                                  hipStream_t s) {
+  const int nch2 = (V + LSA_CHUNK - 1) / LSA_CHUNK;
+  const int ncand = nch2 * LSA_TOPK;
+  int p2 = 64;
+  while (p2 < ncand) p2 <<= 1;
+  // V > 262144 unsupported (8192 candidates = 64 KiB of dynamic LDS); refused before anything is launched, so
+  // neither the logits (penalty) nor the workspace is touched
+  if (p2 > 8192) return -1;
   if (hist && window > 0 && penalty)
     hipLaunchKernelGGL(repeat_penalty_kernel, dim3(B), dim3(64), 0, s, logits, V, hist, window, penalty, last_n,
                        positions);
   const int chunk = 4096;
   const int nch = (V + chunk - 1) / chunk;
   hipLaunchKernelGGL(argmax_partial_kernel, dim3(nch, B), dim3(256), 0, s, logits, V, chunk, part, nch);
-  const int nch2 = (V + LSA_CHUNK - 1) / LSA_CHUNK;
   hipLaunchKernelGGL(topk_partial_kernel, dim3(nch2, B), dim3(256), 0, s, logits, V, cand, nch2);
-  const int ncand = nch2 * LSA_TOPK;
-  int p2 = 64;
-  while (p2 < ncand) p2 <<= 1;
-  if (p2 > 8192) return -1;  // V > 262144 unsupported
   DecodeState st{out_tokens, max_new, gen_len, input_ids, positions, finished, eos, neos, limit, eos_on,
                  window > 0 ? hist : nullptr, window};
   hipLaunchKernelGGL(sample_commit_kernel, dim3(B), dim3(1024), p2 * sizeof(unsigned long long), s, cand, p2, ncand,

@@ -300,7 +300,7 @@ class LLMEngine:
                     REGISTRY.inc("lsa_prefix_cached_tokens_total", hit, "prompt tokens served from the prefix cache",
                                  model=self.name)
                 # a re-admitted (preempted) request continues its random stream where it stopped: the sampler draws
-                # token g from the stream keyed by the seed at counter g + offset (ops/reference.py draw_seed,
+                # token g from the stream keyed by the seed at counter g + offset (ops/reference.py device_uniform,
                 # sampling.hip), and this incarnation's g restarts at 0 after len(resumed) tokens
                 seed = pack_seed(sp.seed if sp.seed is not None else (rid * 7919 + 17), len(req.resumed))
                 entries.append(dict(slot=slot, blocks=self.sched.block_table(rid), limit=sp.max_tokens,

@@ -451,11 +451,90 @@ def pack_seed(key: int, offset: int = 0) -> int:
 
 
 def draw_seed(packed: int, gen_len: int) -> int:
-    """Generator seed of draw gen_len of a request (the host twin of sampling.hip's keyed counter): the scrambled
-    key plus the counter, so nearby keys give unrelated streams and the offset continues a resumed stream."""
+    """Generator seed of draw gen_len of a request, for the CPU path's ``torch.multinomial`` draw: the scrambled
+    key plus the counter, so nearby keys give unrelated streams and the offset continues a resumed stream.  It has
+    the shape of sampling.hip's keyed counter but not its bits (it mixes once more and only seeds a generator);
+    the exact host twin of the device draw is ``device_uniform``."""
     packed &= _M64
     key, off = packed & ((1 << 40) - 1), packed >> 40
     return _mix64((_mix64(key) + 0x9E3779B97F4A7C15 * (off + gen_len + 1)) & _M64) & ((1 << 63) - 1)
+
+
+# --------------------------------------------------------------- exact host twin of sampling.hip's sampled draw
+_GOLDEN = 0x9E3779B97F4A7C15
+SAMPLE_TOPK_CAP = 64     # LSA_TOPK
+SAMPLE_MARGIN = 1e-4     # slack on u and top_p that covers the device's f32 arithmetic (see sample_pick_set)
+
+
+def device_uniform(packed_seed: int, gen_len: int) -> float:
+    """The uniform of draw ``gen_len`` of a request, bit for bit as sample_commit_kernel computes it:
+    ``uniform01(lsa_key_mix(sv & (2^40 - 1)), (sv >> 40) + gen_len)`` in 64-bit wrapping integers.  The result is
+    a multiple of 2^-24 in [0, 1)."""
+    sv = int(packed_seed) & _M64
+    # lsa_key_mix: the golden constant, then two multiply-xorshift rounds
+    z = ((sv & ((1 << 40) - 1)) + _GOLDEN) & _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    seed = z ^ (z >> 31)
+    # uniform01: golden * (counter + 1) onto the seed, then the two rounds with no further add
+    ctr = ((sv >> 40) + int(gen_len)) & _M64
+    z = (seed + _GOLDEN * (ctr + 1)) & _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    z ^= z >> 31
+    return (z >> 40) / 16777216.0
+
+
+def sample_candidates(row_f32: torch.Tensor, top_k: int):
+    """(values f32, indices) of the sampler's candidates in the device's order: descending value, equal values
+    lower index first (the packed key is ``float_key(v) << 32 | ~index``), cut at ``k = top_k if 0 < top_k <= 64
+    else 64`` (fewer when the row is shorter).  The per-chunk top-64 and the merge of sampling.hip select exactly
+    the first 64 of this order.
+
+    Two device conventions are NOT modelled, so keep both out of inputs: the device keys order +0.0 above -0.0
+    (torch compares them equal), and a NaN with the sign bit clear sorts above every number."""
+    row = row_f32.detach().float().cpu()
+    k = top_k if 0 < top_k <= SAMPLE_TOPK_CAP else SAMPLE_TOPK_CAP
+    vals, idx = torch.sort(row, stable=True, descending=True)
+    return vals[:k], idx[:k]
+
+
+def sample_pick(row: torch.Tensor, T: float, top_k: int, top_p: float, u: float) -> int:
+    """The token sample_commit_kernel commits for uniform ``u``, computed in float64:
+
+    * ``e_i = exp((l_i - l_0) / T)`` over the candidates of ``sample_candidates``, ``p = e / sum(e)``;
+    * candidate i is kept iff ``(i == 0 or mass before i < top_p) and e_i > 0`` -- the best token is always kept,
+      ``top_p <= 0`` keeps nothing else, a -inf logit is never kept;
+    * the kept mass is renormalised and the pick is the first kept i whose inclusive cumulative mass exceeds u
+      (``u < cum_i``); when no cumulative value exceeds u (rounding left the last one below u) it is the LAST
+      kept candidate -- a deliberate device convention, never a token outside the nucleus."""
+    return _pick(*sample_candidates(row, top_k), T, top_p, u)
+
+
+def _pick(vals, idx, T, top_p, u) -> int:
+    l = vals.double()
+    e = torch.exp((l - l[0]) / float(T))
+    p = e / e.sum()
+    before = torch.cumsum(p, 0) - p
+    keep = (before < float(top_p)) & (e > 0)
+    keep[0] = bool(e[0] > 0)
+    pk = torch.where(keep, p, torch.zeros_like(p))
+    cum = torch.cumsum(pk / pk.sum(), 0)
+    hit = torch.nonzero(keep & (cum > float(u)))
+    kept = torch.nonzero(keep)
+    if hit.numel():
+        return int(idx[int(hit[0])])
+    return int(idx[int(kept[-1])]) if kept.numel() else int(idx[0])
+
+
+def sample_pick_set(row: torch.Tensor, T: float, top_k: int, top_p: float, u: float, m: float = SAMPLE_MARGIN) -> set:
+    """Tokens the device may commit: ``sample_pick`` over u in {u - m, u, u + m} x top_p in {top_p - m, top_p,
+    top_p + m}.  The device evaluates the same quantities in f32 (``__expf``, shuffle prefix sums); over <= 64
+    candidates the absolute error of any cumulative boundary stays below about 1e-5 (per-term relative error about
+    (|x| + 4) * 2^-23 weighted by p, six levels of prefix rounding, two normalisations), so m = 1e-4 is more than
+    ten times the bound.  A draw is DECIDED when the set has one element: the device must then commit it."""
+    vals, idx = sample_candidates(row, top_k)
+    return {_pick(vals, idx, T, tp, uu) for uu in (u - m, u, u + m) for tp in (top_p - m, top_p, top_p + m)}
 
 
 def sample_commit(logits, hist, penalty, temperature, top_k, top_p, seeds, out_tokens, gen_len, input_ids,
