@@ -81,6 +81,12 @@ int lsa_sample_commit(float* logits, int B, int V, unsigned long long* part, uns
                       const float* top_p, const unsigned long long* seeds, int* out_tokens, int max_new, int* gen_len,
                       int* input_ids, int* positions, int* finished, const int* eos, int neos, const int* limit,
                       const int* eos_on, hipStream_t s);
+int lsa_spec_sample_commit(float* logits, int T, int V, const int* draft, long long* stats, int* hist, int window,
+                           const float* penalty, const int* last_n, const float* temperature, const int* top_k,
+                           const float* top_p, const unsigned long long* seeds, int* out_tokens, int max_new,
+                           int* gen_len, int* input_ids, int* positions, int* finished, const int* eos, int neos,
+                           const int* limit, const int* eos_on, unsigned long long* part, unsigned long long* cand,
+                           int* picks, hipStream_t s);
 int lsa_fp8_gemm(const void* X, int ldx, int M, int K, const void* Wq, const float* wscale, int N, void* out, int epi,
                  int nb, int splitk, hipStream_t stream);
 int lsa_fp8_dequant(const void* Wq, const float* wscale, int N, int K, void* Wf, hipStream_t s);
@@ -1140,6 +1146,61 @@ void sample_commit(at::Tensor& logits, at::Tensor& part, at::Tensor& cand, const
         "sample_commit");
 }
 
+// speculative decoding of a sampled request: penalty + sampled (or, temperature <= 0, argmax) pick of each of the T
+// verify rows at draw counter gen_len[0] + row, then the in-order commit of the accepted run into state row 0 (ring
+// included).  The per-row parameters are row 0's.  picks int32 [T] receives the rows' tokens.
+void spec_sample_commit(at::Tensor& logits, const at::Tensor& draft, at::Tensor& stats,
+                        const c10::optional<at::Tensor>& hist, const c10::optional<at::Tensor>& penalty,
+                        const c10::optional<at::Tensor>& last_n, const at::Tensor& temperature, const at::Tensor& top_k,
+                        const at::Tensor& top_p, const at::Tensor& seeds, at::Tensor& out_tokens, at::Tensor& gen_len,
+                        at::Tensor& input_ids, at::Tensor& positions, at::Tensor& finished, const at::Tensor& eos,
+                        const at::Tensor& limit, const at::Tensor& eos_on, at::Tensor& part, at::Tensor& cand,
+                        at::Tensor& picks) {
+  need(logits, at::kFloat, "logits");
+  TORCH_CHECK(logits.dim() == 2 && logits.is_contiguous() && logits.size(0) >= 2 && logits.size(0) <= 8 &&
+                  logits.size(1) >= 1 && logits.numel() < 0x7fffffffLL, "logits: contiguous [2 <= T <= 8, V >= 1]");
+  const int T = logits.size(0), V = logits.size(1);
+  check_state(1, out_tokens, gen_len, input_ids, positions, finished, eos, limit, eos_on);
+  need(part, at::kLong, "part");
+  need(cand, at::kLong, "cand");
+  need(picks, at::kInt, "picks");
+  TORCH_CHECK(part.numel() >= (int64_t)T * ((V + 4095) / 4096) && cand.numel() >= (int64_t)T * ((V + 2047) / 2048) * 64 &&
+                  picks.numel() >= T && part.is_contiguous() && cand.is_contiguous() && picks.is_contiguous(),
+              "spec_sample_commit workspace too small");
+  need(draft, at::kInt, "draft");
+  need(stats, at::kLong, "stats");
+  TORCH_CHECK(draft.numel() >= T - 1 && draft.is_contiguous() && stats.numel() >= 3 && stats.is_contiguous(),
+              "spec_sample_commit: draft [T - 1], stats [3]");
+  need(temperature, at::kFloat, "temperature");
+  need(top_p, at::kFloat, "top_p");
+  need(top_k, at::kInt, "top_k");
+  need(seeds, at::kLong, "seeds");
+  TORCH_CHECK(temperature.numel() >= 1 && top_p.numel() >= 1 && top_k.numel() >= 1 && seeds.numel() >= 1,
+              "sampling parameters: row 0");
+  if (hist.has_value()) {
+    need(*hist, at::kInt, "hist");
+    TORCH_CHECK(hist->dim() == 2 && hist->size(0) >= 1 && hist->size(1) >= 1 && hist->is_contiguous(), "hist [1, W]");
+    TORCH_CHECK(penalty.has_value() && penalty->numel() >= 1, "repetition penalty: row 0");
+    need(*penalty, at::kFloat, "penalty");
+  }
+  if (last_n.has_value()) {
+    need(*last_n, at::kInt, "last_n");
+    TORCH_CHECK(last_n->numel() >= 1, "last_n: row 0");
+  }
+  const int window = hist.has_value() ? hist->size(1) : 0;
+  check(lsa_spec_sample_commit(logits.data_ptr<float>(), T, V, draft.data_ptr<int>(),
+                               reinterpret_cast<long long*>(stats.data_ptr<int64_t>()), ptr<int>(hist), window,
+                               ptr<const float>(penalty), ptr<const int>(last_n), temperature.data_ptr<float>(),
+                               top_k.data_ptr<int>(), top_p.data_ptr<float>(),
+                               reinterpret_cast<const unsigned long long*>(seeds.data_ptr()), out_tokens.data_ptr<int>(),
+                               out_tokens.size(1), gen_len.data_ptr<int>(), input_ids.data_ptr<int>(),
+                               positions.data_ptr<int>(), finished.data_ptr<int>(), eos.data_ptr<int>(), eos.numel(),
+                               limit.data_ptr<int>(), eos_on.data_ptr<int>(),
+                               reinterpret_cast<unsigned long long*>(part.data_ptr()),
+                               reinterpret_cast<unsigned long long*>(cand.data_ptr()), picks.data_ptr<int>(), cur_stream()),
+        "spec_sample_commit");
+}
+
 // per-token fp8 quantisation of bf16 rows: x8 [M, K] uint8 (e4m3fn bits), sx [M] f32 (amax / 448)
 void quant_rows_fp8(const at::Tensor& x, at::Tensor& x8, at::Tensor& sx) {
   need(x, at::kBFloat16, "x");
@@ -1337,6 +1398,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("gen_len"), py::arg("input_ids"), py::arg("positions"), py::arg("k"), py::arg("n_max"), py::arg("n_min"),
         py::arg("forced"), py::arg("spec_ids"), py::arg("spec_pos"), py::arg("spec_draft"));
   m.def("spec_commit", &spec_commit);
+  m.def("spec_sample_commit", &spec_sample_commit);
   m.def("dfa_mask", &dfa_mask, py::arg("logits"), py::arg("tok_off"), py::arg("tok_blob"), py::arg("cls"),
         py::arg("trans"), py::arg("accept"), py::arg("g_dim"), py::arg("g_on"), py::arg("g_state"), py::arg("g_base"),
         py::arg("rows"), py::arg("gen_len"), py::arg("input_ids"), py::arg("finished"), py::arg("eos"));

@@ -9,6 +9,8 @@
 //                        finished on EOS / length.  A finished row keeps its position (its KV slot is
 //                        re-written, never a new block), so a replayed graph can never walk past the
 //                        blocks reserved for it.
+//   lsa_spec_commit / lsa_spec_sample_commit   the verify rows of a speculative-decoding step: greedy / sampled
+//                        (penalty, draw) pick per row and the in-order commit of the accepted run (see below)
 #include "common.h"
 
 #define LSA_TOPK 64
@@ -161,6 +163,69 @@ __device__ __forceinline__ float uniform01(unsigned long long seed, unsigned lon
   return (float)(z >> 40) * (1.0f / 16777216.0f);
 }
 
+// the greedy pick of one row: the first wave reduces the row's argmax partials (the token on every lane of it)
+__device__ __forceinline__ int argmax_pick(const unsigned long long* __restrict__ part_row, int nch) {
+  unsigned long long best = 0ull;
+  for (int i = threadIdx.x; i < nch; i += 64) {
+    const unsigned long long k = part_row[i];
+    best = k > best ? k : best;
+  }
+  best = wave_max_u64(best);
+  return (int)(0xffffffffu - (uint32_t)(best & 0xffffffffull));
+}
+
+// THE sampler: the sampled pick of one row by its whole block (a: ncand_pow2 keys of dynamic LDS) -- merge the row's
+// candidates, softmax(T), top-k / top-p, inverse-CDF pick at draw counter `ctr` of the seed word `sv`.  The token is
+// returned on the first wave (-1 on the others).  sample_commit_kernel and spec_sample_pick_kernel both call it.
+__device__ int sample_pick(unsigned long long* a, const unsigned long long* __restrict__ cand_row, int ncand_pow2,
+                           int ncand, float T, int k, float tp, unsigned long long sv, unsigned long long ctr) {
+  for (int i = threadIdx.x; i < ncand_pow2; i += blockDim.x) a[i] = i < ncand ? cand_row[i] : 0ull;
+  __syncthreads();
+  bitonic_desc(a, ncand_pow2);
+  if (threadIdx.x >= 64) return -1;
+  if (k <= 0 || k > LSA_TOPK) k = LSA_TOPK;
+  const int i = threadIdx.x;
+  const uint32_t* a32 = reinterpret_cast<const uint32_t*>(a);
+  const float lmax = key_float(a32[1]);
+  const float li = key_float(a32[2 * i + 1]);
+  float e = (i < k && a[i] != 0ull) ? __expf((li - lmax) / T) : 0.f;
+  const float tot = wave_sum(e);
+  float p = e / tot;
+  // inclusive prefix sum over the (sorted) probabilities
+  float cum = p;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const float x = __shfl_up(cum, o, 64);
+    if (i >= o) cum += x;
+  }
+  // keep token i if the mass before it is < top_p (always keeps the first)
+  const bool keep = (i < k) && (i == 0 || (cum - p) < tp) && e > 0.f;
+  const float pk = keep ? p : 0.f;
+  const float ktot = wave_sum(pk);
+  const float pn = pk / ktot;
+  float cumk = pn;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const float x = __shfl_up(cumk, o, 64);
+    if (i >= o) cumk += x;
+  }
+  // draw g of a request: the request's seed is the stream KEY (scrambled, so seeds 0, 1, 2, ... give unrelated
+  // streams) and the draw index the counter; the seed word packs the key (low 40 bits) with a counter offset (high 24
+  // bits: the tokens a preempted request already generated, so its re-admission continues the same stream
+  // whatever slot it lands in).  ops/reference.py device_uniform is the exact host twin (sample_pick of the pick).
+  const float u = uniform01(lsa_key_mix(sv & 0xFFFFFFFFFFull), (sv >> 40) + ctr);
+  // first kept index whose cumulative mass exceeds u (fallback: last kept index)
+  int first_hit = (keep && u < cumk) ? i : 64;
+  int last_kept = keep ? i : -1;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    first_hit = min(first_hit, __shfl_xor(first_hit, o, 64));
+    last_kept = max(last_kept, __shfl_xor(last_kept, o, 64));
+  }
+  const int pick = first_hit < 64 ? first_hit : (last_kept >= 0 ? last_kept : 0);
+  return (int)(0xffffffffu - (uint32_t)(a[pick] & 0xffffffffull));
+}
+
 // stage 2: one block per row — merge candidates, softmax(T), top-k/top-p, draw, commit
 __global__ __launch_bounds__(1024) void sample_commit_kernel(const unsigned long long* __restrict__ cand, int ncand_pow2,
                                                              int ncand, const unsigned long long* __restrict__ amax_part,
@@ -173,68 +238,16 @@ __global__ __launch_bounds__(1024) void sample_commit_kernel(const unsigned long
   const float T = temperature[b];
   if (T <= 0.f) {  // greedy row inside a sampled batch
     if (threadIdx.x < 64) {
-      unsigned long long best = 0ull;
-      for (int i = threadIdx.x; i < nch_amax; i += 64) {
-        const unsigned long long k = amax_part[(size_t)b * nch_amax + i];
-        best = k > best ? k : best;
-      }
-      best = wave_max_u64(best);
-      if (threadIdx.x == 0) commit_token(st, b, (int)(0xffffffffu - (uint32_t)(best & 0xffffffffull)));
+      const int tok = argmax_pick(amax_part + (size_t)b * nch_amax, nch_amax);
+      if (threadIdx.x == 0) commit_token(st, b, tok);
     }
     return;
   }
-  for (int i = threadIdx.x; i < ncand_pow2; i += blockDim.x) a[i] = i < ncand ? cand[(size_t)b * ncand + i] : 0ull;
-  __syncthreads();
-  bitonic_desc(a, ncand_pow2);
-  if (threadIdx.x < 64) {
-    int k = top_k[b];
-    if (k <= 0 || k > LSA_TOPK) k = LSA_TOPK;
-    const int i = threadIdx.x;
-    const uint32_t* a32 = reinterpret_cast<const uint32_t*>(a);
-    const float lmax = key_float(a32[1]);
-    const float li = key_float(a32[2 * i + 1]);
-    float e = (i < k && a[i] != 0ull) ? __expf((li - lmax) / T) : 0.f;
-    const float tot = wave_sum(e);
-    float p = e / tot;
-    // inclusive prefix sum over the (sorted) probabilities
-    float cum = p;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const float x = __shfl_up(cum, o, 64);
-      if (i >= o) cum += x;
-    }
-    const float tp = top_p[b];
-    // keep token i if the mass before it is < top_p (always keeps the first)
-    const bool keep = (i < k) && (i == 0 || (cum - p) < tp) && e > 0.f;
-    const float pk = keep ? p : 0.f;
-    const float ktot = wave_sum(pk);
-    const float pn = pk / ktot;
-    float cumk = pn;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const float x = __shfl_up(cumk, o, 64);
-      if (i >= o) cumk += x;
-    }
-    // draw g of a request: the request's seed is the stream KEY (scrambled, so seeds 0, 1, 2, ... give unrelated
-    // streams) and the draw index the counter; seeds[b] packs the key (low 40 bits) with a counter offset (high 24
-    // bits: the tokens a preempted request already generated, so its re-admission continues the same stream
-    // whatever slot it lands in).  ops/reference.py device_uniform is the exact host twin (sample_pick of the pick).
-    const unsigned long long sv = seeds[b];
-    const float u = uniform01(lsa_key_mix(sv & 0xFFFFFFFFFFull), (sv >> 40) + (unsigned long long)st.gen_len[b]);
-    // first kept index whose cumulative mass exceeds u (fallback: last kept index)
-    int first_hit = (keep && u < cumk) ? i : 64;
-    int last_kept = keep ? i : -1;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      first_hit = min(first_hit, __shfl_xor(first_hit, o, 64));
-      last_kept = max(last_kept, __shfl_xor(last_kept, o, 64));
-    }
-    const int pick = first_hit < 64 ? first_hit : (last_kept >= 0 ? last_kept : 0);
-    if (i == 0) {
-      const int tok = (int)(0xffffffffu - (uint32_t)(a[pick] & 0xffffffffull));
-      commit_token(st, b, tok);
-    }
-  }
+  // the draw counter, read by every thread before the pick's first barrier: thread 0 commits (and advances it) after
+  const int g = st.gen_len[b];
+  const int tok = sample_pick(a, cand + (size_t)b * ncand, ncand_pow2, ncand, T, top_k[b], top_p[b], seeds[b],
+                              (unsigned long long)g);
+  if (threadIdx.x == 0) commit_token(st, b, tok);
 }
 
 extern "C" int lsa_argmax_commit(const float* logits, int B, int V, unsigned long long* part, int* out_tokens,
@@ -294,6 +307,125 @@ extern "C" int lsa_spec_commit(const float* logits, int T, int V, unsigned long 
   hipLaunchKernelGGL(argmax_partial_kernel, dim3(nch, T), dim3(256), 0, s, logits, V, chunk, part, nch);
   DecodeState st{out_tokens, max_new, gen_len, input_ids, positions, finished, eos, neos, limit, eos_on, nullptr, 0};
   hipLaunchKernelGGL(spec_commit_kernel, dim3(1), dim3(64), 0, s, part, nch, T - 1, draft, stats, st);
+  return (int)hipGetLastError();
+}
+
+// ---------------------------------------------------------------- speculative decoding of a sampled request
+// lsa_spec_sample_commit: logits [T, V] are the T = k + 1 verify rows of ONE sequence (state row 0), p = positions[0]
+// and n = gen_len[0] at the launch.  Verify row i makes the very draw the plain step would make for generated token
+// n + i -- penalised over the ring as it would stand had drafts 0 .. i-1 been committed, drawn at counter n + i -- and
+// a draft is accepted exactly when it equals that draw, so the committed sequence is the plain sampled sequence of the
+// same seed.  Four launches after the partials: penalty (grid T) -> argmax / top-k partials (B = T) -> pick (grid T,
+// picks[i]) -> in-order commit (one wave).  No workgroup reads a word another workgroup of its launch writes.
+
+// Repetition penalty of verify row i, in place, with repeat_penalty_kernel's rule over the tokens at context positions
+// (p + i - m, p + i], m = min(last_n, window, p + i + 1): the token at position p + j, 1 <= j <= i, is draft[j - 1];
+// the token at a position <= p is hist[pos % window].  (A ring slot whose position is > p still holds the token
+// `window` positions older; m <= window, so no such slot is ever read for it.)  A draft < 0 or >= V penalises nothing.
+__global__ __launch_bounds__(64) void spec_repeat_penalty_kernel(float* __restrict__ logits, int V,
+                                                                 const int* __restrict__ hist, int window,
+                                                                 const float* __restrict__ penalty,
+                                                                 const int* __restrict__ last_n,
+                                                                 const int* __restrict__ positions,
+                                                                 const int* __restrict__ draft) {
+  const int row = blockIdx.x;
+  const float pen = penalty[0];
+  if (pen == 1.0f) return;
+  const int p = positions[0];
+  const int P = p + row;
+  const int n = min(min(last_n ? last_n[0] : window, window), P + 1);
+  auto tok_at = [&](int pos) { return pos > p ? draft[pos - p - 1] : hist[pos % window]; };
+  for (int i = threadIdx.x; i < n; i += 64) {
+    const int t = tok_at(P - i);
+    if (t < 0 || t >= V) continue;
+    bool first = true;  // the most recent occurrence applies the penalty, once per distinct token
+    for (int k = 0; k < i; ++k) first &= (tok_at(P - k) != t);
+    if (!first) continue;
+    float* q = logits + (size_t)row * V + t;
+    const float v = *q;
+    *q = v > 0.f ? v / pen : v * pen;
+  }
+}
+
+// per verify row: the token the plain step would commit for generated token n + row (the sampler of
+// sample_commit_kernel at draw counter n + row; temperature <= 0: the row's argmax) -> picks[row]
+__global__ __launch_bounds__(1024) void spec_sample_pick_kernel(const unsigned long long* __restrict__ cand,
+                                                                int ncand_pow2, int ncand,
+                                                                const unsigned long long* __restrict__ amax_part,
+                                                                int nch_amax, const float* __restrict__ temperature,
+                                                                const int* __restrict__ top_k,
+                                                                const float* __restrict__ top_p,
+                                                                const unsigned long long* __restrict__ seeds,
+                                                                const int* __restrict__ gen_len, int* __restrict__ picks) {
+  extern __shared__ unsigned long long a[];
+  const int row = blockIdx.x;
+  const float T = temperature[0];
+  if (T <= 0.f) {  // greedy with a repetition penalty
+    if (threadIdx.x < 64) {
+      const int tok = argmax_pick(amax_part + (size_t)row * nch_amax, nch_amax);
+      if (threadIdx.x == 0) picks[row] = tok;
+    }
+    return;
+  }
+  const int tok = sample_pick(a, cand + (size_t)row * ncand, ncand_pow2, ncand, T, top_k[0], top_p[0], seeds[0],
+                              (unsigned long long)(gen_len[0] + row));
+  if (threadIdx.x == 0) picks[row] = tok;
+}
+
+// one wave: a = the number of leading i < k with draft[i] >= 0 && draft[i] == picks[i]; picks[0 .. a] are committed in
+// order through commit_token (ring included), so nothing follows a finishing token; stats as spec_commit_kernel
+__global__ __launch_bounds__(64) void spec_sample_commit_kernel(const int* __restrict__ picks, int k,
+                                                                const int* __restrict__ draft,
+                                                                long long* __restrict__ stats, DecodeState st) {
+  if (threadIdx.x != 0) return;
+  const bool live = !st.finished[0];
+  bool run = true;  // picks[0 .. i-1] matched their drafts
+  int committed = 0, drafted = 0;
+  for (int i = 0; i <= k; ++i) {
+    const int tok = picks[i];
+    if (run && live && !st.finished[0]) {
+      commit_token(st, 0, tok);
+      ++committed;
+    }
+    if (i < k) {
+      const int d = draft[i];
+      drafted += d >= 0;
+      run = run && d >= 0 && d == tok;
+    }
+  }
+  if (live) {
+    stats[0] += 1;
+    stats[1] += drafted;
+    stats[2] += committed > 0 ? committed - 1 : 0;
+  }
+}
+
+// workspace: part (T * ceil(V/4096) u64) + cand (T * ceil(V/2048) * 64 u64) + picks (T int)
+extern "C" int lsa_spec_sample_commit(float* logits, int T, int V, const int* draft, long long* stats, int* hist,
+                                      int window, const float* penalty, const int* last_n, const float* temperature,
+                                      const int* top_k, const float* top_p, const unsigned long long* seeds,
+                                      int* out_tokens, int max_new, int* gen_len, int* input_ids, int* positions,
+                                      int* finished, const int* eos, int neos, const int* limit, const int* eos_on,
+                                      unsigned long long* part, unsigned long long* cand, int* picks, hipStream_t s) {
+  // sizes refused before anything is launched or written: 2 <= T <= 8 verify rows, V <= 262144 (lsa_sample_commit)
+  if (T < 2 || T > 8 || V < 1) return -1;
+  const int nch2 = (V + LSA_CHUNK - 1) / LSA_CHUNK;
+  const int ncand = nch2 * LSA_TOPK;
+  int p2 = 64;
+  while (p2 < ncand) p2 <<= 1;
+  if (p2 > 8192) return -1;
+  if (hist && window > 0 && penalty)
+    hipLaunchKernelGGL(spec_repeat_penalty_kernel, dim3(T), dim3(64), 0, s, logits, V, hist, window, penalty, last_n,
+                       positions, draft);
+  const int chunk = 4096;
+  const int nch = (V + chunk - 1) / chunk;
+  hipLaunchKernelGGL(argmax_partial_kernel, dim3(nch, T), dim3(256), 0, s, logits, V, chunk, part, nch);
+  hipLaunchKernelGGL(topk_partial_kernel, dim3(nch2, T), dim3(256), 0, s, logits, V, cand, nch2);
+  hipLaunchKernelGGL(spec_sample_pick_kernel, dim3(T), dim3(1024), p2 * sizeof(unsigned long long), s, cand, p2, ncand,
+                     part, nch, temperature, top_k, top_p, seeds, gen_len, picks);
+  DecodeState st{out_tokens, max_new, gen_len, input_ids, positions, finished, eos, neos, limit, eos_on,
+                 window > 0 ? hist : nullptr, window};
+  hipLaunchKernelGGL(spec_sample_commit_kernel, dim3(1), dim3(64), 0, s, picks, T - 1, draft, stats, st);
   return (int)hipGetLastError();
 }
 

@@ -221,6 +221,17 @@ int main() {
     auto seeds32 = T({B}, I32);
     expect_reject("sample_commit seeds dtype", [&] { sample_commit(lg, part, cand, hist, pen, lastn, temp, topk, topp, seeds32, ot, gl, ii, ps, fin, eos, lim, eon); });
     expect_reject("sample_commit penalty missing", [&] { sample_commit(lg, part, cand, hist, none, lastn, temp, topk, topp, seeds, ot, gl, ii, ps, fin, eos, lim, eon); });
+    // sampled verify commit: the B rows are the T verify rows of state row 0
+    auto draft = T({B - 1}, I32), stats = T({3}, I64), picks = T({B}, I32);
+    expect_ok("spec_sample_commit", [&] { spec_sample_commit(lg, draft, stats, hist, pen, lastn, temp, topk, topp, seeds, ot, gl, ii, ps, fin, eos, lim, eon, part, cand, picks); });
+    auto lg1 = T({1, V}, F32), lg9 = T({9, V}, F32), part9 = T({9 * 2}, I64), cand9 = T({9 * 3 * 64}, I64), picks9 = T({9}, I32), draft8 = T({8}, I32);
+    expect_reject("spec_sample_commit T = 1", [&] { spec_sample_commit(lg1, draft, stats, hist, pen, lastn, temp, topk, topp, seeds, ot, gl, ii, ps, fin, eos, lim, eon, part, cand, picks); });
+    expect_reject("spec_sample_commit T = 9", [&] { spec_sample_commit(lg9, draft8, stats, hist, pen, lastn, temp, topk, topp, seeds, ot, gl, ii, ps, fin, eos, lim, eon, part9, cand9, picks9); });
+    auto picks_small = T({B - 1}, I32), draft_small = T({B - 2}, I32);
+    expect_reject("spec_sample_commit picks", [&] { spec_sample_commit(lg, draft, stats, hist, pen, lastn, temp, topk, topp, seeds, ot, gl, ii, ps, fin, eos, lim, eon, part, cand, picks_small); });
+    expect_reject("spec_sample_commit draft", [&] { spec_sample_commit(lg, draft_small, stats, hist, pen, lastn, temp, topk, topp, seeds, ot, gl, ii, ps, fin, eos, lim, eon, part, cand, picks); });
+    expect_reject("spec_sample_commit seeds dtype", [&] { spec_sample_commit(lg, draft, stats, hist, pen, lastn, temp, topk, topp, seeds32, ot, gl, ii, ps, fin, eos, lim, eon, part, cand, picks); });
+    expect_reject("spec_sample_commit penalty missing", [&] { spec_sample_commit(lg, draft, stats, hist, none, lastn, temp, topk, topp, seeds, ot, gl, ii, ps, fin, eos, lim, eon, part, cand, picks); });
   }
   // ---- one-shot all-reduce
   {

@@ -71,6 +71,10 @@ class Settings:
     # constrained requests speculate too (off: a request with a regex takes plain guided steps whatever spec_tokens
     # says).  Needs guided and spec_tokens; the tokens are those of the plain guided steps
     spec_guided: bool = dataclasses.field(default_factory=lambda: _env("SPEC_GUIDED", False, bool))
+    # requests that need the sampler speculate too (off: a request with temperature > 0 or a repetition penalty takes
+    # plain steps whatever spec_tokens says).  Needs spec_tokens; verify row i makes the plain step's draw for its
+    # token, so the tokens are those of the plain sampled steps of the same seed
+    spec_sampled: bool = dataclasses.field(default_factory=lambda: _env("SPEC_SAMPLED", False, bool))
     tp: int = dataclasses.field(default_factory=lambda: _env("TP", 1, int))
     dp: int = dataclasses.field(default_factory=lambda: _env("DP", 1, int))
     max_batch: int = dataclasses.field(default_factory=lambda: _env("MAX_BATCH", 32, int))

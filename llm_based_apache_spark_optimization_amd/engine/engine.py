@@ -55,8 +55,10 @@ class SamplingParams:
     repeat_last_n: int = 64
     num_ctx: Optional[int] = None     # Ollama context window (prompt + generated tokens); None = model's
     num_keep: int = 4
-    # prompt-lookup speculative decoding, where the engine runs it (LLMEngine(spec_tokens > 0), greedy, batch 1);
-    # the Ollama option extension "speculate": false opts a request out.  The tokens are the same either way.
+    # prompt-lookup speculative decoding, where the engine runs it (LLMEngine(spec_tokens > 0), batch 1: a greedy
+    # request, and -- on an engine built with spec_sampled (LSA_SPEC_SAMPLED=1) -- one with temperature > 0 and / or a
+    # repetition penalty, whose verify rows make the plain steps' draws of the same seed); the Ollama option extension
+    # "speculate": false opts a request out.  The tokens are the same either way.
     speculate: bool = True
     # prefix cache, where the engine runs it (LLMEngine(prefix_cache=True)): llama.cpp's "cache_prompt": false opts a
     # request out -- it neither reuses cached KV blocks nor publishes its own
@@ -367,7 +369,9 @@ class LLMEngine:
                 ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
                 ev[0].record()
             if spec_T:
-                if guided:  # spec_guided: the verify graph with the mask of the T verify rows
+                if sample:  # spec_sampled: the verify graph that ends in the sampled commit (masked too, if guided)
+                    r.decode_spec(n_steps, max_ctx=max_ctx, guided=guided, sample=True)
+                elif guided:  # spec_guided: the verify graph with the mask of the T verify rows
                     r.decode_spec(n_steps, max_ctx=max_ctx, guided=True)
                 else:
                     r.decode_spec(n_steps, max_ctx=max_ctx)
@@ -458,8 +462,8 @@ class LLMEngine:
     def _spec_run(self, reqs: list, n_steps: int, remaining: int) -> int:
         """Whether this decode run is a run of verify steps (speculative decoding): returns T = drafted tokens + 1, or
         0 for the plain run.  Verify steps need the runner's support (``ModelRunner.spec_supported``), exactly one
-        running request, greedy, in slot 0 (decode bucket 1), that has not opted out or been dropped by the acceptance
-        guard; room for every position the run may write inside the model window; and the KV blocks of those
+        running request, greedy (or, ``spec_sampled``, one that needs the sampler), in slot 0 (decode bucket 1), that
+        has not opted out or been dropped by the acceptance guard; room for every position the run may write inside the model window; and the KV blocks of those
         positions without preempting anyone: the worst case is T committed tokens per step plus T - 1 rows of
         lookahead (also reserved so that a finished row, which rewrites its last T positions while the graph replays,
         stays in its own blocks)."""
@@ -468,9 +472,10 @@ class LLMEngine:
             return 0
         q = reqs[0]
         sp = q.params
-        if (q.slot != 0 or self.sched.highest_slot != 0 or self.sched.num_running != 1 or sp.needs_sampler
-                or not sp.speculate or q.spec_off):
+        if q.slot != 0 or self.sched.highest_slot != 0 or self.sched.num_running != 1 or not sp.speculate or q.spec_off:
             return 0
+        if sp.needs_sampler and not getattr(r, "spec_sampled", False):
+            return 0  # a request that needs the sampler speculates only with the opt-in (the sampled verify graph)
         if q.dfa is not None and not (getattr(r, "spec_guided", False) and getattr(r, "guided", False)):
             return 0  # a constrained request speculates only with the opt-in (the guided verify graph)
         T = r.spec_k() + 1

@@ -48,7 +48,7 @@ class ModelRunner:
                  max_new_cap: Optional[int] = None, tp=None, use_graphs: bool = True,
                  fuse_rope: Optional[bool] = None, seq_parallel: Optional[bool] = None, sp_min_tokens: Optional[int] = None,
                  kv_dtype: Optional[str] = None, spec_tokens: int = 0, spec_ngram: tuple = (3, 1),
-                 spec_quantized: bool = False, spec_guided: bool = False):
+                 spec_quantized: bool = False, spec_guided: bool = False, spec_sampled: bool = False):
         self.w = weights
         # prompt-lookup speculative decoding (``_verify_step``): tokens drafted per step (0 = off) and the drafter's
         # (longest, shortest) n-gram.  Plain attributes: an experiment may set them on a built runner.
@@ -60,6 +60,10 @@ class ModelRunner:
         # opt-in: verify steps for regex-constrained requests too (``_verify_step(guided=True)``: the mask of the T
         # verify rows and the DFA state's hand-over inside the verify graph).  Inert without ``enable_guided``.
         self.spec_guided = bool(spec_guided)
+        # opt-in: verify steps for requests that need the sampler too (temperature > 0 and / or a repetition penalty;
+        # ``_verify_step(sample=True)``: verify row i makes the plain step's draw for generated token n + i, so the
+        # tokens are those of the plain sampled steps of the same seed)
+        self.spec_sampled = bool(spec_sampled)
         # acceptance guard of the engine: a request whose accepted-per-verify-step mean falls below this after 16
         # verify steps takes plain steps for the rest of its life.  Break-even = verify-step time / plain-step time - 1.
         # Measured on MI355X (scripts/bench_spec.py, profiles/spec/spec_decode_mi355x.jsonl; plain vs verify step, k = 3):
@@ -778,6 +782,9 @@ class ModelRunner:
             qkv_buf=torch.zeros(8 * TM * nqkv, **f32), logits=torch.zeros(TM, self.Vl, **f32),
             ssq=torch.zeros(2 * self.L + 2, TM, dtype=torch.int64, device=dev),
             amax_part=torch.zeros(TM * ((self.V + 4095) // 4096), dtype=torch.int64, device=dev),
+            # sampled verify steps (ops.spec_sample_commit): the rows' top-k candidates and their picked tokens
+            cand=torch.zeros(TM * ((self.V + 2047) // 2048) * 64, dtype=torch.int64, device=dev),
+            picks=torch.zeros(TM, **i32),
             attn_ws=ops.verify_workspace(TM, self.H, self.Hkv, nsplit_max, dev))
         return self._spec
 
@@ -795,7 +802,7 @@ class ModelRunner:
         buf.copy_(table.to(torch.int32))
         self._spec_forced = buf
 
-    def _verify_step(self, plan: Optional[tuple] = None, guided: bool = False) -> None:
+    def _verify_step(self, plan: Optional[tuple] = None, guided: bool = False, sample: bool = False) -> None:
         """One speculative-decoding step of the request in slot 0: a forward pass over T = k + 1 rows -- the row's input
         token and k drafted tokens at positions p .. p + T - 1 -- and the in-order commit of the tokens greedy decoding
         would have produced (``ops.spec_commit``): between 1 and T per step, the same sequence as plain steps.
@@ -820,7 +827,14 @@ class ModelRunner:
         ``guided`` (a constrained request, ``spec_guided``): ``dfa_mask_verify`` between the lm_head and spec_commit masks
         row t in the DFA state after the input token and drafts 1..t, so the commit accepts a draft only where the plain
         guided step would have chosen it; ``dfa_spec_advance`` after the commit leaves the state after the accepted
-        drafts where the next mask launch -- verify or plain -- advances from."""
+        drafts where the next mask launch -- verify or plain -- advances from.
+
+        ``sample`` (a request that needs the sampler, ``spec_sampled``): the step ends in ``ops.spec_sample_commit``
+        instead: row i is penalised over the ring as it would stand had drafts 0 .. i-1 been committed and makes the
+        plain step's draw for generated token gen_len + i; a draft is accepted exactly when it equals that draw, so
+        the committed tokens are the plain sampled tokens of the same seed.  A rejected row's draw counter is used
+        again by the next step, as the plain path would use it.  With ``guided`` the mask runs before it (a -inf logit
+        stays -inf under the penalty and is never kept by the sampler) and the DFA hand-over after it, unchanged."""
         w, d, T = self.w, self.d, self.spec_k() + 1
         sb = self._spec_bufs()
         n_max, n_min = self.spec_ngram
@@ -875,8 +889,15 @@ class ModelRunner:
             ops.dfa_mask_verify(logits, self.g_tok_off, self.g_tok_blob, self.g_cls, self.g_trans, self.g_accept,
                                 self.g_dim, self.g_on, self.g_state, self.g_base, st[1], st[2], st[4], self.eos,
                                 sb["draft"][:T - 1], self.g_spec)
-        ops.spec_commit(logits, sb["draft"][:T - 1], sb["stats"], *st, self.eos, self.limit[:1], self.eos_on[:1],
-                        part=sb["amax_part"] if self.on_gpu else None)
+        if sample:
+            ops.spec_sample_commit(logits, sb["draft"][:T - 1], sb["stats"], self.hist[:1], self.penalty[:1],
+                                   self.temperature[:1], self.top_k[:1], self.top_p[:1], self.seeds[:1], *st, self.eos,
+                                   self.limit[:1], self.eos_on[:1],
+                                   workspace=(sb["amax_part"], sb["cand"], sb["picks"]) if self.on_gpu else None,
+                                   last_n=self.last_n[:1])
+        else:
+            ops.spec_commit(logits, sb["draft"][:T - 1], sb["stats"], *st, self.eos, self.limit[:1], self.eos_on[:1],
+                            part=sb["amax_part"] if self.on_gpu else None)
         if guided:
             ops.dfa_spec_advance(self.g_on, self.g_state, self.g_spec, st[1], T - 1)
 
@@ -907,28 +928,36 @@ class ModelRunner:
         return out
 
     def spec_logits(self) -> torch.Tensor:
-        """[T, V] f32: the verify rows of the last verify step (the numerics check reads them)."""
+        """[T, V] f32: the verify rows of the last verify step (the numerics check reads them).  After a guided and /
+        or sampled verify step they are the rows as the commit read them: masked (-inf) and with the repetition
+        penalty of a sampled step applied."""
         return self._spec_bufs()["logits"][: self.spec_k() + 1]
 
     def spec_drafts(self) -> torch.Tensor:
         """[k] int32: the drafts of the last verify step (-1 = none)."""
         return self._spec_bufs()["draft"][: self.spec_k()]
 
-    def decode_spec(self, steps: int, max_ctx: Optional[int] = None, guided: bool = False) -> None:
+    def decode_spec(self, steps: int, max_ctx: Optional[int] = None, guided: bool = False,
+                    sample: bool = False) -> None:
         """Run ``steps`` verify steps of the request in slot 0 (the analogue of ``decode`` at bucket 1); ``max_ctx``
         bounds pos0 + T during the run (picks the split plan's tier).  ``guided``: the variant with the regex mask of
-        the verify rows, for a constrained request (its graph key is the unguided one with a trailing True)."""
+        the verify rows, for a constrained request (its graph key is the unguided one with a trailing True).
+        ``sample``: the variant that ends in the sampled commit, for a request that needs the sampler (its graph key
+        is the greedy one with a trailing "sample"; the greedy graphs and their keys are untouched)."""
         assert self.spec_supported(), ("speculative decoding: TP = 1, spec_tokens > 0, bf16 weights and KV cache "
                                        "(or spec_quantized)")
         assert not guided or (self.guided and self.spec_guided), "guided verify steps need enable_guided() and spec_guided"
+        assert not sample or self.spec_sampled, "sampled verify steps need spec_sampled"
         plan = tuple(self.ctx_plan(1, max_ctx))
         if not self.use_graphs:
             for _ in range(steps):
-                self._verify_step(plan, guided)
+                self._verify_step(plan, guided, sample)
             return
         key = ("spec", self.spec_k() + 1, plan, 0 if self._spec_forced is None else self._spec_forced.data_ptr())
         if guided:
             key += (True,)
+        if sample:
+            key += ("sample",)
         if key not in self.graphs:
             self._spec_bufs()
             s = torch.cuda.Stream(device=self.device)
@@ -936,7 +965,7 @@ class ModelRunner:
             g = torch.cuda.CUDAGraph()
             with torch.cuda.stream(s):
                 with torch.cuda.graph(g, stream=s):
-                    self._verify_step(plan, guided)
+                    self._verify_step(plan, guided, sample)
             torch.cuda.current_stream(self.device).wait_stream(s)
             self.graphs[key] = g
         g = self.graphs[key]

@@ -251,14 +251,19 @@ def check_recorded(eng, prompts, toks, elog, n_steps: int, check_rows: Sequence[
     return res
 
 
-def record_spec_logits(eng, prompt: Sequence[int], n_tokens: int, hidden: Optional[bool] = None):
+def record_spec_logits(eng, prompt: Sequence[int], n_tokens: int, hidden: Optional[bool] = None, params=None):
     """Greedy-decode ONE prompt through the speculative-decoding verify steps (``LLMEngine(spec_tokens > 0)``), one
     verify step per engine iteration.  Returns (tokens [n_tokens + 1], logits [1, n_tokens, V] f32, steps) in
     ``record_decode_logits``'s convention: logits[0, j - 1] is the verify row that chose token j (token 0 comes from
     prefill) -- row i of the step that committed it as its i-th token.  ``hidden``: as in ``record_decode_logits``.
     ``steps``: one dict per engine iteration -- first (index of its first committed token), committed (tokens it
     committed), spec (whether it was a verify step), and for verify steps draft ([k] drafted ids, -1 = none) and
-    row_argmax ([T] argmax of every verify row)."""
+    row_argmax ([T] argmax of every verify row).
+    ``params``: the request's ``SamplingParams`` instead of the greedy ones (None) -- a sampled request on a
+    ``spec_sampled`` engine; its max_tokens and ignore_eos are set as the greedy request's.  The recorded rows of a
+    sampled verify step are the rows its commit read: with the repetition penalty applied."""
+    import dataclasses
+
     from ..engine import SamplingParams
 
     r = eng.runner
@@ -266,7 +271,9 @@ def record_spec_logits(eng, prompt: Sequence[int], n_tokens: int, hidden: Option
     old = eng.run_ahead
     eng.run_ahead = 1
     try:
-        q = eng.add_request(list(prompt), SamplingParams(max_tokens=n_tokens + 1, temperature=0.0, ignore_eos=True))
+        sp = (SamplingParams(max_tokens=n_tokens + 1, temperature=0.0, ignore_eos=True) if params is None
+              else dataclasses.replace(params, max_tokens=n_tokens + 1, ignore_eos=True))
+        q = eng.add_request(list(prompt), sp)
         out = torch.zeros(1, n_tokens, r.V, dtype=torch.float32, device=r.device)
         hid = torch.zeros(1, n_tokens, r.d, dtype=torch.float32, device=r.device) if hidden else None
         steps, have = [], 0

@@ -1533,6 +1533,33 @@ def spec_commit(logits, draft, stats, out_tokens, gen_len, input_ids, positions,
     ext().spec_commit(logits, part, draft, stats, out_tokens, gen_len, input_ids, positions, finished, eos, limit, eos_on)
 
 
+def spec_sample_commit(logits, draft, stats, hist, penalty, temperature, top_k, top_p, seeds, out_tokens, gen_len,
+                       input_ids, positions, finished, eos, limit=None, eos_on=None, workspace=None, last_n=None):
+    """Sampled verification of the T = k + 1 verify rows ``logits`` (2 <= T <= 8, V <= 262144) of the sequence in
+    state row 0 (kernels/sampling.hip lsa_spec_sample_commit).  Row i is penalised over the ring ``hist`` [1, W] as it
+    would stand had drafts 0 .. i-1 been committed (``logits`` is modified) and makes the draw of the plain
+    ``sample_commit`` step for generated token gen_len[0] + i (temperature <= 0: the argmax); a draft is accepted
+    exactly when it equals that draw, and the accepted run is committed in order, ring included, so the tokens are
+    those of the plain sampled steps of the same seed.  The parameters are row 0's; stats int64 [3] += (steps, drafted,
+    accepted).  ``workspace`` = (part, cand, picks): int64 [T * ceil(V / 4096)], int64 [T * ceil(V / 2048) * 64],
+    int32 [T] (the rows' tokens)."""
+    T, V = logits.shape
+    limit, eos_on = _row_defaults(1, out_tokens, limit, eos_on)
+    if not _gpu(logits):
+        if not 2 <= T <= 8 or V > 262144:  # as the binding and the launcher refuse them
+            raise RuntimeError("spec_sample_commit: 2 <= T <= 8 verify rows, V <= 262144")
+        return ref.spec_sample_commit(logits, draft, stats, hist, penalty, temperature, top_k, top_p, seeds,
+                                      out_tokens, gen_len, input_ids, positions, finished, eos, limit, eos_on,
+                                      last_n=last_n)
+    if workspace is None:
+        workspace = (torch.empty(T * ((V + 4095) // 4096), device=logits.device, dtype=torch.int64),
+                     torch.empty(T * ((V + 2047) // 2048) * 64, device=logits.device, dtype=torch.int64),
+                     torch.empty(T, device=logits.device, dtype=torch.int32))
+    part, cand, picks = workspace
+    ext().spec_sample_commit(logits, draft, stats, hist, penalty, last_n, temperature, top_k, top_p, seeds, out_tokens,
+                             gen_len, input_ids, positions, finished, eos, limit, eos_on, part, cand, picks)
+
+
 # ----------------------------------------------------------------------------------- regex-constrained decoding
 def dfa_mask(logits, tok_off, tok_blob, cls, trans, accept, g_dim, g_on, g_state, g_base, gen_len, input_ids,
              finished, eos, rows=None):

@@ -557,3 +557,93 @@ def sample_commit(logits, hist, penalty, temperature, top_k, top_p, seeds, out_t
         g = generator if generator is not None else torch.Generator().manual_seed(draw_seed(int(seeds[b]), int(gen_len[b])))
         toks[b] = int(idx[torch.multinomial(p.cpu(), 1, generator=g)])
     commit(toks, out_tokens, gen_len, input_ids, positions, finished, eos, limit, eos_on, hist=hist)
+
+
+# --------------------------------------------------------------- speculative decoding of a sampled request
+def spec_penalised_row(row, hist_row, draft, i, pen, pos, last_n):
+    """Verify row ``i`` of a sampled verify step with its repetition penalty (spec_repeat_penalty_kernel): ``row``
+    (modified and returned) is penalised with ``repeat_penalty``'s rule over the distinct tokens at context positions
+    (pos + i - m, pos + i], m = min(last_n, W, pos + i + 1), where ``pos`` is the row's position at the launch: the
+    token at position pos + j, 1 <= j <= i, is ``draft[j - 1]``, the token at a position <= pos is
+    ``hist_row[position % W]`` -- the ring the plain step at position pos + i would see had drafts 0 .. i-1 been
+    committed.  (A ring slot whose position is > pos holds a token W positions older; m <= W, so it is never read for
+    it.)  A draft < 0 or >= V penalises nothing; pen == 1 changes nothing."""
+    if float(pen) == 1.0:
+        return row
+    W = hist_row.numel()
+    P = pos + i
+    m = min(W if last_n is None else int(last_n), W, P + 1)
+    toks = set()
+    for j in range(m):
+        q = P - j
+        toks.add(int(draft[q - pos - 1]) if q > pos else int(hist_row[q % W]))
+    for t in toks:
+        if 0 <= t < row.numel():
+            row[t] = row[t] / pen if row[t] > 0 else row[t] * pen
+    return row
+
+
+def _spec_rows(logits, draft, hist, penalty, last_n, positions):
+    """The T verify rows (f32 clones) with the penalty of ``spec_penalised_row``."""
+    rows = []
+    for i in range(logits.shape[0]):
+        row = logits[i].float().clone()
+        if hist is not None and penalty is not None and float(penalty[0]) != 1.0:
+            row = spec_penalised_row(row, hist[0].cpu(), draft.cpu(), i, float(penalty[0]), int(positions[0]),
+                                     None if last_n is None else int(last_n[0]))
+        rows.append(row)
+    return rows
+
+
+def spec_sample_commit(logits, draft, stats, hist, penalty, temperature, top_k, top_p, seeds, out_tokens, gen_len,
+                       input_ids, positions, finished, eos, limit=None, eos_on=None, last_n=None):
+    """The CPU engine's twin of lsa_spec_sample_commit.  logits [T, V]: the verify rows of the sequence in state row 0,
+    n = gen_len[0] at the call.  Row i is penalised as ``spec_penalised_row`` says (written back into ``logits``) and
+    draws as ``sample_commit`` draws for gen_len = n + i (``sample_probs`` and ``torch.multinomial`` under
+    ``draw_seed(seed, n + i)``; temperature <= 0: the argmax), so a verify step is bit-equal to the plain sampled
+    steps.  Commits picks[0 .. a] in order, ring included (a = leading drafts >= 0 equal to their row's pick),
+    stopping after a finishing token; stats += (1, drafts >= 0, tokens committed beyond the first).  A finished row
+    changes no state."""
+    T = logits.shape[0]
+    n = int(gen_len[0])
+    rows = _spec_rows(logits, draft, hist, penalty, last_n, positions)
+    Tmp = float(temperature[0])
+    picks = []
+    for i, row in enumerate(rows):
+        logits[i].copy_(row)
+        if Tmp <= 0:
+            picks.append(int(row.argmax()))
+            continue
+        idx, p = sample_probs(row, Tmp, int(top_k[0]), float(top_p[0]))
+        g = torch.Generator().manual_seed(draw_seed(int(seeds[0]), n + i))
+        picks.append(int(idx[torch.multinomial(p.cpu(), 1, generator=g)]))
+    if int(finished[0]):
+        return
+    committed = 0
+    for i in range(T):
+        if int(finished[0]):
+            break
+        commit(torch.tensor([picks[i]]), out_tokens, gen_len, input_ids, positions, finished, eos, limit, eos_on,
+               hist=hist)
+        committed += 1
+        if i >= T - 1 or int(draft[i]) < 0 or int(draft[i]) != picks[i]:
+            break
+    stats[0] += 1
+    stats[1] += int((draft[:T - 1] >= 0).sum())
+    stats[2] += max(committed - 1, 0)
+
+
+def spec_sample_pick_sets(logits, draft, hist, penalty, temperature, top_k, top_p, seeds, gen_len, positions,
+                          last_n=None, m: float = SAMPLE_MARGIN) -> list:
+    """The exact device twin of the picks of lsa_spec_sample_commit: per verify row i the set of tokens the device
+    may write to picks[i] -- ``sample_pick_set`` of the penalised row at ``device_uniform(seed, gen_len[0] + i)``, or
+    the plain argmax for temperature <= 0.  A one-element set is a decided draw."""
+    n = int(gen_len[0])
+    Tmp = float(temperature[0])
+    out = []
+    for i, row in enumerate(_spec_rows(logits, draft, hist, penalty, last_n, positions)):
+        if Tmp <= 0:
+            out.append({int(row.argmax())})
+        else:
+            out.append(sample_pick_set(row, Tmp, int(top_k[0]), float(top_p[0]), device_uniform(int(seeds[0]), n + i), m))
+    return out

@@ -8,12 +8,23 @@
   e2e      tokens/s of a request at planted acceptance 0, about half, and all: the envelope.  (Random-init weights
            give no meaningful natural acceptance; real acceptance needs a checkpoint, LSA_CHECKPOINT_DIR.)
 
+With --sampled: speculative decoding of requests that need the sampler (``spec_sampled``) instead, appended to
+profiles/spec/spec_sampled_mi355x.jsonl:
+
+  commit   device time of the sampled verify commit (ops.spec_sample_commit: penalty, partials, per-row pick, in-order
+           commit) against the greedy one (ops.spec_commit) at the same T, and next to it the plain step's
+           sample_commit minus argmax_commit at B = 1 from the same run: the extra cost should be of that order.
+  e2e      tokens/s of ONE sampled request with Ollama's default options (temperature 0.8, top_k 40, top_p 0.9,
+           repeat_penalty 1.1) and a fixed seed on the two prompts above: spec_sampled off (the plain sampled steps)
+           against on with the n-gram drafter (its acceptance counts recorded) and with planted acceptance 0, about
+           half, and all.
+
 Every graph is warmed, times are device events, the arms alternate within one process.  Appends JSON lines to
 profiles/spec/spec_decode_mi355x.jsonl, or -- with quantised weights or the fp8 cache (``spec_quantized`` engines) --
 to profiles/spec/spec_decode_quant_mi355x.jsonl (--out overrides).  Needs a GPU.
 
   python scripts/bench_spec.py [--layers N] [--skip kernel,step,e2e] [--reps 5] [--dtype bf16|fp8|mxfp4]
-                               [--kv-dtype bf16|fp8] [--models duckdb-nsql,llama3.2] [--out FILE]
+                               [--kv-dtype bf16|fp8] [--models duckdb-nsql,llama3.2] [--out FILE] [--sampled]
 """
 from __future__ import annotations
 
@@ -37,6 +48,8 @@ from llm_based_apache_spark_optimization_amd.ops import reference as ref  # noqa
 
 OUT = os.path.join(ROOT, "profiles", "spec", "spec_decode_mi355x.jsonl")
 OUT_QUANT = os.path.join(ROOT, "profiles", "spec", "spec_decode_quant_mi355x.jsonl")
+OUT_SAMPLED = os.path.join(ROOT, "profiles", "spec", "spec_sampled_mi355x.jsonl")
+OLLAMA = dict(temperature=0.8, top_k=40, top_p=0.9, repeat_penalty=1.1)  # Ollama's default option set
 
 
 def emit(rec: dict) -> None:
@@ -194,6 +207,100 @@ def bench_engine(dev, layers, reps: int, skip, dtype: str = "bf16", kv_dtype: st
         torch.cuda.empty_cache()
 
 
+def bench_sampled_commit(dev, reps: int, models=()) -> None:
+    """The verify commits alone, over static rows: every launch commits one token (the drafts are -1)."""
+    W, max_new = 64, 8192  # ~520 launches per arm and measurement: no row reaches its limit
+    for base in ("duckdb-nsql", "llama3.2"):
+        if models and base not in models:
+            continue
+        V = get_spec(base).vocab_size
+        g = torch.Generator().manual_seed(V)
+        logits0 = (torch.randn(8, V, generator=g) * 2).to(dev)
+        i32 = dict(dtype=torch.int32, device=dev)
+        par = dict(hist=torch.randint(0, V, (1, W), generator=g, dtype=torch.int32).to(dev),
+                   pen=torch.tensor([OLLAMA["repeat_penalty"]], device=dev), last_n=torch.tensor([W], **i32),
+                   temp=torch.tensor([OLLAMA["temperature"]], device=dev), top_k=torch.tensor([OLLAMA["top_k"]], **i32),
+                   top_p=torch.tensor([OLLAMA["top_p"]], device=dev),
+                   seeds=torch.tensor([ref.pack_seed(17, 0)], dtype=torch.int64, device=dev))
+        eos = torch.tensor([-1], **i32)
+        draft = torch.full((8,), -1, **i32)
+        part = torch.zeros(8 * ((V + 4095) // 4096), dtype=torch.int64, device=dev)
+        cand = torch.zeros(8 * ((V + 2047) // 2048) * 64, dtype=torch.int64, device=dev)
+        picks = torch.zeros(8, **i32)
+
+        def state():
+            return (torch.zeros(1, max_new, **i32), torch.zeros(1, **i32), torch.zeros(1, **i32),
+                    torch.full((1,), 100, **i32), torch.zeros(1, **i32))
+
+        def arm(kind: str, T: int):
+            st, stats, lg = state(), torch.zeros(3, dtype=torch.int64, device=dev), logits0[:T].clone()
+            if kind == "spec_sampled":
+                return lambda: ops.spec_sample_commit(lg, draft[:T - 1], stats, par["hist"], par["pen"], par["temp"],
+                                                      par["top_k"], par["top_p"], par["seeds"], *st, eos,
+                                                      workspace=(part, cand, picks), last_n=par["last_n"])
+            if kind == "spec_greedy":
+                return lambda: ops.spec_commit(lg, draft[:T - 1], stats, *st, eos, part=part)
+            if kind == "plain_sampled":
+                return lambda: ops.sample_commit(lg, par["hist"], par["pen"], par["temp"], par["top_k"], par["top_p"],
+                                                 par["seeds"], *st, eos, workspace=(part, cand), last_n=par["last_n"])
+            return lambda: ops.argmax_commit(lg, *st, eos, part=part)
+
+        us = {}
+        for _ in range(reps):  # alternate the arms
+            for kind, T in [("plain_greedy", 1), ("plain_sampled", 1)] + [(k, T) for T in (2, 4, 8)
+                                                                         for k in ("spec_greedy", "spec_sampled")]:
+                us.setdefault(f"{kind}_T{T}", []).append(time_graph(arm(kind, T)))
+        med = {k: round(statistics.median(v), 2) for k, v in us.items()}
+        plain_extra = med["plain_sampled_T1"] - med["plain_greedy_T1"]
+        emit(dict(bench="sampled_commit", model=base, V=V, us=med, plain_extra_us=round(plain_extra, 2),
+                  verify_extra_us={T: round(med[f"spec_sampled_T{T}"] - med[f"spec_greedy_T{T}"], 2) for T in (2, 4, 8)},
+                  verify_extra_over_plain_extra={T: round((med[f"spec_sampled_T{T}"] - med[f"spec_greedy_T{T}"])
+                                                          / plain_extra, 2) for T in (2, 4, 8)}))
+
+
+def bench_sampled_engine(dev, layers, reps: int, models=(), k: int = 3, seed: int = 11) -> None:
+    for base, plen, new in (("duckdb-nsql", 128, 128), ("llama3.2", 2048, 128)):
+        if models and base not in models:
+            continue
+        spec = get_spec(base)
+        if layers:
+            spec = dataclasses.replace(spec, n_layers=layers, name=f"{base}-{layers}l")
+        w = init_random(spec, dev, seed=5)
+        r = ModelRunner(w, max_slots=2, max_model_len=plen + new + 64, num_kv_blocks=2 * ((plen + new) // 64 + 3),
+                        spec_tokens=k, spec_sampled=True)
+        eng = LLMEngine(r, name=spec.name)
+        g = torch.Generator().manual_seed(7)
+        ids = [1] + torch.randint(3, 30000, (plen - 1,), generator=g).tolist()
+        sp = SamplingParams(max_tokens=new, ignore_eos=True, seed=seed, **OLLAMA)
+
+        def run(on: bool, kind: str = "", toks=None):
+            """(tokens, decode steps, tokens / s of the decode phase, (verify steps, drafted, accepted))."""
+            r.spec_sampled = on
+            r.set_spec_forced(None if not kind else forced(toks, kind, r.spec_k(), spec.vocab_size))
+            d0, n0, c0 = eng.stats["decode_device_s"], eng.stats["decode_steps"], r.spec_counts()
+            out = eng.generate([ids], sp)[0].token_ids
+            ds, ns = eng.stats["decode_device_s"] - d0, eng.stats["decode_steps"] - n0
+            return out, ns, (len(out) - 1) / ds, [a - b for a, b in zip(r.spec_counts(), c0)]
+
+        plain = run(False)[0]     # warms the plain sampled graphs
+        toks = run(True)[0]       # ... and the sampled verify graph (n-gram drafts): the verify path's own tokens
+        res, counts, same = {}, {}, {}
+        for _ in range(reps):
+            for name, args in (("off", (False,)), ("ngram", (True,)), ("none", (True, "none", toks)),
+                               ("half", (True, "half", toks)), ("all", (True, "all", toks))):
+                out, ns, tps, c = run(*args)
+                res.setdefault(name, []).append(tps)
+                counts[name] = dict(decode_steps=ns, verify_steps=c[0], drafted=c[1], accepted=c[2])
+                same[name] = out == (plain if name == "off" else toks)
+        tok_s = {n: round(statistics.median(v), 1) for n, v in res.items()}
+        emit(dict(bench="sampled_e2e", model=spec.name, layers=spec.n_layers, prompt=plen, new=new, k=r.spec_k(),
+                  options=OLLAMA, seed=seed, decode_tok_s=tok_s, counts=counts, tokens_repeat=same,
+                  verify_tokens_equal_plain=toks == plain,
+                  speedup_over_off={n: round(v / tok_s["off"], 3) for n, v in tok_s.items()}))
+        del eng, r, w
+        torch.cuda.empty_cache()
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--layers", type=int, default=0, help="truncate the models to this many layers (0 = full depth)")
@@ -203,14 +310,22 @@ def main() -> None:
     ap.add_argument("--kv-dtype", default="bf16", choices=("bf16", "fp8"), help="KV cache dtype of the engines")
     ap.add_argument("--models", default="", help="comma list of duckdb-nsql,llama3.2 (default both)")
     ap.add_argument("--out", default="", help="JSON-lines file to append to")
+    ap.add_argument("--sampled", action="store_true", help="measure spec_sampled (sampled verify commit, sampled request)")
     a = ap.parse_args()
     global OUT
-    OUT = a.out or (OUT if (a.dtype, a.kv_dtype) == ("bf16", "bf16") else OUT_QUANT)
+    OUT = a.out or (OUT_SAMPLED if a.sampled else OUT if (a.dtype, a.kv_dtype) == ("bf16", "bf16") else OUT_QUANT)
     if not torch.cuda.is_available():
         raise SystemExit("bench_spec.py needs a GPU")
     ops.ext()
     dev = torch.device("cuda:0")
     skip = set(a.skip.split(",")) if a.skip else set()
+    if a.sampled:
+        models = tuple(m for m in a.models.split(",") if m)
+        if "kernel" not in skip:
+            bench_sampled_commit(dev, a.reps, models)
+        if "e2e" not in skip:
+            bench_sampled_engine(dev, a.layers, a.reps, models)
+        return
     if "kernel" not in skip:
         bench_kernel(dev, a.reps)
     if not {"step", "e2e"} <= skip:
