@@ -84,7 +84,6 @@ __global__ __launch_bounds__(64 * WAVES) void gemm_skinny_kernel(const uint16_t*
   const int nk = kbB - kbA;
   const int nch = (nk + U - 1) / U;                     // chunks in this split
   const int n_it = nch > w ? (nch - w + WAVES - 1) / WAVES : 0;  // chunks of this wave
-  const int last_c = w + WAVES * (n_it - 1);
 
   f32x4_t acc[NB][MT];
 #pragma unroll
@@ -211,18 +210,29 @@ __global__ __launch_bounds__(64 * WAVES) void gemm_skinny_kernel(const uint16_t*
   if (n_it > 0) {
     int i = 0;
     // sched_barrier(0) pins the issue order: the next chunk's loads all leave before this chunk's
-    // MFMAs (hipcc otherwise interleaves them and keeps only ~8 loads in flight)
-    for (; i + 1 < n_it; i += 2) {
+    // MFMAs (hipcc otherwise interleaves them and keeps only ~8 loads in flight).  The last iteration is
+    // peeled: the steady-state loop always has a chunk i + 2 to request, and the tail requests nothing it does
+    // not use (an even chunk count used to re-request its last chunk, weights and activations, and drop it:
+    // one load in eight of the o projection's at batch 32).
+    for (; i + 2 < n_it; i += 2) {
       load(wB, xB, w + WAVES * (i + 1));
       __builtin_amdgcn_sched_barrier(0);
       comp(wA, xA, w + WAVES * i);
       __builtin_amdgcn_sched_barrier(0);
-      load(wA, xA, min(w + WAVES * (i + 2), last_c));  // clamped: the tail re-reads a cached chunk
+      load(wA, xA, w + WAVES * (i + 2));
       __builtin_amdgcn_sched_barrier(0);
       comp(wB, xB, w + WAVES * (i + 1));
       __builtin_amdgcn_sched_barrier(0);
     }
-    if (i < n_it) comp(wA, xA, w + WAVES * i);
+    if (i + 1 < n_it) {
+      load(wB, xB, w + WAVES * (i + 1));
+      __builtin_amdgcn_sched_barrier(0);
+      comp(wA, xA, w + WAVES * i);
+      __builtin_amdgcn_sched_barrier(0);
+      comp(wB, xB, w + WAVES * (i + 1));
+    } else {
+      comp(wA, xA, w + WAVES * i);
+    }
   }
 
   // cross-wave reduction: red[w][tile][lane]
