@@ -128,6 +128,8 @@ int lsa_ar_run(float* data, long n, float* out, uint8_t* const* regions, int ran
 int lsa_fp4_gemm_ex(const void* X, int ldx, int M, int K, const void* Wq, const void* S, int N, void* out, int epi,
                     int nb, int splitk, int waves, int xfrag, const LsaEpi* ep, hipStream_t stream);
 int lsa_fp4_dequant(const void* Wq, const void* S, int N, int K, void* Wf, hipStream_t s);
+int lsa_gemm_z12(const void* X, int M, int K, const void* lo, const void* hi, const void* esc, int base, int N,
+                 void* out, int epi, int nb, int splitk, int waves, int div, const LsaEpi* ep, hipStream_t stream);
 }
 
 namespace {
@@ -310,6 +312,34 @@ void gemm_xf(const at::Tensor& xf, int64_t M, int64_t K, const at::Tensor& wf, i
         "gemm_xf");
 }
 
+// gemm_xf at 17..32 rows over the lossless 12-bit weight stream (kernels/gemm_z12.hip; lo / hi / esc / base:
+// ops.pack_z12 of the [N, K] bf16 weight): bit-identical to gemm_xf at the same (nb, splitk, waves, div).
+// Epilogues bf16, f32 slabs, SiLU; row scale; no residual epilogue.
+void z12_gemm_xf(const at::Tensor& xf, int64_t M, int64_t K, const at::Tensor& lo, const at::Tensor& hi,
+                 const at::Tensor& esc, int64_t base, int64_t N, at::Tensor& out, int64_t epi, int64_t nb,
+                 int64_t splitk, int64_t waves, int64_t div, const c10::optional<at::Tensor>& rowss, double eps) {
+  need(xf, at::kBFloat16, "xf");
+  need(lo, at::kByte, "lo");
+  need(hi, at::kByte, "hi");
+  need(esc, at::kInt, "esc");
+  TORCH_CHECK(M > 16 && M <= 32 && K >= 32 && K % 32 == 0 && N >= 16 && N % 16 == 0,
+              "z12_gemm_xf: M in 17..32, K % 32 == 0, N % 16 == 0");
+  TORCH_CHECK(epi >= 0 && epi <= 2, "z12_gemm_xf: epilogue bf16 (0), f32 (1) or silu (2)");
+  TORCH_CHECK(base >= 1 && base <= 120, "z12_gemm_xf: base out of range");
+  TORCH_CHECK(splitk >= 1 && splitk <= K / 32 && (epi == 1 || splitk == 1), "z12_gemm_xf: bad splitk");
+  TORCH_CHECK(xf.is_contiguous() && xf.numel() >= 2 * 16 * K, "xf too small for M=", M, " K=", K);
+  TORCH_CHECK(lo.is_contiguous() && hi.is_contiguous() && esc.is_contiguous() && lo.numel() == N * K &&
+                  hi.numel() == N * K / 2 && esc.numel() == (N / 16) * (K / 32) * 4,
+              "z12 planes do not match N x K");
+  check_out(epi, out, splitk, M, N, 2);
+  // the fragment-major SiLU output is written in whole 32-column k-steps of two row tiles
+  TORCH_CHECK(epi != 2 || out.numel() >= 32 * ((N / 2 + 31) / 32 * 32), "z12_gemm_xf: silu out too small");
+  const EpiOpts eo = epi_opts(epi, M, N, K, rowss, eps, c10::nullopt, c10::nullopt, 0, c10::nullopt, c10::nullopt, 0);
+  check(lsa_gemm_z12(xf.data_ptr(), (int)M, (int)K, lo.data_ptr(), hi.data_ptr(), esc.data_ptr(), (int)base, (int)N,
+                     out.data_ptr(), (int)epi, (int)nb, (int)splitk, (int)waves, (int)div, eo.on ? &eo.e : nullptr,
+                     cur_stream()),
+        "z12_gemm_xf");
+}
 
 // fp8 weights, activations in the fragment-major decode layout (ops.to_xfrag), M <= 64
 void fp8_gemm_xf(const at::Tensor& xf, int64_t M, int64_t K, const at::Tensor& wq, const at::Tensor& wscale, int64_t N,
@@ -1321,6 +1351,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_xf", &gemm_xf, py::arg("xf"), py::arg("M"), py::arg("K"), py::arg("wf"), py::arg("N"), py::arg("out"),
         py::arg("epi"), py::arg("nb"), py::arg("splitk"), py::arg("waves") = 4, py::arg("div") = 4,
         py::arg("rowss") = py::none(), py::arg("eps") = 1e-5, py::arg("h") = py::none(), py::arg("xout") = py::none(), py::arg("xmt") = 0, py::arg("ss_out") = py::none(), py::arg("tickets") = py::none());
+  m.def("z12_gemm_xf", &z12_gemm_xf, py::arg("xf"), py::arg("M"), py::arg("K"), py::arg("lo"), py::arg("hi"),
+        py::arg("esc"), py::arg("base"), py::arg("N"), py::arg("out"), py::arg("epi"), py::arg("nb"), py::arg("splitk"),
+        py::arg("waves") = 4, py::arg("div") = 4, py::arg("rowss") = py::none(), py::arg("eps") = 1e-5);
   m.def("gemm_sk", &gemm_sk, py::arg("x"), py::arg("wf"), py::arg("N"), py::arg("out"), py::arg("epi"), py::arg("ws"),
         py::arg("tickets"), py::arg("ncu"), py::arg("min_share") = 0, py::arg("cfg") = -1, py::arg("xf") = 0,
         py::arg("rows") = 0);

@@ -1,0 +1,340 @@
+// Decode GEMM at 17-32 rows over a lossless 12-bit weight stream ("z12"):  out[M, N] = X[M, K] @ W[N, K]^T with the
+// bf16 values of W, bit for bit, read as 784 bytes per 16 x 32 MFMA fragment instead of 1024.
+//
+// z12 (ops.pack_z12) is derived per tensor from the fragment-major bf16 layout Wf[nb][kb][lane][8] of gemm.hip; lane
+// 16 g + r owns the same 8 elements W[16 nb + r][32 kb + 8 g + i]:
+//   LO  [N/16][K/32][64 lanes][8 B]  byte i = the low byte of element i (exponent bit 0 + the 7 mantissa bits)
+//   HI  [N/16][K/32][64 lanes][4 B]  one nibble per element, sign << 3 | (exp[7:1] - base); element j in the low and
+//                                    element 4 + j in the high nibble of byte j.  base is one integer per tensor: the
+//                                    start of the 8-value window of exp[7:1] (16 binades) that covers most elements
+//   ESC [N/16][K/32][4] u32          up to four exact patches per fragment for elements outside the window (zeros,
+//                                    outliers): valid << 31 | lane << 20 | slot << 16 | bf16 bits
+// A wave loads LO (8 B per lane), HI (4 B per lane) and the fragment's ESC record (lane l its entry l & 3: a vector load,
+// so the record arrives in order with the planes and waiting for it does not wait for the next chunk's, as a scalar
+// load's out-of-order counter would; the entries are read back with v_readlane under a ballot), rebuilds exactly the
+// uint4 gemm_skinny_kernel would have loaded, and issues the same MFMAs: the work split (chunks of U k-steps dealt
+// round-robin to the waves of a split-K range), the accumulation order, the cross-wave reduction and the epilogues are
+// gemm.hip's, so at equal (nb, splitk, waves, div) the output is bit-identical to the bf16 kernel's.
+//
+// Fragment-major activations (ops.to_xfrag) and two row tiles (MT = 2) only; epilogues bf16, f32 slabs, SiLU(gate)*up.
+#include "common.h"
+
+#define EPI_BF16 0
+#define EPI_F32 1
+#define EPI_SILU 2
+
+typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ uint2 ldg_nt2(const uint2* p) {
+  const u32x2_t v = __builtin_nontemporal_load(reinterpret_cast<const u32x2_t*>(p));
+  return make_uint2(v[0], v[1]);
+}
+__device__ __forceinline__ uint32_t ldg_nt1(const uint32_t* p) { return __builtin_nontemporal_load(p); }
+
+// One fragment-lane: 8 low bytes + 8 codes -> the lane's 8 bf16.  The high byte of a code c is
+// (c & 8) << 4 | ((c & 7) + base), formed for four codes at a time on a dword (base4 = base in every byte; (c & 7) +
+// base <= 127, no carry between bytes), then two byte permutes per high-byte dword interleave it with the low bytes.
+// v_perm_b32 selects from {src0 (bytes 4..7), src1 (bytes 0..3)}.
+__device__ __forceinline__ uint4 z12_decode(const uint2 lo, const uint32_t hi, const uint32_t base4) {
+  const uint32_t ha = ((hi & 0x07070707u) + base4) | ((hi & 0x08080808u) << 4);
+  const uint32_t hb = (((hi >> 4) & 0x07070707u) + base4) | (hi & 0x80808080u);
+  uint4 r;
+  r.x = __builtin_amdgcn_perm(ha, lo.x, 0x05010400u);
+  r.y = __builtin_amdgcn_perm(ha, lo.x, 0x07030602u);
+  r.z = __builtin_amdgcn_perm(hb, lo.y, 0x05010400u);
+  r.w = __builtin_amdgcn_perm(hb, lo.y, 0x07030602u);
+  return r;
+}
+
+// one patch entry (wave-uniform) into the owning lane's fragment: unrolled selects, no register indexing
+__device__ __forceinline__ void z12_patch1(uint4& w, const uint32_t e, const int lane) {
+  const bool mine = (e >> 31) != 0u && ((e >> 20) & 63u) == (uint32_t)lane;
+  const uint32_t slot = (e >> 16) & 7u, d = slot >> 1;
+  const uint32_t keep = (slot & 1u) ? 0x0000ffffu : 0xffff0000u;
+  const uint32_t ins = (slot & 1u) ? (e << 16) : (e & 0xffffu);
+  w.x = (mine && d == 0u) ? ((w.x & keep) | ins) : w.x;
+  w.y = (mine && d == 1u) ? ((w.y & keep) | ins) : w.y;
+  w.z = (mine && d == 2u) ? ((w.z & keep) | ins) : w.z;
+  w.w = (mine && d == 3u) ? ((w.w & keep) | ins) : w.w;
+}
+
+// chunk depth of gemm.hip's SkinnyCfg (the k-step -> (split, wave, order) assignment must be the bf16 kernel's)
+template <int MT, int NB, int DIV>
+struct Z12Cfg {
+  static constexpr int U0 = (16 / (NB > 2 * MT ? NB : 2 * MT)) < 2 ? 2 : (16 / (NB > 2 * MT ? NB : 2 * MT));
+  static constexpr int U = (U0 / DIV) < 1 ? 1 : (U0 / DIV);
+};
+
+template <int NB, int EPI, int WAVES, int DIV>
+__global__ __launch_bounds__(64 * WAVES) void gemm_z12_kernel(const uint16_t* __restrict__ X, int M, int KB,
+                                                              const uint2* __restrict__ Lo,
+                                                              const uint32_t* __restrict__ Hi,
+                                                              const uint32_t* __restrict__ Esc, uint32_t base4,
+                                                              void* __restrict__ out, int ldo, int kb_per_split,
+                                                              LsaEpi ep) {
+  constexpr int MT = 2;
+  constexpr int U = Z12Cfg<MT, NB, DIV>::U;
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform: chunk indices stay scalar
+  const int r = lane & 15;
+  int nb0, cnt;  // this workgroup's n-blocks (ragged grids: common.h skinny_nblocks)
+  skinny_nblocks<NB, EPI == EPI_SILU ? 2 : 1>(EPI == EPI_SILU ? ldo / 8 : ldo / 16, nb0, cnt);
+  const int kbA = blockIdx.y * kb_per_split;
+  const int kbB = min(KB, kbA + kb_per_split);
+  const int nk = kbB - kbA;
+  const int nch = (nk + U - 1) / U;                               // chunks in this split
+  const int n_it = nch > w ? (nch - w + WAVES - 1) / WAVES : 0;  // chunks of this wave
+
+  f32x4_t acc[NB][MT];
+#pragma unroll
+  for (int i = 0; i < NB; ++i)
+#pragma unroll
+    for (int j = 0; j < MT; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+
+  const uint16_t* xp[MT];
+  bool xvalid[MT];
+#pragma unroll
+  for (int j = 0; j < MT; ++j) {
+    xvalid[j] = j * 16 + r < M;
+    xp[j] = X + ((size_t)j * 64 + lane) * 8;
+  }
+  size_t fb[NB];  // first record of n-block i (blocks >= cnt re-read the workgroup's last block and are never stored)
+#pragma unroll
+  for (int i = 0; i < NB; ++i) fb[i] = (size_t)(nb0 + min(i, cnt - 1)) * KB;
+
+  struct Chunk {
+    uint2 lo[U][NB];
+    uint32_t hi[U][NB];
+    uint32_t esc[U][NB];  // lane l holds entry l & 3 of the fragment's record
+    uint4 x[U][MT];
+  };
+  auto load = [&](Chunk& c, int ci) {
+    const int kb = kbA + ci * U;
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int kk = min(kb + u, kbB - 1);
+#pragma unroll
+      for (int i = 0; i < NB; ++i) {
+        const size_t f = fb[i] + kk;
+        c.lo[u][i] = ldg_nt2(Lo + f * 64 + lane);
+        c.hi[u][i] = ldg_nt1(Hi + f * 64 + lane);
+        c.esc[u][i] = Esc[f * 4 + (lane & 3)];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int kk = min(kb + u, kbB - 1);
+#pragma unroll
+      for (int j = 0; j < MT; ++j) c.x[u][j] = *reinterpret_cast<const uint4*>(xp[j] + (size_t)kk * MT * 512);
+    }
+  };
+  auto comp = [&](const Chunk& c, int ci) {
+    const int kb = kbA + ci * U;
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const bool live = (kb + u) < kbB;
+      uint4 wv[NB];
+#pragma unroll
+      for (int i = 0; i < NB; ++i) {
+        wv[i] = z12_decode(c.lo[u][i], c.hi[u][i], base4);
+        const uint32_t e = c.esc[u][i];
+        if (__builtin_amdgcn_ballot_w64((e >> 31) != 0u)) {  // wave-uniform, rare
+          z12_patch1(wv[i], __builtin_amdgcn_readlane(e, 0), lane);
+          z12_patch1(wv[i], __builtin_amdgcn_readlane(e, 1), lane);
+          z12_patch1(wv[i], __builtin_amdgcn_readlane(e, 2), lane);
+          z12_patch1(wv[i], __builtin_amdgcn_readlane(e, 3), lane);
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < MT; ++j) {
+        const bool ok = live && xvalid[j];
+        uint4 xv = c.x[u][j];
+        xv.x = ok ? xv.x : 0u; xv.y = ok ? xv.y : 0u; xv.z = ok ? xv.z : 0u; xv.w = ok ? xv.w : 0u;
+#pragma unroll
+        for (int i = 0; i < NB; ++i) acc[i][j] = mfma16x16x32(wv[i], xv, acc[i][j]);
+      }
+    }
+  };
+  auto ch = [&](int i) { return w + WAVES * i; };
+
+  // gemm.hip's two-deep register pipeline with the peeled tail.  sched_barrier(0) pins the issue order: a chunk's loads
+  // all leave before the previous chunk's decode and MFMAs; nothing is requested that is not used.  (A third chunk in
+  // flight measured slower or equal on every 7B shape and was removed, ARCHITECTURE.md section 4.)
+  Chunk A, B;
+  if (n_it > 0) {
+    load(A, ch(0));
+    int i = 0;
+    for (; i + 2 < n_it; i += 2) {
+      load(B, ch(i + 1));
+      __builtin_amdgcn_sched_barrier(0);
+      comp(A, ch(i));
+      __builtin_amdgcn_sched_barrier(0);
+      load(A, ch(i + 2));
+      __builtin_amdgcn_sched_barrier(0);
+      comp(B, ch(i + 1));
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    if (i + 1 < n_it) {
+      load(B, ch(i + 1));
+      __builtin_amdgcn_sched_barrier(0);
+      comp(A, ch(i));
+      __builtin_amdgcn_sched_barrier(0);
+      comp(B, ch(i + 1));
+    } else {
+      comp(A, ch(i));
+    }
+  }
+
+  // cross-wave reduction and epilogues of gemm_skinny_kernel: red[w][tile][lane]
+  __shared__ __attribute__((aligned(16))) f32x4_t red[WAVES][NB * MT][64];
+#pragma unroll
+  for (int i = 0; i < NB; ++i)
+#pragma unroll
+    for (int j = 0; j < MT; ++j) red[w][i * MT + j][lane] = acc[i][j];
+  __syncthreads();
+
+  if constexpr (EPI == EPI_SILU) {
+    for (int idx = threadIdx.x; idx < (NB / 2) * MT * 64; idx += 64 * WAVES) {
+      const int l = idx & 63;
+      const int t = idx >> 6;
+      const int j = t % MT, p = t / MT;
+      f32x4_t gs = red[0][(2 * p) * MT + j][l], us = red[0][(2 * p + 1) * MT + j][l];
+#pragma unroll
+      for (int ww = 1; ww < WAVES; ++ww) {
+        gs += red[ww][(2 * p) * MT + j][l];
+        us += red[ww][(2 * p + 1) * MT + j][l];
+      }
+      const int m = j * 16 + (l & 15);
+      if (m < M && 2 * p < cnt) {
+        const int n = ((nb0 + 2 * p) >> 1) * 16 + 4 * (l >> 4);
+        const float sc = epi_row_scale(ep, m);
+        f32x4_t v;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) v[q] = silu(gs[q] * sc) * (us[q] * sc);
+        uint2 pk;  // fragment-major in -> fragment-major out (the down projection's input)
+        pk.x = pack2bf(v[0], v[1]);
+        pk.y = pack2bf(v[2], v[3]);
+        *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(out) + xf_off(m, n, MT)) = pk;
+      }
+    }
+  } else {
+    const size_t slab = (size_t)blockIdx.y * M * ldo;
+    for (int idx = threadIdx.x; idx < NB * MT * 64; idx += 64 * WAVES) {
+      const int l = idx & 63;
+      const int t = idx >> 6;
+      const int j = t % MT, i = t / MT;
+      f32x4_t s = red[0][t][l];
+#pragma unroll
+      for (int ww = 1; ww < WAVES; ++ww) s += red[ww][t][l];
+      const int m = j * 16 + (l & 15);
+      if (m < M && i < cnt) {
+        s *= epi_row_scale(ep, m);
+        const int n = (nb0 + i) * 16 + 4 * (l >> 4);
+        if constexpr (EPI == EPI_F32) {
+          float* o = reinterpret_cast<float*>(out) + slab + (size_t)m * ldo + n;
+          *reinterpret_cast<float4*>(o) = make_float4(s[0], s[1], s[2], s[3]);
+        } else {
+          uint2 pk;
+          pk.x = pack2bf(s[0], s[1]);
+          pk.y = pack2bf(s[2], s[3]);
+          *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(out) + (size_t)m * ldo + n) = pk;
+        }
+      }
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// host launcher
+// ------------------------------------------------------------------------------------------------
+struct Z12Args {
+  const uint16_t* X;
+  int M, KB;
+  const uint2* lo;
+  const uint32_t* hi;
+  const uint32_t* esc;
+  uint32_t base4;
+  int NBtot;
+  void* out;
+  int ldo, splitk, waves, div;
+  LsaEpi ep;
+  hipStream_t s;
+};
+
+template <int NB, int EPI, int WV, int DV>
+static void launch_z12_d(const Z12Args& a) {
+  const int kbps = (a.KB + a.splitk - 1) / a.splitk;
+  dim3 grid((a.NBtot + NB - 1) / NB, a.splitk);  // ragged when NB does not divide NBtot (kernel deals the blocks)
+  hipLaunchKernelGGL((gemm_z12_kernel<NB, EPI, WV, DV>), grid, dim3(64 * WV), 0, a.s, a.X, a.M, a.KB, a.lo, a.hi, a.esc,
+                     a.base4, a.out, a.ldo, kbps, a.ep);
+}
+
+// the (waves, div) -> variant map of gemm.hip's launch_skinny_x
+template <int NB, int EPI>
+static void launch_z12_n(const Z12Args& a) {
+  if constexpr (NB >= 6) {
+    if (a.div == 1) launch_z12_d<NB, EPI, 4, 1>(a);
+    else launch_z12_d<NB, EPI, 4, 2>(a);
+  } else if (a.div == 2) {
+    if (a.waves == 8) launch_z12_d<NB, EPI, 8, 2>(a);
+    else launch_z12_d<NB, EPI, 4, 2>(a);
+  } else if (a.div == 4) {
+    launch_z12_d<NB, EPI, 4, 4>(a);
+  } else {
+    if (a.waves == 8) launch_z12_d<NB, EPI, 8, 1>(a);
+    else launch_z12_d<NB, EPI, 4, 1>(a);
+  }
+}
+
+template <int EPI>
+static int launch_z12_e(const Z12Args& a, int nb) {
+  if (nb == 2) launch_z12_n<2, EPI>(a);
+  else if (nb == 4) launch_z12_n<4, EPI>(a);
+  else if (nb == 6) launch_z12_n<6, EPI>(a);
+  else return -2;
+  return 0;
+}
+
+// X fragment-major (ops.to_xfrag, two row tiles); lo / hi / esc / base: ops.pack_z12 of the [N, K] weight.
+// ep (nullable): row scale only (no residual epilogue).
+extern "C" int lsa_gemm_z12(const void* X, int M, int K, const void* lo, const void* hi, const void* esc, int base, int N,
+                            void* out, int epi, int nb, int splitk, int waves, int div, const LsaEpi* ep,
+                            hipStream_t stream) {
+  if (K % 32 != 0 || N % 16 != 0 || M <= 16 || M > 32) return -1;
+  if (base < 1 || base > 120) return -1;
+  if (ep && (ep->h || ep->xout || ep->ss_out)) return -8;
+  if (epi != EPI_BF16 && epi != EPI_F32 && epi != EPI_SILU) return -4;
+  const int NBtot = N / 16;
+  if (nb != 2 && nb != 4 && nb != 6) return -2;
+  // a ragged grid (nb not dividing the n-blocks) needs >= 1 column unit per workgroup; SiLU units are pairs
+  if (epi == EPI_SILU && NBtot % 2) return -2;
+  if (NBtot % nb != 0 && (epi == EPI_SILU ? NBtot / 2 < (NBtot + nb - 1) / nb : NBtot < (NBtot + nb - 1) / nb))
+    return -2;
+  if (splitk < 1) splitk = 1;
+  if (splitk > K / 32) return -3;
+  if (epi != EPI_F32 && splitk != 1) return -3;
+  Z12Args a;
+  a.X = reinterpret_cast<const uint16_t*>(X);
+  a.M = M;
+  a.KB = K / 32;
+  a.lo = reinterpret_cast<const uint2*>(lo);
+  a.hi = reinterpret_cast<const uint32_t*>(hi);
+  a.esc = reinterpret_cast<const uint32_t*>(esc);
+  a.base4 = (uint32_t)base * 0x01010101u;
+  a.NBtot = NBtot;
+  a.out = out;
+  a.ldo = epi == EPI_SILU ? N / 2 : N;
+  a.splitk = splitk;
+  a.waves = waves == 8 ? 8 : 4;
+  a.div = (div == 1 || div == 2) ? div : 4;
+  a.ep = ep ? *ep : LsaEpi{};
+  a.s = stream;
+  int rc;
+  switch (epi) {
+    case EPI_BF16: rc = launch_z12_e<EPI_BF16>(a, nb); break;
+    case EPI_F32: rc = launch_z12_e<EPI_F32>(a, nb); break;
+    default: rc = launch_z12_e<EPI_SILU>(a, nb); break;
+  }
+  if (rc) return rc;
+  return (int)hipGetLastError();
+}

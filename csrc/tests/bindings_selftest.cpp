@@ -90,6 +90,18 @@ int main() {
     expect_reject("gemm_xf K % 32", [&] { gemm_xf(xf, 20, 48, wf, 128, o, 1, 2, 2, 4, 4, none, 1e-5, none, none, 0, none, none); });
   }
   {
+    // 12-bit weight stream: LO N * K bytes, HI N * K / 2 bytes, ESC 4 words per 16 x 32 fragment
+    auto xf = T({2 * 16 * 64}, BF), lo = T({128 * 64}, U8), hi = T({128 * 32}, U8), esc = T({8 * 2 * 4}, I32);
+    auto o = T({2, 20, 128}, F32);
+    expect_ok("z12_gemm_xf", [&] { z12_gemm_xf(xf, 20, 64, lo, hi, esc, 56, 128, o, 1, 2, 2, 4, 4, none, 1e-5); });
+    expect_reject("z12_gemm_xf M <= 16", [&] { z12_gemm_xf(xf, 16, 64, lo, hi, esc, 56, 128, o, 1, 2, 2, 4, 4, none, 1e-5); });
+    auto hi_small = T({128 * 16}, U8), esc_small = T({8 * 2 * 3}, I32);
+    expect_reject("z12_gemm_xf hi plane", [&] { z12_gemm_xf(xf, 20, 64, lo, hi_small, esc, 56, 128, o, 1, 2, 2, 4, 4, none, 1e-5); });
+    expect_reject("z12_gemm_xf esc records", [&] { z12_gemm_xf(xf, 20, 64, lo, hi, esc_small, 56, 128, o, 1, 2, 2, 4, 4, none, 1e-5); });
+    expect_reject("z12_gemm_xf base", [&] { z12_gemm_xf(xf, 20, 64, lo, hi, esc, 121, 128, o, 1, 2, 2, 4, 4, none, 1e-5); });
+    expect_reject("z12_gemm_xf split-K over K / 32", [&] { z12_gemm_xf(xf, 20, 64, lo, hi, esc, 56, 128, o, 1, 2, 3, 4, 4, none, 1e-5); });
+  }
+  {
     auto xf = T({16 * 128}, BF), wq = T({64 * 128}, U8), sc = T({64}, F32), o = T({1, 4, 64}, F32);
     expect_ok("fp8_gemm_xf", [&] { fp8_gemm_xf(xf, 4, 128, wq, sc, 64, o, 1, 1, 1, 4, 1, none, 1e-5, none, none, 0, none, none); });
     auto wq_bad = T({64 * 127}, U8);

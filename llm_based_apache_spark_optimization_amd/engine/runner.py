@@ -36,6 +36,8 @@ REPEAT_WINDOW = 64  # repetition-penalty ring (Ollama repeat_last_n default; lar
 # it removes (3B 2k TTFT 14.38 vs 14.34 ms, profiles/r5/prefill_norm_free_ab.txt)
 # batch-1 decode with the residual add folded into the next GEMM's prologue (ModelRunner._decode_step_rr)
 RR_DECODE = os.environ.get("LSA_RR", "1") != "0"
+# largest decode bucket whose bf16 GEMMs read the 12-bit weight stream (ModelRunner.z12_max_batch; 0 = off)
+Z12_MAX_BATCH = 32
 
 
 class TPCommError(RuntimeError):
@@ -231,7 +233,11 @@ class ModelRunner:
         # profiles/r3/res_ring_ab_mi355x.txt -- a standalone full-K stream cannot ramp 128-352 KB per CU fast
         # enough with <= 63 KB of LDS-DMA in flight per loader wave; not wired in)
         self.fused_norm_max_batch = 16 if self.d >= 4096 else 0
-        self.res_cfg = None  # experiment hook: (nb, splitk, waves, div) of the norm-free step's o / down GEMMs
+        # 12-bit weight stream (ops.pack_z12, gemm_z12.hip) for the bf16 decode GEMMs and the lm_head of the buckets
+        # 17..z12_max_batch (the kernel covers up to 32 rows); 0 = off.  Same tokens either way: the kernel forms the
+        # bf16 values bit for bit and sums in the bf16 kernel's order.  Read when a step is captured.
+        self.z12_max_batch = Z12_MAX_BATCH
+        self.res_cfg = None # experiment hook: (nb, splitk, waves, div) of the norm-free step's o / down GEMMs
         self.ssq = torch.zeros(2 * self.L + 2, S, dtype=torch.int64, device=dev)  # Q24 fixed point (ops.ss_q24)
         # arrival counters of the split-K residual epilogues (one per 16 output columns; left zeroed)
         self.res_tickets = torch.zeros(max(64, self.d // 16), dtype=torch.int32, device=dev)
@@ -341,12 +347,12 @@ class ModelRunner:
         measured 8-20 % faster GEMMs at B = 32 (scripts/bench_xf.py); bf16 and fp8 weights."""
         return self.on_gpu and 16 < B <= 64 and self.w.layers[0].wqkv.kind in ("bf16", "fp8", "mxfp4")
 
-    def _lm_head(self, xn: torch.Tensor, M: int, xf: bool = False) -> torch.Tensor:
+    def _lm_head(self, xn: torch.Tensor, M: int, xf: bool = False, z12: bool = False) -> torch.Tensor:
         """logits [M, V] (f32) for the normalised rows xn [M, d] (fragment-major when xf)."""
         loc = self.logits_l[:M] if M <= self.max_slots else torch.empty(M, self.Vl, dtype=torch.float32,
                                                                          device=self.device)
         if xf:
-            ops.linear_xf(xn, M, self.w.lm_head, "f32", out=loc, splitk=1)
+            ops.linear_xf(xn, M, self.w.lm_head, "f32", out=loc, splitk=1, z12=z12)
         else:
             ops.linear(xn, self.w.lm_head, "f32", out=loc, splitk=1)
         return self._gather_logits(loc, M)
@@ -418,11 +424,14 @@ class ModelRunner:
         if xf:  # every GEMM input lives in the fragment-major layout, written by its producer
             xn, attn, act = self.xn_f, self.attn_f, self.act_f
 
+            z12 = 16 < B <= self.z12_max_batch
+
             def lin(x, wt, epi, **kw):
-                return ops.linear_xf(x, B, wt, epi, **kw)
+                return ops.linear_xf(x, B, wt, epi, z12=z12, **kw)
         else:
             xn, attn, act = self.xn[:B], self.attn[:B], self.act[:B]
             lin = ops.linear
+            z12 = False
         for l, lw in enumerate(w.layers):
             if l == 0 and raw0:
                 ops.add_rmsnorm(h, lw.attn_norm, self.eps, xn, ids=ids, emb=w.embed, rows=B, xf=xf,
@@ -467,7 +476,7 @@ class ModelRunner:
             else:
                 lin(act, lw.w_down, "f32", out=d_parts, splitk=sk_d)
         ops.add_rmsnorm(h, w.final_norm, self.eps, xn, parts=self._reduce_parts(d_parts), rows=B, xf=xf)
-        self._decode_tail(B, sample, xn, xf, guided)
+        self._decode_tail(B, sample, xn, xf, guided, z12=z12)
 
     def _decode_step_fused(self, B: int, sample: bool, plan: Optional[tuple] = None, guided: bool = False) -> None:
         """Norm-free decode step (TP = 1): 5 launches per layer instead of 7.
@@ -597,8 +606,8 @@ class ModelRunner:
         ops.add_rmsnorm(hs[cur], w.final_norm, self.eps, xn, parts=d_parts, rows=1, write_h=False)
         self._decode_tail(B, sample, xn, False, guided)
 
-    def _decode_tail(self, B: int, sample: bool, xn, xf: bool, guided: bool = False) -> None:
-        logits = self._lm_head(xn, B, xf)
+    def _decode_tail(self, B: int, sample: bool, xn, xf: bool, guided: bool = False, z12: bool = False) -> None:
+        logits = self._lm_head(xn, B, xf, z12)
         if guided:  # -inf into every token that would kill a constrained row's DFA; the commits below run unchanged
             self._dfa_mask(logits, self.gen_len[:B], self.input_ids[:B], self.finished[:B])
         st = (self.out_tokens[:B], self.gen_len[:B], self.input_ids[:B], self.positions[:B], self.finished[:B])

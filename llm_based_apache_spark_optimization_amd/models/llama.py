@@ -96,7 +96,10 @@ def pack_layer(spec: ModelSpec, wq, wk, wv, wo, wg, wu, wd, an, mn, rank=0, tp=1
         wqkv = (wqkv.float() * an.float()[None, :]).to(torch.bfloat16)
         gu = (gu.float() * mn.float()[None, :]).to(torch.bfloat16)
         an, mn = torch.ones_like(an), torch.ones_like(mn)
-    P = ops.PackedWeight.from_dense
+    def P(w, kind):  # bf16 weights of an unsharded model also get their 12-bit stream, one tensor at a time
+        pw = ops.PackedWeight.from_dense(w, kind)
+        return pw.add_z12() if tp == 1 else pw
+
     return LayerWeights(P(wqkv.contiguous(), kind), P(wo_s.contiguous(), kind), P(gu.contiguous(), kind),
                         P(wd_s.contiguous(), kind), an.contiguous(),
                         mn.contiguous(), norms_folded=FOLD_NORMS)
@@ -131,6 +134,8 @@ def init_random(spec: ModelSpec, device="cpu", seed: int = 0, kind: str = "bf16"
     final_norm = ones(d)
     head = embed if spec.tie_embeddings else rnd(spec.vocab_size, d)
     lm_head = ops.PackedWeight.from_dense(_shard_rows(head, tp_rank, tp_size).contiguous(), kind)
+    if tp_size == 1:
+        lm_head.add_z12()
     return LlamaWeights(spec, embed, layers, final_norm, lm_head, tp_rank, tp_size)
 
 
@@ -154,6 +159,8 @@ def from_hf_state_dict(spec: ModelSpec, sd: dict, device="cpu", kind: str = "bf1
     embed = t("model.embed_tokens.weight").contiguous()
     head = embed if (spec.tie_embeddings or "lm_head.weight" not in sd) else t("lm_head.weight")
     lm_head = ops.PackedWeight.from_dense(_shard_rows(head, tp_rank, tp_size).contiguous(), kind)
+    if tp_size == 1:
+        lm_head.add_z12()
     return LlamaWeights(spec, embed, layers, t("model.norm.weight").contiguous(), lm_head, tp_rank, tp_size)
 
 

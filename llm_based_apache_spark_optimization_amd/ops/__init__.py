@@ -191,6 +191,82 @@ def dequantize_mxfp4(wq: torch.Tensor, sw: torch.Tensor, N: int, K: int) -> torc
     return (vals.view(N, K // 32, 32) * scale[..., None]).view(N, K)
 
 
+# "z12": the bf16 values of a weight as a lossless 12-bit stream for the 17-32-row decode GEMM (csrc/kernels/gemm_z12.hip
+# documents the format).  The exponents of a weight matrix sit in a handful of binades, so per tensor one window of 8
+# consecutive values of exp[7:1] (16 binades) covers all but ~1e-4 of the elements; those are patched exactly from a
+# list of up to four entries per 16 x 32 fragment.  784 bytes per fragment instead of 1024.
+# LSA_Z12=0 skips the packing at load (it costs 0.77 x the bf16 bytes on top of them: the bf16 copy stays for prefill and
+# every other bucket).
+Z12 = os.environ.get("LSA_Z12", "1") != "0"
+Z12_WINDOW = 8      # values of exp[7:1] a HI code addresses
+Z12_MAX_ESC = 4     # patch entries per fragment
+
+
+class Z12Planes(NamedTuple):
+    lo: torch.Tensor    # uint8 [N/16, K/32, 64, 8]: byte i = low byte of the lane's element i
+    hi: torch.Tensor    # uint8 [N/16, K/32, 64, 4]: byte j = code(element j) | code(element 4 + j) << 4
+    esc: torch.Tensor   # int32 [N/16, K/32, 4]: valid << 31 | lane << 20 | slot << 16 | bf16 bits
+    base: int           # first exp[7:1] value of the window
+
+    @property
+    def nbytes(self) -> int:
+        return self.lo.numel() + self.hi.numel() + 4 * self.esc.numel()
+
+
+def z12_base(wf: torch.Tensor) -> int:
+    """The window start (1..120) whose 8 consecutive exp[7:1] values cover the most elements (the first such).  Windows
+    never hold exp[7:1] = 0: zeros and values below 2^-125 are always patch entries."""
+    e7 = (wf.reshape(-1).view(torch.int16).to(torch.int32) >> 8) & 0x7F
+    hist = torch.bincount(e7, minlength=128)[:128].to(torch.int64)
+    c = torch.cat([hist.new_zeros(1), hist.cumsum(0)])
+    cover = c[1 + Z12_WINDOW:129] - c[1:129 - Z12_WINDOW]  # cover[b - 1] = sum(hist[b : b + 8]), b = 1..120
+    return int(cover.argmax().item()) + 1
+
+
+def pack_z12(w: torch.Tensor) -> Optional[Z12Planes]:
+    """bf16 weight ([N, K], or already fragment-major as ``shuffle_weight`` returns it) -> its z12 planes, or None when
+    some fragment has more than four elements outside the tensor's window (not compressible: the weight keeps only its
+    bf16 copy and kernel)."""
+    wf = shuffle_weight(w) if w.dim() == 2 else w
+    assert wf.dtype == torch.bfloat16 and wf[0, 0].numel() == 512, (wf.dtype, wf.shape)
+    NB, KB = wf.shape[:2]
+    wf = wf.reshape(NB, KB, 64, 8)
+    base = z12_base(wf)
+    bits = wf.contiguous().view(torch.int16).to(torch.int32) & 0xFFFF
+    hb = bits >> 8
+    e7 = hb & 0x7F
+    out = (e7 < base) | (e7 >= base + Z12_WINDOW)
+    if int(out.sum(dim=(2, 3)).max().item()) > Z12_MAX_ESC:
+        return None
+    code = torch.where(out, torch.zeros_like(hb), ((hb >> 7) << 3) | (e7 - base))  # filler: +, first binade pair
+    lo = (bits & 0xFF).to(torch.uint8)
+    hi = (code[..., :4] | (code[..., 4:] << 4)).to(torch.uint8)
+    esc = torch.zeros(NB * KB, Z12_MAX_ESC, dtype=torch.int64, device=wf.device)
+    idx = out.nonzero()  # row-major order: a fragment's entries by (lane, slot)
+    if idx.shape[0]:
+        f = idx[:, 0] * KB + idx[:, 1]
+        first = torch.searchsorted(f, f)  # f is sorted: the first entry of each fragment
+        rank = torch.arange(f.numel(), device=f.device) - first
+        val = bits[idx[:, 0], idx[:, 1], idx[:, 2], idx[:, 3]].to(torch.int64)
+        esc[f, rank] = (1 << 31) | (idx[:, 2] << 20) | (idx[:, 3] << 16) | val
+    esc = torch.where(esc >= (1 << 31), esc - (1 << 32), esc).to(torch.int32)
+    return Z12Planes(lo.contiguous(), hi.contiguous(), esc.view(NB, KB, Z12_MAX_ESC).contiguous(), base)
+
+
+def unpack_z12(z: Z12Planes) -> torch.Tensor:
+    """z12 planes -> the fragment-major bf16 tensor [N/16, K/32, 64, 8], formed the way the kernel forms it: high byte
+    (c & 8) << 4 | ((c & 7) + base) over the low byte, then the valid patch entries."""
+    hi = z.hi.to(torch.int32)
+    code = torch.cat([hi & 0xF, hi >> 4], dim=-1)
+    bits = ((((code & 8) << 4) | ((code & 7) + z.base)) << 8) | z.lo.to(torch.int32)
+    e = z.esc.to(torch.int64) & 0xFFFFFFFF
+    at = (e >> 31).nonzero()
+    if at.shape[0]:
+        ev = e[at[:, 0], at[:, 1], at[:, 2]]
+        bits[at[:, 0], at[:, 1], (ev >> 20) & 63, (ev >> 16) & 7] = (ev & 0xFFFF).to(torch.int32)
+    return torch.where(bits >= 0x8000, bits - 0x10000, bits).to(torch.int16).view(torch.bfloat16)
+
+
 @dataclasses.dataclass
 class PackedWeight:
     """A linear layer's weight in the layout its kernel streams."""
@@ -201,6 +277,14 @@ class PackedWeight:
     data: torch.Tensor
     scale: Optional[torch.Tensor] = None
     requested: Optional[str] = None  # "dense" only: the kind the weight was packed for (the CPU keeps every kind dense)
+    z12: Optional[Z12Planes] = None  # "bf16" only: the same values as a 12-bit stream (linear_xf at 17-32 rows)
+
+    def add_z12(self) -> "PackedWeight":
+        """Attach the z12 companion of a GPU bf16 weight (a no-op for other kinds, under LSA_Z12=0, and for tensors that
+        are not compressible)."""
+        if Z12 and self.kind == "bf16" and self.z12 is None:
+            self.z12 = pack_z12(self.data)
+        return self
 
     @staticmethod
     def from_dense(w: torch.Tensor, kind: str = "bf16") -> "PackedWeight":
@@ -730,11 +814,14 @@ def from_xfrag(xf: torch.Tensor, M: int, K: int) -> torch.Tensor:
 
 def linear_xf(xf: torch.Tensor, M: int, w: PackedWeight, epi: str = "bf16", out: Optional[torch.Tensor] = None,
               splitk: Optional[int] = None, nb: Optional[int] = None, waves: Optional[int] = None,
-              div: Optional[int] = None, rownorm=None, res=None) -> torch.Tensor:
+              div: Optional[int] = None, rownorm=None, res=None, z12: bool = False) -> torch.Tensor:
     """``linear`` with the activations in the fragment-major layout (``to_xfrag``), M <= 64, bf16 or fp8 weights.
     epi='silu' writes its [M, N/2] output in the fragment-major layout too (the next GEMM's input);
     for that epilogue ``out`` is a flat buffer of at least xfrag_tiles(M) * 16 * N/2 elements.
-    epi='res' writes its bf16 copy of the residual in the fragment-major layout."""
+    epi='res' writes its bf16 copy of the residual in the fragment-major layout.
+    ``z12``: the caller allows the 12-bit weight stream (gemm_z12.hip) where the weight has one and 16 < M <= 32; same
+    values, same summation order, fewer bytes.  A weight without it (not compressible) runs the bf16 kernel, as does
+    a shape whose ':z12' tuning entry says "off" (measured slower) unless the call names its own ``nb``."""
     if not _gpu(xf) or w.kind not in ("bf16", "fp8", "mxfp4"):
         if epi != "silu":
             return linear(from_xfrag(xf, M, w.K), w, epi, out, splitk, nb, waves, div, rownorm, res, _xf=True)
@@ -744,21 +831,32 @@ def linear_xf(xf: torch.Tensor, M: int, w: PackedWeight, epi: str = "bf16", out:
         out.view(-1)[: y.numel()].copy_(y)
         return out
     nb0, sk0, wv0, dv0 = pick_gemm_config(M, w.N, w.K, epi, xf=True, kind=w.kind)
+    z12 = z12 and w.kind == "bf16" and w.z12 is not None and 16 < M <= 32 and epi in ("bf16", "f32", "silu")
+    if z12:  # ':z12' entries: the bf16 pick's (splitk, waves, div) -- the summation order -- with their own nb
+        e = _tuning_table().get(f"{w.N}x{w.K}:{epi}:b32:z12")
+        if e is not None and e.get("off"):
+            z12 = nb is not None
+        elif e is not None:
+            nb0, sk0, wv0, dv0 = e["nb"], e["splitk"], e["waves"], e["div"]
     nb = nb0 if nb is None else nb
     splitk = sk0 if splitk is None else splitk
     waves = wv0 if waves is None else waves
     div = dv0 if div is None else div
+    z12 = z12 and nb in (2, 4, 6)
     if epi == "res":
         splitk, out = _res_split(res, splitk, out, M, w.N, xf.device)
     if out is None:
         if epi == "f32":
             out = torch.empty(splitk, M, w.N, device=xf.device, dtype=torch.float32)
-        elif epi == "silu":
-            out = torch.zeros(xfrag_tiles(M) * 16 * (w.N // 2), device=xf.device, dtype=torch.bfloat16)
+        elif epi == "silu":  # whole 32-column k-steps of the fragment-major output
+            out = torch.zeros(xfrag_tiles(M) * 16 * (-(-(w.N // 2) // 32) * 32), device=xf.device, dtype=torch.bfloat16)
         else:
             out = torch.empty(M, w.N, device=xf.device, dtype=torch.bfloat16)
     kw = _epi_kw(rownorm, res, xfrag_tiles(M))
-    if w.kind == "fp8":
+    if z12:
+        z = w.z12
+        ext().z12_gemm_xf(xf, M, w.K, z.lo, z.hi, z.esc, z.base, w.N, out, EPI[epi], nb, splitk, waves, div, **kw)
+    elif w.kind == "fp8":
         ext().fp8_gemm_xf(xf, M, w.K, w.data, w.scale, w.N, out, EPI[epi], nb, splitk, waves, _fp8_depth(div), **kw)
     elif w.kind == "mxfp4":
         ext().fp4_gemm_xf(xf, M, w.K, w.data, w.scale, w.N, out, EPI[epi], nb, splitk, waves, **kw)
