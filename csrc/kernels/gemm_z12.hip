@@ -9,12 +9,15 @@
 //                                    start of the 8-value window of exp[7:1] (16 binades) that covers most elements
 //   ESC [N/16][K/32][4] u32          up to four exact patches per fragment for elements outside the window (zeros,
 //                                    outliers): valid << 31 | lane << 20 | slot << 16 | bf16 bits
-// A wave loads LO (8 B per lane), HI (4 B per lane) and the fragment's ESC record (lane l its entry l & 3: a vector load,
-// so the record arrives in order with the planes and waiting for it does not wait for the next chunk's, as a scalar
-// load's out-of-order counter would; the entries are read back with v_readlane under a ballot), rebuilds exactly the
-// uint4 gemm_skinny_kernel would have loaded, and issues the same MFMAs: the work split (chunks of U k-steps dealt
-// round-robin to the waves of a split-K range), the accumulation order, the cross-wave reduction and the epilogues are
-// gemm.hip's, so at equal (nb, splitk, waves, div) the output is bit-identical to the bf16 kernel's.
+// A wave loads LO (8 B per lane) and HI (4 B per lane) of each fragment and, once per k-step, the ESC records of all its
+// NB fragments (lane l entry l & 3 of fragment min(l >> 2, NB - 1): a vector load, so the records arrive in order with
+// the planes and waiting for them does not wait for the next chunk's, as a scalar load's out-of-order counter would;
+// one ballot per k-step, nibble i of it says whether fragment i has patches, and the entries are read back with
+// v_readlane at lanes 4 i .. 4 i + 3: 2 NB + 3 vector loads per k-step, 15 at nb 6, where a record load per fragment
+// made 20), rebuilds exactly the uint4 gemm_skinny_kernel would have loaded, and issues the same MFMAs: the work split
+// (chunks of U k-steps dealt round-robin to the waves of a split-K range), the accumulation order, the cross-wave
+// reduction and the epilogues are gemm.hip's, so at equal (nb, splitk, waves, div) the output is bit-identical to the
+// bf16 kernel's.
 //
 // Fragment-major activations (ops.to_xfrag) and two row tiles (MT = 2) only; epilogues bf16, f32 slabs, SiLU(gate)*up.
 #include "common.h"
@@ -101,11 +104,13 @@ __global__ __launch_bounds__(64 * WAVES) void gemm_z12_kernel(const uint16_t* __
   size_t fb[NB];  // first record of n-block i (blocks >= cnt re-read the workgroup's last block and are never stored)
 #pragma unroll
   for (int i = 0; i < NB; ++i) fb[i] = (size_t)(nb0 + min(i, cnt - 1)) * KB;
+  // this lane's patch entry: entry lane & 3 of the record of fragment min(lane >> 2, NB - 1), n-block as in fb[]
+  const uint32_t* escp = Esc + (size_t)(nb0 + min(min(lane >> 2, NB - 1), cnt - 1)) * KB * 4 + (lane & 3);
 
   struct Chunk {
     uint2 lo[U][NB];
     uint32_t hi[U][NB];
-    uint32_t esc[U][NB];  // lane l holds entry l & 3 of the fragment's record
+    uint32_t esc[U];  // lanes 4 i .. 4 i + 3 hold the record of fragment i
     uint4 x[U][MT];
   };
   auto load = [&](Chunk& c, int ci) {
@@ -118,8 +123,8 @@ __global__ __launch_bounds__(64 * WAVES) void gemm_z12_kernel(const uint16_t* __
         const size_t f = fb[i] + kk;
         c.lo[u][i] = ldg_nt2(Lo + f * 64 + lane);
         c.hi[u][i] = ldg_nt1(Hi + f * 64 + lane);
-        c.esc[u][i] = Esc[f * 4 + (lane & 3)];
       }
+      c.esc[u] = escp[(size_t)kk * 4];
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -135,15 +140,19 @@ __global__ __launch_bounds__(64 * WAVES) void gemm_z12_kernel(const uint16_t* __
       const bool live = (kb + u) < kbB;
       uint4 wv[NB];
 #pragma unroll
-      for (int i = 0; i < NB; ++i) {
-        wv[i] = z12_decode(c.lo[u][i], c.hi[u][i], base4);
-        const uint32_t e = c.esc[u][i];
-        if (__builtin_amdgcn_ballot_w64((e >> 31) != 0u)) {  // wave-uniform, rare
-          z12_patch1(wv[i], __builtin_amdgcn_readlane(e, 0), lane);
-          z12_patch1(wv[i], __builtin_amdgcn_readlane(e, 1), lane);
-          z12_patch1(wv[i], __builtin_amdgcn_readlane(e, 2), lane);
-          z12_patch1(wv[i], __builtin_amdgcn_readlane(e, 3), lane);
-        }
+      for (int i = 0; i < NB; ++i) wv[i] = z12_decode(c.lo[u][i], c.hi[u][i], base4);
+      const uint32_t e = c.esc[u];
+      // nibble i: the valid bits of fragment i's four entries (lanes >= 4 NB repeat the last record: masked off)
+      const uint64_t pm = __builtin_amdgcn_ballot_w64((e >> 31) != 0u) & ((1ull << (4 * NB)) - 1ull);
+      if (pm) {  // wave-uniform, rare
+#pragma unroll
+        for (int i = 0; i < NB; ++i)
+          if ((pm >> (4 * i)) & 15ull) {
+            z12_patch1(wv[i], __builtin_amdgcn_readlane(e, 4 * i + 0), lane);
+            z12_patch1(wv[i], __builtin_amdgcn_readlane(e, 4 * i + 1), lane);
+            z12_patch1(wv[i], __builtin_amdgcn_readlane(e, 4 * i + 2), lane);
+            z12_patch1(wv[i], __builtin_amdgcn_readlane(e, 4 * i + 3), lane);
+          }
       }
 #pragma unroll
       for (int j = 0; j < MT; ++j) {
@@ -158,8 +167,9 @@ __global__ __launch_bounds__(64 * WAVES) void gemm_z12_kernel(const uint16_t* __
   auto ch = [&](int i) { return w + WAVES * i; };
 
   // gemm.hip's two-deep register pipeline with the peeled tail.  sched_barrier(0) pins the issue order: a chunk's loads
-  // all leave before the previous chunk's decode and MFMAs; nothing is requested that is not used.  (A third chunk in
-  // flight measured slower or equal on every 7B shape and was removed, ARCHITECTURE.md section 4.)
+  // all leave before the previous chunk's decode and MFMAs; nothing is requested that is not used.  (Three and four
+  // chunks in flight, with counted vmcnt waits, measured equal or slower on every 7B shape and slower inside the decode
+  // step, and were removed, ARCHITECTURE.md section 4.)
   Chunk A, B;
   if (n_it > 0) {
     load(A, ch(0));
