@@ -251,6 +251,13 @@ __device__ __forceinline__ float silu(float x) { return x / (1.0f + __expf(-x));
 //  * EPI_RES (splitk 1): h[m][n] += y (f32 residual, row stride ldh); xout = bf16(h) (fragment-major
 //    with xmt row tiles when xmt > 0, else row-major [M][ldh]) for the next GEMM; ss_out[m] += sum over
 //    this workgroup's columns of h^2 (one device-scope float atomic per row and workgroup).
+//
+// GEMM epilogue modes, shared by every GEMM file and the host callers' `epi` argument:
+//   EPI_BF16 -> bf16 [M, N];  EPI_F32 -> f32 [splitk][M][N];  EPI_SILU -> bf16 [M, N/2] = silu(gate) * up, gate /
+//   up rows interleaved per 16;  EPI_RES -> the residual epilogue above.
+#define EPI_BF16 0
+#define EPI_F32 1
+#define EPI_SILU 2
 #define EPI_RES 3
 
 // Row sums of squares travel as Q24 fixed point in int64: integer atomics add exactly, so the sum (and every

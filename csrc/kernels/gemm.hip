@@ -3,59 +3,15 @@
 // Weights live in the "fragment-major" layout produced by ops.shuffle_weight():
 //     Wf[nb][kb][lane][8 bf16]  with  nb = n / 16, kb = k / 32, lane = 16 * ((k % 32) / 8) + n % 16
 // i.e. one 1 KiB MFMA A-fragment (16 rows x 32 k) per (nb, kb), lane-linear.  Every weight load
-// is therefore a fully coalesced 1 KiB wave-instruction (global_load_dwordx4) and, in the tiled
-// kernel, a lane-linear global_load_lds_dwordx4 whose LDS image is read back with conflict-free
-// ds_read_b128 at lane*16 (no swizzle needed: cdna_hip_programming.md §5 Caveat / rule 21).
+// is therefore a fully coalesced 1 KiB wave-instruction (global_load_dwordx4).
 //
-// Two kernels:
-//   * gemm_skinny  — decode (M <= 64).  Memory-bound weight stream: 8 waves/WG split K, each wave
-//     keeps 16 x 1 KiB weight fragments in flight straight into VGPRs (no LDS round trip, the
-//     'GEMV / M <= 16 decode weights' row of the guide), non-temporal weight loads, cross-wave
-//     reduction through LDS, fused epilogues (bf16 store, f32 split-K slab for the following
-//     residual+RMSNorm kernel, SiLU(gate)*up for the interleaved gate_up projection).
-//   * gemm_tile    — prefill (M > 64) when the 256^2 kernel (gemm_tile256.hip) would under-fill the
-//     chip.  128x128x64 LDS tile, both operands staged by global_load_lds (16 B), double-buffered,
-//     4 waves of 64x64.
-//
-// Epilogue modes: EPI_BF16 -> bf16 [M, N];  EPI_F32 -> f32 [splitk][M][N];
-//                 EPI_SILU -> bf16 [M, N/2] = silu(gate) * up, gate/up rows interleaved per 16.
-#include "common.h"
-
-#define EPI_BF16 0
-#define EPI_F32 1
-#define EPI_SILU 2
-
-
-template <int EPI>
-__device__ __forceinline__ void store4(void* out, int ldo, size_t slab, int m, int n, f32x4_t v) {
-  if constexpr (EPI == EPI_F32) {
-    float* o = reinterpret_cast<float*>(out) + slab + (size_t)m * ldo + n;
-    *reinterpret_cast<float4*>(o) = make_float4(v[0], v[1], v[2], v[3]);
-  } else {
-    uint16_t* o = reinterpret_cast<uint16_t*>(out) + (size_t)m * ldo + n;
-    uint2 p;
-    p.x = pack2bf(v[0], v[1]);
-    p.y = pack2bf(v[2], v[3]);
-    *reinterpret_cast<uint2*>(o) = p;
-  }
-}
-
-
-// ------------------------------------------------------------------------------------------------
-// decode / small-M kernel
-//
-// Work split: workgroup = 8 waves over NB n-blocks (16 rows each) and one split-K range; the range is
-// cut into chunks of U k-steps dealt round-robin to the waves.  Each wave streams its chunks with a
-// two-deep register pipeline: chunk i+1's NB*U weight fragments (+ the activation fragments) are in
-// flight while chunk i's MFMAs run, so the memory pipe never drains between chunks.  Out-of-range
-// k-steps are clamped (duplicate L2 hits) and masked by zeroing the activation fragment, never by a
-// per-load branch (which would force vmcnt(0) per element).
-// ------------------------------------------------------------------------------------------------
-template <int MT, int NB, int DIV = 1>
-struct SkinnyCfg {
-  static constexpr int U0 = (16 / (NB > 2 * MT ? NB : 2 * MT)) < 2 ? 2 : (16 / (NB > 2 * MT ? NB : 2 * MT));
-  static constexpr int U = (U0 / DIV) < 1 ? 1 : (U0 / DIV);
-};
+// gemm_skinny — decode (M <= 64; prefill runs gemm_tile256.hip).  Memory-bound weight stream: 4 or 8 waves per
+// workgroup split K, each wave keeps its chunk's 1 KiB weight fragments in flight straight into VGPRs (no LDS round
+// trip, the 'GEMV / M <= 16 decode weights' row of the guide), non-temporal weight loads.  The work split, the
+// two-deep pipeline (peeled tail), the cross-wave reduction and the fused epilogues (bf16 store, f32 split-K slab
+// for the following residual+RMSNorm kernel, SiLU(gate)*up for the interleaved gate_up projection, residual) are
+// gemm_skinny.h's; this file has the bf16 fragment loads, the MFMAs and the residual-reduce prologue.
+#include "gemm_skinny.h"
 
 // XF: X is in the fragment-major activation layout Xf[k/32][MT][64 lanes][8 bf16] (ops.to_xfrag,
 // written directly by the producing kernels in the decode path), so an activation fragment is one
@@ -79,11 +35,8 @@ __global__ __launch_bounds__(64 * WAVES) void gemm_skinny_kernel(const uint16_t*
   const int r = lane & 15, g = lane >> 4;
   int nb0, cnt;  // this workgroup's n-blocks (ragged grids: common.h skinny_nblocks)
   skinny_nblocks<NB, EPI == EPI_SILU ? 2 : 1>(EPI == EPI_SILU ? ldo / 8 : ldo / 16, nb0, cnt);
-  const int kbA = blockIdx.y * kb_per_split;
-  const int kbB = min(KB, kbA + kb_per_split);
-  const int nk = kbB - kbA;
-  const int nch = (nk + U - 1) / U;                     // chunks in this split
-  const int n_it = nch > w ? (nch - w + WAVES - 1) / WAVES : 0;  // chunks of this wave
+  const SkinnySplit ks = skinny_split<U, WAVES>(KB, kb_per_split, w);
+  const int kbA = ks.kbA, kbB = ks.kbB, n_it = ks.n_it;
 
   f32x4_t acc[NB][MT];
 #pragma unroll
@@ -118,8 +71,9 @@ __global__ __launch_bounds__(64 * WAVES) void gemm_skinny_kernel(const uint16_t*
       for (int i = 0; i < NB; ++i) wr[u][i] = ldg_nt(wp[i] + (size_t)kk * 64);
     }
   };
-  // RR: the workgroup's X slice as bf16 (k - kbA * 32), filled by the prologue below
-  __shared__ __attribute__((aligned(16))) uint4 xs[RR ? RR_KMAX / 8 : 1];
+  // RR: the workgroup's X slice as bf16 (k - kbA * 32), filled by the prologue below (the widest alignment of the
+  // kernel's LDS arrays: placed first, so the k-step reads address it without an offset)
+  __shared__ __attribute__((aligned(32))) uint4 xs[RR ? RR_KMAX / 8 : 1];
   auto xload = [&](uint4 (&xr)[U][MT], int c) {
     const int kb = kbA + c * U;
 #pragma unroll
@@ -138,11 +92,16 @@ __global__ __launch_bounds__(64 * WAVES) void gemm_skinny_kernel(const uint16_t*
       }
     }
   };
-  auto load = [&](uint4 (&wr)[U][NB], uint4 (&xr)[U][MT], int c) {
-    wload(wr, c);
-    xload(xr, c);
+  struct Chunk {
+    uint4 w[U][NB], x[U][MT];
   };
-  auto comp = [&](const uint4 (&wr)[U][NB], const uint4 (&xr)[U][MT], int c) {
+  auto load = [&](Chunk& ch, int c) {
+    wload(ch.w, c);
+    xload(ch.x, c);
+  };
+  auto comp = [&](const Chunk& ch, int c) {
+    const uint4(&wr)[U][NB] = ch.w;
+    const uint4(&xr)[U][MT] = ch.x;
     const int kb = kbA + c * U;
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -162,11 +121,11 @@ __global__ __launch_bounds__(64 * WAVES) void gemm_skinny_kernel(const uint16_t*
   // slice's sum of squares.  The first weight chunk is requested before it (it does not depend on X), so the
   // prologue's L2 round trip overlaps the weight stream's HBM latency.
   float rr_scale = 1.f;
-  uint4 wA[U][NB], xA[U][MT], wB[U][NB], xB[U][MT];
+  Chunk A, B;
   if constexpr (RR > 0) {
-    if (n_it > 0) wload(wA, w);
+    if (n_it > 0) wload(A.w, w);
     __shared__ float rr_red[WAVES];
-    const int k0 = kbA * 32, n8 = nk * 4;  // 8-value groups of the slice
+    const int k0 = kbA * 32, n8 = ks.nk * 4;  // 8-value groups of the slice
     const bool wr_h = blockIdx.x == 0;
     float ssl = 0.f;
     for (int i = threadIdx.x; i < n8; i += 64 * WAVES) {
@@ -203,130 +162,12 @@ __global__ __launch_bounds__(64 * WAVES) void gemm_skinny_kernel(const uint16_t*
     for (int ww = 0; ww < WAVES; ++ww) tot += rr_red[ww];
     if (rr.local) rr_scale = rsqrtf(tot * rr.inv_k + rr.eps);
     else if (wr_h && threadIdx.x == 0) atomicAdd(reinterpret_cast<unsigned long long*>(rr.ss_out), (unsigned long long)ss_to_q24(tot));
-    if (n_it > 0) xload(xA, w);
+    if (n_it > 0) xload(A.x, w);
   } else {
-    if (n_it > 0) load(wA, xA, w);
+    if (n_it > 0) load(A, w);
   }
-  if (n_it > 0) {
-    int i = 0;
-    // sched_barrier(0) pins the issue order: the next chunk's loads all leave before this chunk's
-    // MFMAs (hipcc otherwise interleaves them and keeps only ~8 loads in flight).  The last iteration is
-    // peeled: the steady-state loop always has a chunk i + 2 to request, and the tail requests nothing it does
-    // not use (an even chunk count used to re-request its last chunk, weights and activations, and drop it:
-    // one load in eight of the o projection's at batch 32).
-    for (; i + 2 < n_it; i += 2) {
-      load(wB, xB, w + WAVES * (i + 1));
-      __builtin_amdgcn_sched_barrier(0);
-      comp(wA, xA, w + WAVES * i);
-      __builtin_amdgcn_sched_barrier(0);
-      load(wA, xA, w + WAVES * (i + 2));
-      __builtin_amdgcn_sched_barrier(0);
-      comp(wB, xB, w + WAVES * (i + 1));
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    if (i + 1 < n_it) {
-      load(wB, xB, w + WAVES * (i + 1));
-      __builtin_amdgcn_sched_barrier(0);
-      comp(wA, xA, w + WAVES * i);
-      __builtin_amdgcn_sched_barrier(0);
-      comp(wB, xB, w + WAVES * (i + 1));
-    } else {
-      comp(wA, xA, w + WAVES * i);
-    }
-  }
-
-  // cross-wave reduction: red[w][tile][lane]
-  __shared__ __attribute__((aligned(16))) f32x4_t red[WAVES][NB * MT][64];
-  __shared__ unsigned long long ssw[16 * MT];  // EPI_RES: per-row sum of h^2 over this workgroup's columns (Q24)
-#pragma unroll
-  for (int i = 0; i < NB; ++i)
-#pragma unroll
-    for (int j = 0; j < MT; ++j) red[w][i * MT + j][lane] = acc[i][j];
-  if constexpr (EPI == EPI_RES) {
-    if (threadIdx.x < 16 * MT) ssw[threadIdx.x] = 0ull;
-  }
-  __syncthreads();
-
-  if constexpr (EPI == EPI_SILU) {
-    for (int idx = threadIdx.x; idx < (NB / 2) * MT * 64; idx += 64 * WAVES) {
-      const int l = idx & 63;
-      const int t = idx >> 6;
-      const int j = t % MT, p = t / MT;
-      f32x4_t gs = red[0][(2 * p) * MT + j][l], us = red[0][(2 * p + 1) * MT + j][l];
-#pragma unroll
-      for (int ww = 1; ww < WAVES; ++ww) {
-        gs += red[ww][(2 * p) * MT + j][l];
-        us += red[ww][(2 * p + 1) * MT + j][l];
-      }
-      const int m = j * 16 + (l & 15);
-      if (m < M && 2 * p < cnt) {
-        const int n = ((nb0 + 2 * p) >> 1) * 16 + 4 * (l >> 4);
-        const float sc = epi_row_scale(ep, m) * rr_scale;
-        f32x4_t v;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) v[q] = silu(gs[q] * sc) * (us[q] * sc);
-        if constexpr (XF) {  // fragment-major in -> fragment-major out (the down projection's input)
-          uint2 pk;
-          pk.x = pack2bf(v[0], v[1]);
-          pk.y = pack2bf(v[2], v[3]);
-          *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(out) + xf_off(m, n, MT)) = pk;
-        } else {
-          store4<EPI_SILU>(out, ldo, 0, m, n, v);
-        }
-      }
-    }
-  } else {
-    const size_t slab = (size_t)blockIdx.y * M * ldo;
-    if constexpr (EPI == EPI_RES) {
-      if (gridDim.y > 1) {  // split-K: publish, ticket, the last split finishes the column
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(out, 0, 0x7fffffff, 0x00020000);
-        for (int idx = threadIdx.x; idx < NB * MT * 64; idx += 64 * WAVES) {
-          const int l = idx & 63, t = idx >> 6;
-          const int j = t % MT, i = t / MT;
-          f32x4_t s = red[0][t][l];
-#pragma unroll
-          for (int ww = 1; ww < WAVES; ++ww) s += red[ww][t][l];
-          const int m = j * 16 + (l & 15);
-          if (m < M && i < cnt) res_store_partial(rs, slab + (size_t)m * ldo + (nb0 + i) * 16 + 4 * (l >> 4), s);
-        }
-        __shared__ int s_last;
-        if (!res_publish_and_ticket<64 * WAVES>(ep, &s_last)) return;
-        for (int idx = threadIdx.x; idx < NB * MT * 64; idx += 64 * WAVES) {
-          const int l = idx & 63, t = idx >> 6;
-          const int j = t % MT, i = t / MT;
-          const int m = j * 16 + (l & 15);
-          if (m < M && i < cnt) {
-            const int n = (nb0 + i) * 16 + 4 * (l >> 4);
-            atomicAdd(&ssw[m], (unsigned long long)ss_to_q24(
-                epi_residual4(ep, m, n, res_slab_sum(rs, (size_t)m * ldo + n, (size_t)M * ldo, gridDim.y) *
-                                        epi_row_scale(ep, m))));
-          }
-        }
-        __syncthreads();
-        if (threadIdx.x < M) atomicAdd(reinterpret_cast<unsigned long long*>(ep.ss_out) + threadIdx.x, ssw[threadIdx.x]);
-        return;
-      }
-    }
-    for (int idx = threadIdx.x; idx < NB * MT * 64; idx += 64 * WAVES) {
-      const int l = idx & 63;
-      const int t = idx >> 6;
-      const int j = t % MT, i = t / MT;
-      f32x4_t s = red[0][t][l];
-#pragma unroll
-      for (int ww = 1; ww < WAVES; ++ww) s += red[ww][t][l];
-      const int m = j * 16 + (l & 15);
-      if (m < M && i < cnt) {
-        s *= epi_row_scale(ep, m) * rr_scale;
-        const int n = (nb0 + i) * 16 + 4 * (l >> 4);
-        if constexpr (EPI == EPI_RES) atomicAdd(&ssw[m], (unsigned long long)ss_to_q24(epi_residual4(ep, m, n, s)));
-        else store4<EPI>(out, ldo, slab, m, n, s);
-      }
-    }
-    if constexpr (EPI == EPI_RES) {
-      __syncthreads();
-      if (threadIdx.x < M) atomicAdd(reinterpret_cast<unsigned long long*>(ep.ss_out) + threadIdx.x, ssw[threadIdx.x]);
-    }
-  }
+  if (n_it > 0) skinny_pipe_peeled<WAVES>(A, B, w, n_it, load, comp);
+  skinny_epilogue<MT, NB, EPI, WAVES, XF, false, (RR > 0)>(acc, w, lane, M, nb0, cnt, out, ldo, ep, nullptr, rr_scale);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -346,24 +187,11 @@ static void launch_skinny_x(const uint16_t* X, int ldx, int M, int KB, const uin
                             int ldo, int splitk, hipStream_t s) {
   const int kbps = (KB + splitk - 1) / splitk;
   dim3 grid((NBtot + NB - 1) / NB, splitk);  // ragged when NB does not divide NBtot (kernel deals the blocks)
-#define LSA_SKL(WV, DV) \
-  hipLaunchKernelGGL((gemm_skinny_kernel<MT, NB, EPI, WV, DV, XF, RR>), grid, dim3(64 * WV), 0, s, X, \
-                     ldx, M, KB, Wf, out, ldo, kbps, g_epi, g_rr)
-  if constexpr (NB >= 6) {
-    // wide n-groups (one activation fragment feeds NB weight fragments): 4 waves only, the cross-wave
-    // reduction buffer is WAVES * NB * MT KiB
-    if (g_skinny_div == 1) LSA_SKL(4, 1);
-    else LSA_SKL(4, 2);
-  } else if (g_skinny_div == 2) {
-    if (g_skinny_waves == 8) LSA_SKL(8, 2);
-    else LSA_SKL(4, 2);
-  } else if (g_skinny_div == 4) {
-    LSA_SKL(4, 4);
-  } else {
-    if (g_skinny_waves == 8) LSA_SKL(8, 1);
-    else LSA_SKL(4, 1);
-  }
-#undef LSA_SKL
+  skinny_variant<NB>(g_skinny_waves, g_skinny_div, [&](auto wv, auto dv) {
+    constexpr int WV = decltype(wv)::value, DV = decltype(dv)::value;
+    hipLaunchKernelGGL((gemm_skinny_kernel<MT, NB, EPI, WV, DV, XF, RR>), grid, dim3(64 * WV), 0, s, X, ldx, M, KB, Wf,
+                       out, ldo, kbps, g_epi, g_rr);
+  });
 }
 
 static thread_local int g_xfrag = 0;
@@ -431,10 +259,7 @@ extern "C" int lsa_gemm_ex(const void* X, int ldx, int M, int K, const void* Wf,
   if (M <= 64) {
     if (nb <= 0) nb = 1;
     if (epi == EPI_SILU && nb < 2) nb = 2;
-    // a ragged grid (nb not dividing the n-blocks) needs >= 1 column unit per workgroup; SiLU units are pairs
-    if (NBtot % nb != 0 && (epi == EPI_SILU ? (nb % 2 || NBtot % 2 || NBtot / 2 < (NBtot + nb - 1) / nb)
-                                              : NBtot < (NBtot + nb - 1) / nb))
-      return -2;
+    if (!skinny_grid_ok(NBtot, nb, epi == EPI_SILU)) return -2;
     if (splitk < 1) splitk = 1;
     if (epi != EPI_F32 && epi != EPI_RES && splitk != 1) return -3;
     if (M > 32 && nb > 2) nb = 2;

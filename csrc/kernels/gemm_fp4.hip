@@ -12,14 +12,10 @@
 // Scales: S[nb][kb128 / 4][lane][4 B] -- the lane's E8M0 byte of four consecutive 128-k steps in one word.
 // Dequantisation in registers: v_cvt_scalef32_pk_bf16_fp4 (2 nibbles -> 2 bf16, times the block's 2^(e - 127),
 // exact: an e2m1 value times a power of two is a bf16 value), one VALU op per 2 weights.
-// Epilogues as gemm.hip / gemm_fp8.hip: bf16, f32 split-K slabs, SiLU * up (gate / up rows interleaved per 16),
-// the norm-free decode extensions (LsaEpi row scale / residual).  Prefill (M > 64) dequantises the layer into a
-// bf16 fragment-layout scratch (lsa_fp4_dequant) for the 256^2 tile GEMM.
-#include "common.h"
-
-#define EPI_BF16 0
-#define EPI_F32 1
-#define EPI_SILU 2
+// Work split, pipeline (clamped tail), reduction and epilogues: gemm_skinny.h -- bf16, f32 split-K slabs, SiLU * up
+// (gate / up rows interleaved per 16), the norm-free decode extensions (LsaEpi row scale / residual).  Prefill
+// (M > 64) dequantises the layer into a bf16 fragment-layout scratch (lsa_fp4_dequant) for the 256^2 tile GEMM.
+#include "gemm_skinny.h"
 
 namespace {
 
@@ -44,18 +40,15 @@ __global__ __launch_bounds__(64 * WAVES) void gemm_fp4_skinny_kernel(const uint1
                                                                      const uint32_t* __restrict__ Sw,
                                                                      void* __restrict__ out, int ldo, int kb_per_split,
                                                                      LsaEpi ep) {
-  // chunks of U 128-k steps round-robin over the waves, two-deep register pipeline pinned with sched_barrier(0)
+  // chunks of U 128-k steps
   const int lane = threadIdx.x & 63;
   const int w = threadIdx.x >> 6;
   const int r = lane & 15, g = lane >> 4;
   int nb0, cnt;  // this workgroup's n-blocks (ragged grids: common.h skinny_nblocks)
   skinny_nblocks<NB, EPI == EPI_SILU ? 2 : 1>(EPI == EPI_SILU ? ldo / 8 : ldo / 16, nb0, cnt);
-  const int kbA = blockIdx.y * kb_per_split;
-  const int kbB = min(KB128, kbA + kb_per_split);
-  const int nk = kbB - kbA;
-  const int nch = (nk + U - 1) / U;
-  const int n_it = nch > w ? (nch - w + WAVES - 1) / WAVES : 0;
-  const int last_c = w + WAVES * (n_it - 1);
+  const SkinnySplit ks = skinny_split<U, WAVES>(KB128, kb_per_split, w);
+  const int kbA = ks.kbA, kbB = ks.kbB;
+  const int last_c = w + WAVES * (ks.n_it - 1);  // this wave's last chunk: the clamped pipeline's bound (gemm_skinny.h)
   const int KB4 = (KB128 + 3) >> 2;
 
   f32x4_t acc[NB][MT];
@@ -82,7 +75,14 @@ __global__ __launch_bounds__(64 * WAVES) void gemm_fp4_skinny_kernel(const uint1
     sp[i] = Sw + (size_t)(nb0 + min(i, cnt - 1)) * KB4 * 64 + lane;
   }
 
-  auto load = [&](uint4 (&wr)[U][NB], uint32_t (&sr)[U][NB], uint4 (&xr)[U][MT][4], int c) {
+  struct Chunk {
+    uint4 w[U][NB], x[U][MT][4];
+    uint32_t s[U][NB];
+  };
+  auto load = [&](Chunk& ch, int c) {
+    uint4(&wr)[U][NB] = ch.w;
+    uint32_t(&sr)[U][NB] = ch.s;
+    uint4(&xr)[U][MT][4] = ch.x;
     const int kb = kbA + c * U;
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -109,7 +109,10 @@ __global__ __launch_bounds__(64 * WAVES) void gemm_fp4_skinny_kernel(const uint1
       }
     }
   };
-  auto comp = [&](const uint4 (&wr)[U][NB], const uint32_t (&sr)[U][NB], const uint4 (&xr)[U][MT][4], int c) {
+  auto comp = [&](const Chunk& ch, int c) {
+    const uint4(&wr)[U][NB] = ch.w;
+    const uint32_t(&sr)[U][NB] = ch.s;
+    const uint4(&xr)[U][MT][4] = ch.x;
     const int kb = kbA + c * U;
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -128,117 +131,12 @@ __global__ __launch_bounds__(64 * WAVES) void gemm_fp4_skinny_kernel(const uint1
       }
     }
   };
-  if (n_it > 0) {
-    uint4 wA[U][NB], xA[U][MT][4], wB[U][NB], xB[U][MT][4];
-    uint32_t sA[U][NB], sB[U][NB];
-    load(wA, sA, xA, w);
-    int i = 0;
-    for (; i + 1 < n_it; i += 2) {
-      load(wB, sB, xB, w + WAVES * (i + 1));
-      __builtin_amdgcn_sched_barrier(0);
-      comp(wA, sA, xA, w + WAVES * i);
-      __builtin_amdgcn_sched_barrier(0);
-      load(wA, sA, xA, min(w + WAVES * (i + 2), last_c));
-      __builtin_amdgcn_sched_barrier(0);
-      comp(wB, sB, xB, w + WAVES * (i + 1));
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    if (i < n_it) comp(wA, sA, xA, w + WAVES * i);
+  if (ks.n_it > 0) {
+    Chunk A, B;
+    load(A, w);
+    skinny_pipe_clamped<WAVES>(A, B, w, ks.n_it, last_c, load, comp);
   }
-
-  __shared__ __attribute__((aligned(16))) f32x4_t red[WAVES][NB * MT][64];
-  __shared__ unsigned long long ssw[16 * MT];  // EPI_RES: per-row sum of h^2 over this workgroup's columns (Q24)
-#pragma unroll
-  for (int i = 0; i < NB; ++i)
-#pragma unroll
-    for (int j = 0; j < MT; ++j) red[w][i * MT + j][lane] = acc[i][j];
-  if constexpr (EPI == EPI_RES) {
-    if (threadIdx.x < 16 * MT) ssw[threadIdx.x] = 0ull;
-  }
-  __syncthreads();
-
-  if constexpr (EPI == EPI_SILU) {
-    for (int idx = threadIdx.x; idx < (NB / 2) * MT * 64; idx += 64 * WAVES) {
-      const int l = idx & 63, t = idx >> 6;
-      const int j = t % MT, p = t / MT;
-      f32x4_t gs = red[0][(2 * p) * MT + j][l], us = red[0][(2 * p + 1) * MT + j][l];
-#pragma unroll
-      for (int ww = 1; ww < WAVES; ++ww) {
-        gs += red[ww][(2 * p) * MT + j][l];
-        us += red[ww][(2 * p + 1) * MT + j][l];
-      }
-      const int m = j * 16 + (l & 15);
-      if (m < M && 2 * p < cnt) {
-        const int n = ((nb0 + 2 * p) >> 1) * 16 + 4 * (l >> 4);
-        const float sc = epi_row_scale(ep, m);
-        float v[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) v[q] = silu(gs[q] * sc) * (us[q] * sc);
-        uint2 pk;
-        pk.x = pack2bf(v[0], v[1]);
-        pk.y = pack2bf(v[2], v[3]);
-        *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(out) + (XF ? xf_off(m, n, MT) : (size_t)m * ldo + n)) = pk;
-      }
-    }
-  } else {
-    const size_t slab = (size_t)blockIdx.y * M * ldo;
-    if constexpr (EPI == EPI_RES) {
-      if (gridDim.y > 1) {  // split-K: publish, ticket, the last split finishes the column (gemm.hip)
-        const __amdgpu_buffer_rsrc_t rsc = __builtin_amdgcn_make_buffer_rsrc(out, 0, 0x7fffffff, 0x00020000);
-        for (int idx = threadIdx.x; idx < NB * MT * 64; idx += 64 * WAVES) {
-          const int l = idx & 63, t = idx >> 6;
-          const int j = t % MT, i = t / MT;
-          f32x4_t s = red[0][t][l];
-#pragma unroll
-          for (int ww = 1; ww < WAVES; ++ww) s += red[ww][t][l];
-          const int m = j * 16 + (l & 15);
-          if (m < M && i < cnt) res_store_partial(rsc, slab + (size_t)m * ldo + (nb0 + i) * 16 + 4 * (l >> 4), s);
-        }
-        __shared__ int s_last;
-        if (!res_publish_and_ticket<64 * WAVES>(ep, &s_last)) return;
-        for (int idx = threadIdx.x; idx < NB * MT * 64; idx += 64 * WAVES) {
-          const int l = idx & 63, t = idx >> 6;
-          const int j = t % MT, i = t / MT;
-          const int m = j * 16 + (l & 15);
-          if (m < M && i < cnt) {
-            const int n = (nb0 + i) * 16 + 4 * (l >> 4);
-            atomicAdd(&ssw[m], (unsigned long long)ss_to_q24(
-                epi_residual4(ep, m, n, res_slab_sum(rsc, (size_t)m * ldo + n, (size_t)M * ldo, gridDim.y) *
-                                        epi_row_scale(ep, m))));
-          }
-        }
-        __syncthreads();
-        if (threadIdx.x < M) atomicAdd(reinterpret_cast<unsigned long long*>(ep.ss_out) + threadIdx.x, ssw[threadIdx.x]);
-        return;
-      }
-    }
-    for (int idx = threadIdx.x; idx < NB * MT * 64; idx += 64 * WAVES) {
-      const int l = idx & 63, t = idx >> 6;
-      const int j = t % MT, i = t / MT;
-      f32x4_t s = red[0][t][l];
-#pragma unroll
-      for (int ww = 1; ww < WAVES; ++ww) s += red[ww][t][l];
-      const int m = j * 16 + (l & 15);
-      if (m >= M || i >= cnt) continue;
-      const int n = (nb0 + i) * 16 + 4 * (l >> 4);
-      s *= epi_row_scale(ep, m);
-      if constexpr (EPI == EPI_RES) {
-        atomicAdd(&ssw[m], (unsigned long long)ss_to_q24(epi_residual4(ep, m, n, s)));
-      } else if constexpr (EPI == EPI_F32) {
-        *reinterpret_cast<float4*>(reinterpret_cast<float*>(out) + slab + (size_t)m * ldo + n) =
-            make_float4(s[0], s[1], s[2], s[3]);
-      } else {
-        uint2 pk;
-        pk.x = pack2bf(s[0], s[1]);
-        pk.y = pack2bf(s[2], s[3]);
-        *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(out) + (size_t)m * ldo + n) = pk;
-      }
-    }
-    if constexpr (EPI == EPI_RES) {
-      __syncthreads();
-      if (threadIdx.x < M) atomicAdd(reinterpret_cast<unsigned long long*>(ep.ss_out) + threadIdx.x, ssw[threadIdx.x]);
-    }
-  }
+  skinny_epilogue<MT, NB, EPI, WAVES, XF>(acc, w, lane, M, nb0, cnt, out, ldo, ep);
 }
 
 // mxfp4 [nb][kb128][lane][16 B] + scales -> bf16 fragment layout [nb][kb32][lane][8] (ops.shuffle_weight)
@@ -324,10 +222,7 @@ extern "C" int lsa_fp4_gemm_ex(const void* X, int ldx, int M, int K, const void*
   const int ldo = (epi == EPI_SILU) ? N / 2 : N;
   if (nb <= 0) nb = 1;
   if (epi == EPI_SILU && nb < 2) nb = 2;
-  // a ragged grid (nb not dividing the n-blocks) needs >= 1 column unit per workgroup; SiLU units are pairs
-  if (NBtot % nb != 0 && (epi == EPI_SILU ? (nb % 2 || NBtot % 2 || NBtot / 2 < (NBtot + nb - 1) / nb)
-                                            : NBtot < (NBtot + nb - 1) / nb))
-    return -2;
+  if (!skinny_grid_ok(NBtot, nb, epi == EPI_SILU)) return -2;
   if (splitk < 1) splitk = 1;
   if (epi != EPI_F32 && epi != EPI_RES && splitk != 1) return -3;
   if (M > 32 && nb > 2) nb = 2;

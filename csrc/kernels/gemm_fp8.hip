@@ -8,8 +8,9 @@
 // (one VALU op per 2 weights, far below the HBM-bound budget), per-output-channel scale in the epilogue.
 // Decode therefore streams half the bytes of the bf16 path.  For prefill (M > 64) the layer is
 // dequantised (lsa_fp8_dequant) into a bf16 fragment-layout scratch buffer owned by the caller
-// and run through gemm_tile.
-#include "common.h"
+// and run through the bf16 tile GEMM.  Work split, pipeline (clamped tail), reduction and epilogues: gemm_skinny.h,
+// the epilogues with the per-channel scale policy.
+#include "gemm_skinny.h"
 
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 
@@ -23,10 +24,6 @@ __device__ __forceinline__ void fp8x16_to_bf16(const uint4 q, uint4& a, uint4& b
   b.x = cvt2<false>(q.z); b.y = cvt2<true>(q.z); b.z = cvt2<false>(q.w); b.w = cvt2<true>(q.w);
 }
 
-#define EPI_BF16 0
-#define EPI_F32 1
-#define EPI_SILU 2
-
 // XF: X in the fragment-major decode layout (common.h xf_off): lane (r, g)'s 16 activations
 // k = 64 kb64 + 16 g .. +15 are the two 16-B pieces (g' = 2 (g & 1), g' + 1) of bf16 k-step 2 kb64 + g / 2
 template <int MT, int NB, int EPI, int WAVES, int U, bool XF = false>
@@ -35,18 +32,14 @@ __global__ __launch_bounds__(64 * WAVES) void gemm_fp8_skinny_kernel(const uint1
                                                                      const float* __restrict__ wscale,
                                                                      void* __restrict__ out, int ldo, int kb_per_split,
                                                                      LsaEpi ep) {
-  // same work split as gemm_skinny_kernel: chunks of U k64-steps round-robin over the waves, two-deep
-  // register pipeline pinned with sched_barrier(0)
+  // chunks of U k64-steps
   const int lane = threadIdx.x & 63;
   const int w = threadIdx.x >> 6;
   const int r = lane & 15, g = lane >> 4;
-  const int nb0 = blockIdx.x * NB;
-  const int kbA = blockIdx.y * kb_per_split;
-  const int kbB = min(KB64, kbA + kb_per_split);
-  const int nk = kbB - kbA;
-  const int nch = (nk + U - 1) / U;
-  const int n_it = nch > w ? (nch - w + WAVES - 1) / WAVES : 0;
-  const int last_c = w + WAVES * (n_it - 1);
+  const int nb0 = blockIdx.x * NB;  // exact grids only (the host rejects a ragged one)
+  const SkinnySplit ks = skinny_split<U, WAVES>(KB64, kb_per_split, w);
+  const int kbA = ks.kbA, kbB = ks.kbB;
+  const int last_c = w + WAVES * (ks.n_it - 1);  // this wave's last chunk: the clamped pipeline's bound (gemm_skinny.h)
 
   f32x4_t acc[NB][MT];
 #pragma unroll
@@ -70,7 +63,12 @@ __global__ __launch_bounds__(64 * WAVES) void gemm_fp8_skinny_kernel(const uint1
 #pragma unroll
   for (int i = 0; i < NB; ++i) wp[i] = Wq + (size_t)(nb0 + i) * KB64 * 64 + lane;
 
-  auto load = [&](uint4 (&wr)[U][NB], uint4 (&xr)[U][MT][2], int c) {
+  struct Chunk {
+    uint4 w[U][NB], x[U][MT][2];
+  };
+  auto load = [&](Chunk& ch, int c) {
+    uint4(&wr)[U][NB] = ch.w;
+    uint4(&xr)[U][MT][2] = ch.x;
     const int kb = kbA + c * U;
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -97,7 +95,9 @@ __global__ __launch_bounds__(64 * WAVES) void gemm_fp8_skinny_kernel(const uint1
       }
     }
   };
-  auto comp = [&](const uint4 (&wr)[U][NB], const uint4 (&xr)[U][MT][2], int c) {
+  auto comp = [&](const Chunk& ch, int c) {
+    const uint4(&wr)[U][NB] = ch.w;
+    const uint4(&xr)[U][MT][2] = ch.x;
     const int kb = kbA + c * U;
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -123,125 +123,12 @@ __global__ __launch_bounds__(64 * WAVES) void gemm_fp8_skinny_kernel(const uint1
       }
     }
   };
-  if (n_it > 0) {
-    uint4 wA[U][NB], xA[U][MT][2], wB[U][NB], xB[U][MT][2];
-    load(wA, xA, w);
-    int i = 0;
-    for (; i + 1 < n_it; i += 2) {
-      load(wB, xB, w + WAVES * (i + 1));
-      __builtin_amdgcn_sched_barrier(0);
-      comp(wA, xA, w + WAVES * i);
-      __builtin_amdgcn_sched_barrier(0);
-      load(wA, xA, min(w + WAVES * (i + 2), last_c));
-      __builtin_amdgcn_sched_barrier(0);
-      comp(wB, xB, w + WAVES * (i + 1));
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    if (i < n_it) comp(wA, xA, w + WAVES * i);
+  if (ks.n_it > 0) {
+    Chunk A, B;
+    load(A, w);
+    skinny_pipe_clamped<WAVES>(A, B, w, ks.n_it, last_c, load, comp);
   }
-
-  __shared__ __attribute__((aligned(16))) f32x4_t red[WAVES][NB * MT][64];
-  __shared__ unsigned long long ssw[16 * MT];  // EPI_RES: per-row sum of h^2 over this workgroup's columns (Q24)
-#pragma unroll
-  for (int i = 0; i < NB; ++i)
-#pragma unroll
-    for (int j = 0; j < MT; ++j) red[w][i * MT + j][lane] = acc[i][j];
-  if constexpr (EPI == EPI_RES) {
-    if (threadIdx.x < 16 * MT) ssw[threadIdx.x] = 0ull;
-  }
-  __syncthreads();
-
-  if constexpr (EPI == EPI_SILU) {
-    for (int idx = threadIdx.x; idx < (NB / 2) * MT * 64; idx += 64 * WAVES) {
-      const int l = idx & 63, t = idx >> 6;
-      const int j = t % MT, p = t / MT;
-      f32x4_t gs = red[0][(2 * p) * MT + j][l], us = red[0][(2 * p + 1) * MT + j][l];
-#pragma unroll
-      for (int ww = 1; ww < WAVES; ++ww) {
-        gs += red[ww][(2 * p) * MT + j][l];
-        us += red[ww][(2 * p + 1) * MT + j][l];
-      }
-      const int m = j * 16 + (l & 15);
-      if (m < M) {
-        const int nrow_g = (nb0 + 2 * p) * 16 + 4 * (l >> 4);
-        const int nrow_u = nrow_g + 16;
-        const int n = ((nb0 + 2 * p) >> 1) * 16 + 4 * (l >> 4);
-        uint2 pk;
-        float v[4];
-        const float sc = epi_row_scale(ep, m);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) v[q] = silu(gs[q] * (sc * wscale[nrow_g + q])) * (us[q] * (sc * wscale[nrow_u + q]));
-        pk.x = pack2bf(v[0], v[1]);
-        pk.y = pack2bf(v[2], v[3]);
-        // fragment-major in -> fragment-major out (the down projection's input)
-        *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(out) + (XF ? xf_off(m, n, MT) : (size_t)m * ldo + n)) = pk;
-      }
-    }
-  } else {
-    const size_t slab = (size_t)blockIdx.y * M * ldo;
-    if constexpr (EPI == EPI_RES) {
-      if (gridDim.y > 1) {  // split-K: publish (channel-scaled), ticket, the last split finishes the column
-        const __amdgpu_buffer_rsrc_t rsc = __builtin_amdgcn_make_buffer_rsrc(out, 0, 0x7fffffff, 0x00020000);
-        for (int idx = threadIdx.x; idx < NB * MT * 64; idx += 64 * WAVES) {
-          const int l = idx & 63, t = idx >> 6;
-          const int j = t % MT, i = t / MT;
-          f32x4_t s = red[0][t][l];
-#pragma unroll
-          for (int ww = 1; ww < WAVES; ++ww) s += red[ww][t][l];
-          const int m = j * 16 + (l & 15);
-          if (m >= M) continue;
-          const int n = (nb0 + i) * 16 + 4 * (l >> 4);
-          const float4 sc = *reinterpret_cast<const float4*>(wscale + n);
-          s[0] *= sc.x; s[1] *= sc.y; s[2] *= sc.z; s[3] *= sc.w;
-          res_store_partial(rsc, slab + (size_t)m * ldo + n, s);
-        }
-        __shared__ int s_last;
-        if (!res_publish_and_ticket<64 * WAVES>(ep, &s_last)) return;
-        for (int idx = threadIdx.x; idx < NB * MT * 64; idx += 64 * WAVES) {
-          const int l = idx & 63, t = idx >> 6;
-          const int j = t % MT, i = t / MT;
-          const int m = j * 16 + (l & 15);
-          if (m < M) {
-            const int n = (nb0 + i) * 16 + 4 * (l >> 4);
-            atomicAdd(&ssw[m], (unsigned long long)ss_to_q24(
-                epi_residual4(ep, m, n, res_slab_sum(rsc, (size_t)m * ldo + n, (size_t)M * ldo, gridDim.y) *
-                                        epi_row_scale(ep, m))));
-          }
-        }
-        __syncthreads();
-        if (threadIdx.x < M) atomicAdd(reinterpret_cast<unsigned long long*>(ep.ss_out) + threadIdx.x, ssw[threadIdx.x]);
-        return;
-      }
-    }
-    for (int idx = threadIdx.x; idx < NB * MT * 64; idx += 64 * WAVES) {
-      const int l = idx & 63, t = idx >> 6;
-      const int j = t % MT, i = t / MT;
-      f32x4_t s = red[0][t][l];
-#pragma unroll
-      for (int ww = 1; ww < WAVES; ++ww) s += red[ww][t][l];
-      const int m = j * 16 + (l & 15);
-      if (m >= M) continue;
-      const int n = (nb0 + i) * 16 + 4 * (l >> 4);
-      const float4 sc = *reinterpret_cast<const float4*>(wscale + n);
-      const float rs = epi_row_scale(ep, m);
-      s[0] *= sc.x * rs; s[1] *= sc.y * rs; s[2] *= sc.z * rs; s[3] *= sc.w * rs;
-      if constexpr (EPI == EPI_RES) {
-        atomicAdd(&ssw[m], (unsigned long long)ss_to_q24(epi_residual4(ep, m, n, s)));
-      } else if constexpr (EPI == EPI_F32) {
-        *reinterpret_cast<float4*>(reinterpret_cast<float*>(out) + slab + (size_t)m * ldo + n) =
-            make_float4(s[0], s[1], s[2], s[3]);
-      } else {
-        uint2 pk;
-        pk.x = pack2bf(s[0], s[1]);
-        pk.y = pack2bf(s[2], s[3]);
-        *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(out) + (size_t)m * ldo + n) = pk;
-      }
-    }
-    if constexpr (EPI == EPI_RES) {
-      __syncthreads();
-      if (threadIdx.x < M) atomicAdd(reinterpret_cast<unsigned long long*>(ep.ss_out) + threadIdx.x, ssw[threadIdx.x]);
-    }
-  }
+  skinny_epilogue<MT, NB, EPI, WAVES, XF, true>(acc, w, lane, M, nb0, NB, out, ldo, ep, wscale);
 }
 
 // fp8 [nb][kb64][lane][16] -> bf16 fragment layout [nb][kb32][lane][8] with the channel scale applied

@@ -6,9 +6,10 @@
 // per fp4 byte) through L2 and the VALU conversion sits in every k-step.  Here the activations are e4m3 and the
 // weights go to the matrix core in their stored format -- e4m3 (WK 0) or MXFP4 e2m1 (WK 1, the weight's own E8M0
 // block scales as the MFMA's A scale operand) -- so one MFMA consumes a 16 x 128 weight slab and a 16 x 128
-// activation slab: half the activation bytes, no conversion VALU, a quarter of the MFMA issues.  Same work split as
-// the skinny kernels: chunks of U k128-steps dealt round-robin to the waves, split-K over blockIdx.y, a two-deep
-// register pipeline pinned with sched_barrier, cross-wave reduction through LDS.
+// activation slab: half the activation bytes, no conversion VALU, a quarter of the MFMA issues.  The work split
+// (chunks of U k128-steps) and the cross-wave reduction are gemm_skinny.h's; the two-deep pipeline (clamped tail, the
+// form of gemm_skinny.h, see below why not its code) and the epilogues (sx row scales, the WK switch, the quantising
+// e4m3 SiLU output) are this file's own.
 //
 // Activations ("xf8", common.h xf8_off): X8[kb128][MT][lane][32 B], lane (g, r) holds row 16 mt + r at k = 128 s + 16 g
 // .. +15 and 128 s + 64 + 16 g .. +15 -- the K order the matrix core reads an 8-bit operand in (measured,
@@ -29,10 +30,7 @@
 // as e4m3 in the xf8 layout with one E8M0 scale per (row, 32 columns) for a W8A8 / W4A8 down projection (NB a
 // multiple of 4: a workgroup's column pairs (2 c, 2 c + 1) are exactly one 32-column block; the block amax
 // through LDS).  The rownorm extension (LsaEpi.rowss) multiplies a row scale in like the other decode GEMMs.
-#include "common.h"
-
-#define EPI_F32 1
-#define EPI_SILU 2
+#include "gemm_skinny.h"
 
 typedef int a8_i32x8_t __attribute__((ext_vector_type(8)));
 
@@ -76,11 +74,8 @@ __global__ __launch_bounds__(64 * WAVES) void gemm_a8_skinny_kernel(const uint4*
   const int r = lane & 15, g = lane >> 4;
   int nb0, cnt;  // this workgroup's n-blocks (ragged grids: common.h skinny_nblocks)
   skinny_nblocks<NB, EPI == EPI_SILU ? 2 : 1>(EPI == EPI_SILU ? ldo / 8 : ldo / 16, nb0, cnt);
-  const int kbA = blockIdx.y * kb_per_split;
-  const int kbB = min(KB128, kbA + kb_per_split);
-  const int nk = kbB - kbA;
-  const int nch = (nk + U - 1) / U;
-  const int n_it = nch > w ? (nch - w + WAVES - 1) / WAVES : 0;
+  const SkinnySplit ks = skinny_split<U, WAVES>(KB128, kb_per_split, w);
+  const int kbA = ks.kbA, kbB = ks.kbB, nk = ks.nk, n_it = ks.n_it;
   const int last_c = w + WAVES * (n_it - 1);
   const int KB4 = (KB128 + 3) >> 2;
 
@@ -231,6 +226,9 @@ __global__ __launch_bounds__(64 * WAVES) void gemm_a8_skinny_kernel(const uint4*
   } else {
     if (n_it > 0) load(wA, saA, xA, sbA, w);
   }
+  // gemm_skinny.h's clamped pipeline, kept as this kernel's own copy over separate register arrays: through the shared
+  // driver (one struct per chunk) hipcc waits for each E8M0 scale word of the first chunk before it requests the next
+  // fragment, and the batch-1 W4A8 gate_up (7B, nb 4, e4m3 output) measured 12.3 -> 13.1 us
   if (n_it > 0) {
     int i = 0;
     for (; i + 1 < n_it; i += 2) {
@@ -246,13 +244,9 @@ __global__ __launch_bounds__(64 * WAVES) void gemm_a8_skinny_kernel(const uint4*
     if (i < n_it) comp(wA, saA, xA, sbA, w + WAVES * i);
   }
 
-  __shared__ __attribute__((aligned(16))) f32x4_t red[WAVES][NB * MT][64];
+  auto& red = skinny_red_store<WAVES>(acc, w, lane);
   constexpr int NBLK = (XFO == 2 && NB >= 4) ? NB / 4 : 1;  // 32-column blocks of a SiLU workgroup
   __shared__ uint32_t bmax[16 * MT][NBLK];                   // their per-row amax (float bits, >= 0)
-#pragma unroll
-  for (int i = 0; i < NB; ++i)
-#pragma unroll
-    for (int j = 0; j < MT; ++j) red[w][i * MT + j][lane] = acc[i][j];
   if constexpr (XFO == 2) {
     for (int t = threadIdx.x; t < 16 * MT * NBLK; t += 64 * WAVES) (&bmax[0][0])[t] = 0u;
   }
@@ -262,12 +256,8 @@ __global__ __launch_bounds__(64 * WAVES) void gemm_a8_skinny_kernel(const uint4*
     for (int idx = threadIdx.x; idx < (NB / 2) * MT * 64; idx += 64 * WAVES) {
       const int l = idx & 63, t = idx >> 6;
       const int j = t % MT, p = t / MT;
-      f32x4_t gs = red[0][(2 * p) * MT + j][l], us = red[0][(2 * p + 1) * MT + j][l];
-#pragma unroll
-      for (int ww = 1; ww < WAVES; ++ww) {
-        gs += red[ww][(2 * p) * MT + j][l];
-        us += red[ww][(2 * p + 1) * MT + j][l];
-      }
+      f32x4_t gs, us;
+      tile_sum2(red, (2 * p) * MT + j, (2 * p + 1) * MT + j, l, gs, us);
       const int m = j * 16 + (l & 15);
       if (m < M && 2 * p < cnt) {
         const int nrow_g = (nb0 + 2 * p) * 16 + 4 * (l >> 4);
@@ -315,9 +305,7 @@ __global__ __launch_bounds__(64 * WAVES) void gemm_a8_skinny_kernel(const uint4*
     for (int idx = threadIdx.x; idx < NB * MT * 64; idx += 64 * WAVES) {
       const int l = idx & 63, t = idx >> 6;
       const int j = t % MT, i = t / MT;
-      f32x4_t s = red[0][t][l];
-#pragma unroll
-      for (int ww = 1; ww < WAVES; ++ww) s += red[ww][t][l];
+      const f32x4_t s = tile_sum(red, t, l);
       const int m = j * 16 + (l & 15);
       if (m >= M || i >= cnt) continue;
       const int n = (nb0 + i) * 16 + 4 * (l >> 4);
@@ -443,10 +431,7 @@ extern "C" int lsa_a8_gemm(const void* X8, const void* s8, const float* sx, int 
   if (nb <= 0) nb = 2;
   if (epi == EPI_SILU && nb < 2) nb = 2;
   if (M > 32 && nb > 2 && !(epi == EPI_SILU && xfo == 2 && nb == 4)) nb = 2;
-  // a ragged grid (nb not dividing the n-blocks) needs >= 1 column unit per workgroup; SiLU units are pairs
-  if (NBtot % nb != 0 && (epi == EPI_SILU ? (nb % 2 || NBtot % 2 || NBtot / 2 < (NBtot + nb - 1) / nb)
-                                            : NBtot < (NBtot + nb - 1) / nb))
-    return -2;
+  if (!skinny_grid_ok(NBtot, nb, epi == EPI_SILU)) return -2;
   // the e4m3 SiLU output: every workgroup holds whole 32-column blocks (nb a multiple of 4, no ragged tail)
   if (epi == EPI_SILU && xfo == 2 && (nb % 4 || NBtot % nb || !out_s8)) return -9;
   if (splitk < 1) splitk = 1;

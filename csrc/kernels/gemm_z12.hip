@@ -14,17 +14,13 @@
 // the planes and waiting for them does not wait for the next chunk's, as a scalar load's out-of-order counter would;
 // one ballot per k-step, nibble i of it says whether fragment i has patches, and the entries are read back with
 // v_readlane at lanes 4 i .. 4 i + 3: 2 NB + 3 vector loads per k-step, 15 at nb 6, where a record load per fragment
-// made 20), rebuilds exactly the uint4 gemm_skinny_kernel would have loaded, and issues the same MFMAs: the work split
-// (chunks of U k-steps dealt round-robin to the waves of a split-K range), the accumulation order, the cross-wave
-// reduction and the epilogues are gemm.hip's, so at equal (nb, splitk, waves, div) the output is bit-identical to the
-// bf16 kernel's.
+// made 20), rebuilds exactly the uint4 gemm_skinny_kernel would have loaded, and issues the same MFMAs.  The chunk depth
+// (SkinnyCfg), the work split, the peeled two-deep pipeline, the cross-wave reduction and the epilogues are the code of
+// gemm_skinny.h that gemm_skinny_kernel runs too, so at equal (nb, splitk, waves, div) the output is bit-identical to
+// the bf16 kernel's.
 //
 // Fragment-major activations (ops.to_xfrag) and two row tiles (MT = 2) only; epilogues bf16, f32 slabs, SiLU(gate)*up.
-#include "common.h"
-
-#define EPI_BF16 0
-#define EPI_F32 1
-#define EPI_SILU 2
+#include "gemm_skinny.h"
 
 typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
 
@@ -61,13 +57,6 @@ __device__ __forceinline__ void z12_patch1(uint4& w, const uint32_t e, const int
   w.w = (mine && d == 3u) ? ((w.w & keep) | ins) : w.w;
 }
 
-// chunk depth of gemm.hip's SkinnyCfg (the k-step -> (split, wave, order) assignment must be the bf16 kernel's)
-template <int MT, int NB, int DIV>
-struct Z12Cfg {
-  static constexpr int U0 = (16 / (NB > 2 * MT ? NB : 2 * MT)) < 2 ? 2 : (16 / (NB > 2 * MT ? NB : 2 * MT));
-  static constexpr int U = (U0 / DIV) < 1 ? 1 : (U0 / DIV);
-};
-
 template <int NB, int EPI, int WAVES, int DIV>
 __global__ __launch_bounds__(64 * WAVES) void gemm_z12_kernel(const uint16_t* __restrict__ X, int M, int KB,
                                                               const uint2* __restrict__ Lo,
@@ -76,17 +65,14 @@ __global__ __launch_bounds__(64 * WAVES) void gemm_z12_kernel(const uint16_t* __
                                                               void* __restrict__ out, int ldo, int kb_per_split,
                                                               LsaEpi ep) {
   constexpr int MT = 2;
-  constexpr int U = Z12Cfg<MT, NB, DIV>::U;
+  constexpr int U = SkinnyCfg<MT, NB, DIV>::U;
   const int lane = threadIdx.x & 63;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform: chunk indices stay scalar
   const int r = lane & 15;
   int nb0, cnt;  // this workgroup's n-blocks (ragged grids: common.h skinny_nblocks)
   skinny_nblocks<NB, EPI == EPI_SILU ? 2 : 1>(EPI == EPI_SILU ? ldo / 8 : ldo / 16, nb0, cnt);
-  const int kbA = blockIdx.y * kb_per_split;
-  const int kbB = min(KB, kbA + kb_per_split);
-  const int nk = kbB - kbA;
-  const int nch = (nk + U - 1) / U;                               // chunks in this split
-  const int n_it = nch > w ? (nch - w + WAVES - 1) / WAVES : 0;  // chunks of this wave
+  const SkinnySplit ks = skinny_split<U, WAVES>(KB, kb_per_split, w);
+  const int kbA = ks.kbA, kbB = ks.kbB;
 
   f32x4_t acc[NB][MT];
 #pragma unroll
@@ -164,94 +150,15 @@ __global__ __launch_bounds__(64 * WAVES) void gemm_z12_kernel(const uint16_t* __
       }
     }
   };
-  auto ch = [&](int i) { return w + WAVES * i; };
 
-  // gemm.hip's two-deep register pipeline with the peeled tail.  sched_barrier(0) pins the issue order: a chunk's loads
-  // all leave before the previous chunk's decode and MFMAs; nothing is requested that is not used.  (Three and four
-  // chunks in flight, with counted vmcnt waits, measured equal or slower on every 7B shape and slower inside the decode
-  // step, and were removed, ARCHITECTURE.md section 4.)
-  Chunk A, B;
-  if (n_it > 0) {
-    load(A, ch(0));
-    int i = 0;
-    for (; i + 2 < n_it; i += 2) {
-      load(B, ch(i + 1));
-      __builtin_amdgcn_sched_barrier(0);
-      comp(A, ch(i));
-      __builtin_amdgcn_sched_barrier(0);
-      load(A, ch(i + 2));
-      __builtin_amdgcn_sched_barrier(0);
-      comp(B, ch(i + 1));
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    if (i + 1 < n_it) {
-      load(B, ch(i + 1));
-      __builtin_amdgcn_sched_barrier(0);
-      comp(A, ch(i));
-      __builtin_amdgcn_sched_barrier(0);
-      comp(B, ch(i + 1));
-    } else {
-      comp(A, ch(i));
-    }
+  // Two chunks in flight.  (Three and four, with counted vmcnt waits, measured equal or slower on every 7B shape and
+  // slower inside the decode step, and were removed, ARCHITECTURE.md section 4.)
+  if (ks.n_it > 0) {
+    Chunk A, B;
+    load(A, w);
+    skinny_pipe_peeled<WAVES>(A, B, w, ks.n_it, load, comp);
   }
-
-  // cross-wave reduction and epilogues of gemm_skinny_kernel: red[w][tile][lane]
-  __shared__ __attribute__((aligned(16))) f32x4_t red[WAVES][NB * MT][64];
-#pragma unroll
-  for (int i = 0; i < NB; ++i)
-#pragma unroll
-    for (int j = 0; j < MT; ++j) red[w][i * MT + j][lane] = acc[i][j];
-  __syncthreads();
-
-  if constexpr (EPI == EPI_SILU) {
-    for (int idx = threadIdx.x; idx < (NB / 2) * MT * 64; idx += 64 * WAVES) {
-      const int l = idx & 63;
-      const int t = idx >> 6;
-      const int j = t % MT, p = t / MT;
-      f32x4_t gs = red[0][(2 * p) * MT + j][l], us = red[0][(2 * p + 1) * MT + j][l];
-#pragma unroll
-      for (int ww = 1; ww < WAVES; ++ww) {
-        gs += red[ww][(2 * p) * MT + j][l];
-        us += red[ww][(2 * p + 1) * MT + j][l];
-      }
-      const int m = j * 16 + (l & 15);
-      if (m < M && 2 * p < cnt) {
-        const int n = ((nb0 + 2 * p) >> 1) * 16 + 4 * (l >> 4);
-        const float sc = epi_row_scale(ep, m);
-        f32x4_t v;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) v[q] = silu(gs[q] * sc) * (us[q] * sc);
-        uint2 pk;  // fragment-major in -> fragment-major out (the down projection's input)
-        pk.x = pack2bf(v[0], v[1]);
-        pk.y = pack2bf(v[2], v[3]);
-        *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(out) + xf_off(m, n, MT)) = pk;
-      }
-    }
-  } else {
-    const size_t slab = (size_t)blockIdx.y * M * ldo;
-    for (int idx = threadIdx.x; idx < NB * MT * 64; idx += 64 * WAVES) {
-      const int l = idx & 63;
-      const int t = idx >> 6;
-      const int j = t % MT, i = t / MT;
-      f32x4_t s = red[0][t][l];
-#pragma unroll
-      for (int ww = 1; ww < WAVES; ++ww) s += red[ww][t][l];
-      const int m = j * 16 + (l & 15);
-      if (m < M && i < cnt) {
-        s *= epi_row_scale(ep, m);
-        const int n = (nb0 + i) * 16 + 4 * (l >> 4);
-        if constexpr (EPI == EPI_F32) {
-          float* o = reinterpret_cast<float*>(out) + slab + (size_t)m * ldo + n;
-          *reinterpret_cast<float4*>(o) = make_float4(s[0], s[1], s[2], s[3]);
-        } else {
-          uint2 pk;
-          pk.x = pack2bf(s[0], s[1]);
-          pk.y = pack2bf(s[2], s[3]);
-          *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(out) + (size_t)m * ldo + n) = pk;
-        }
-      }
-    }
-  }
+  skinny_epilogue<MT, NB, EPI, WAVES, true>(acc, w, lane, M, nb0, cnt, out, ldo, ep);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -279,21 +186,9 @@ static void launch_z12_d(const Z12Args& a) {
                      a.base4, a.out, a.ldo, kbps, a.ep);
 }
 
-// the (waves, div) -> variant map of gemm.hip's launch_skinny_x
 template <int NB, int EPI>
 static void launch_z12_n(const Z12Args& a) {
-  if constexpr (NB >= 6) {
-    if (a.div == 1) launch_z12_d<NB, EPI, 4, 1>(a);
-    else launch_z12_d<NB, EPI, 4, 2>(a);
-  } else if (a.div == 2) {
-    if (a.waves == 8) launch_z12_d<NB, EPI, 8, 2>(a);
-    else launch_z12_d<NB, EPI, 4, 2>(a);
-  } else if (a.div == 4) {
-    launch_z12_d<NB, EPI, 4, 4>(a);
-  } else {
-    if (a.waves == 8) launch_z12_d<NB, EPI, 8, 1>(a);
-    else launch_z12_d<NB, EPI, 4, 1>(a);
-  }
+  skinny_variant<NB>(a.waves, a.div, [&](auto wv, auto dv) { launch_z12_d<NB, EPI, decltype(wv)::value, decltype(dv)::value>(a); });
 }
 
 template <int EPI>
@@ -316,10 +211,7 @@ extern "C" int lsa_gemm_z12(const void* X, int M, int K, const void* lo, const v
   if (epi != EPI_BF16 && epi != EPI_F32 && epi != EPI_SILU) return -4;
   const int NBtot = N / 16;
   if (nb != 2 && nb != 4 && nb != 6) return -2;
-  // a ragged grid (nb not dividing the n-blocks) needs >= 1 column unit per workgroup; SiLU units are pairs
-  if (epi == EPI_SILU && NBtot % 2) return -2;
-  if (NBtot % nb != 0 && (epi == EPI_SILU ? NBtot / 2 < (NBtot + nb - 1) / nb : NBtot < (NBtot + nb - 1) / nb))
-    return -2;
+  if (!skinny_grid_ok(NBtot, nb, epi == EPI_SILU)) return -2;
   if (splitk < 1) splitk = 1;
   if (splitk > K / 32) return -3;
   if (epi != EPI_F32 && splitk != 1) return -3;
