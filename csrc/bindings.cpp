@@ -55,14 +55,15 @@ int lsa_attn_prefill(const void* q, const void* kc, const void* vc, const int* b
 int lsa_argmax_commit(const float* logits, int B, int V, unsigned long long* part, int* out_tokens, int max_new,
                       int* gen_len, int* input_ids, int* positions, int* finished, const int* eos, int neos,
                       const int* limit, const int* eos_on, hipStream_t s);
-int lsa_attn_verify(const void* q, const void* kc, const void* vc, const int* bt, int max_blocks, const int* pos0, int T,
-                    int H, int Hkv, float scale, int chunk_blocks, int nsplit, int unsplit_max, void* out, float* opart,
+int lsa_attn_verify(const void* q, const void* kc, const void* vc, const int* bt, int max_blocks, const int* pos0, int S,
+                    int T, int H, int Hkv, float scale, int chunk_blocks, int nsplit, int unsplit_max, void* out, float* opart,
                     float* mlpart, int* counters, hipStream_t s, const float* ks = nullptr, const float* vs = nullptr);
 int lsa_kv_copy_blocks(void* kv, void* scale, const int* pairs, int npairs, int planes, int nb, long long tile_bytes,
                        long long scale_bytes, hipStream_t s);
 int lsa_spec_draft(const int* prompt_tok, int prompt_ld, const int* prompt_len, const int* out_tokens, int max_new,
                    const int* gen_len, const int* input_ids, const int* positions, int rows, int k, int n_max, int n_min,
-                   const int* forced, int nf, int* spec_ids, int* spec_pos, int* spec_draft, hipStream_t s);
+                   const int* forced, int nf, int forced_ld, int* spec_ids, int* spec_pos, int* spec_draft,
+                   hipStream_t s);
 int lsa_dfa_mask(float* logits, int B, int V, const int* tok_off, const uint8_t* tok_blob, const uint8_t* cls,
                  const uint16_t* trans, const uint8_t* accept, const int* g_dim, const int* g_on, int* g_state,
                  const int* g_base, const int* rows, const int* gen_len, const int* input_ids, const int* finished,
@@ -73,8 +74,8 @@ int lsa_dfa_mask_verify(float* logits, int T, int V, const int* tok_off, const u
                         const int* eos, int neos, const int* draft, int* g_spec, hipStream_t s);
 int lsa_dfa_spec_advance(const int* g_on, int* g_state, const int* g_spec, const int* gen_len, int r, int k,
                          hipStream_t s);
-int lsa_spec_commit(const float* logits, int T, int V, unsigned long long* part, const int* draft, long long* stats,
-                    int* out_tokens, int max_new, int* gen_len, int* input_ids, int* positions, int* finished,
+int lsa_spec_commit(const float* logits, int S, int T, int V, unsigned long long* part, const int* draft,
+                    long long* stats, int* out_tokens, int max_new, int* gen_len, int* input_ids, int* positions, int* finished,
                     const int* eos, int neos, const int* limit, const int* eos_on, hipStream_t s);
 int lsa_sample_commit(float* logits, int B, int V, unsigned long long* part, unsigned long long* cand, int* hist,
                       int window, const float* penalty, const int* last_n, const float* temperature, const int* top_k,
@@ -946,7 +947,9 @@ void argmax_commit(const at::Tensor& logits, at::Tensor& part, at::Tensor& out_t
         "argmax_commit");
 }
 
-// speculative decoding: attention of the T = k + 1 verify rows of one sequence (kernels/attention_verify.hip)
+// speculative decoding: attention of the T = k + 1 verify rows of each of S sequences (kernels/attention_verify.hip):
+// q [S, T, H, 128] with block_table [S, max_blocks], pos0 [S] and out [S * T, H * 128]; q [T, H, 128] with one block-table
+// row is the one-sequence form
 void attn_verify(const at::Tensor& q, const at::Tensor& kc, const at::Tensor& vc, const at::Tensor& block_table,
                  const at::Tensor& pos0, int64_t H, int64_t Hkv, double scale, int64_t chunk_blocks, int64_t nsplit,
                  int64_t unsplit_max, at::Tensor& out, at::Tensor& opart, at::Tensor& mlpart, at::Tensor& counters,
@@ -956,23 +959,30 @@ void attn_verify(const at::Tensor& q, const at::Tensor& kc, const at::Tensor& vc
   check_cache(kc, vc, ks, vs);  // bf16 cache without scales, e4m3 bytes with both
   need(pos0, at::kInt, "pos0");
   need(block_table, at::kInt, "block_table");
-  TORCH_CHECK(q.dim() == 3 && q.size(1) == H && q.size(2) == 128 && q.is_contiguous(), "q: contiguous [T, H, 128]");
-  const int64_t T = q.size(0);
+  TORCH_CHECK((q.dim() == 3 || q.dim() == 4) && q.size(-2) == H && q.size(-1) == 128 && q.is_contiguous(),
+              "q: contiguous [T, H, 128] or [S, T, H, 128]");
+  const int64_t S = q.dim() == 4 ? q.size(0) : 1, T = q.size(-3);
   TORCH_CHECK(H > 0 && Hkv > 0 && H % Hkv == 0 && kc.size(1) == Hkv, "heads: H % Hkv == 0, cache has Hkv heads");
   TORCH_CHECK(T >= 1 && T <= 8 && T * (H / Hkv) <= 16, "attn_verify: T <= 8 and T * H / Hkv <= 16 query rows per kv head");
-  TORCH_CHECK(pos0.numel() >= 1, "pos0: one int32");
-  TORCH_CHECK(block_table.is_contiguous() && block_table.numel() >= 1 && (block_table.dim() == 1 || block_table.size(0) == 1),
-              "block_table: one contiguous row [max_blocks]");
-  TORCH_CHECK(out.is_contiguous() && out.numel() >= T * H * 128, "attn_verify out too small");
+  TORCH_CHECK(S >= 1 && S <= 8, "attn_verify: 1 <= S <= 8 sequences");
+  TORCH_CHECK(S * T <= 32, "attn_verify: S * T <= 32 rows");
+  TORCH_CHECK(pos0.numel() >= S && pos0.is_contiguous(), "pos0: one int32 per sequence");
+  TORCH_CHECK(block_table.is_contiguous() && block_table.numel() >= 1 &&
+                  (q.dim() == 4 ? (block_table.dim() == 2 && block_table.size(0) == S)
+                                : (block_table.dim() == 1 || block_table.size(0) == 1)),
+              "block_table: one contiguous row [max_blocks], or [S, max_blocks] with q [S, T, H, 128]");
+  const int64_t max_blocks = block_table.numel() / S;
+  TORCH_CHECK(out.is_contiguous() && out.numel() >= S * T * H * 128, "attn_verify out too small");
   TORCH_CHECK(nsplit >= 1 && nsplit <= 256 && chunk_blocks >= 1, "attn_verify: 1 <= nsplit <= 256, chunk_blocks >= 1");
   need(opart, at::kFloat, "opart");
   need(mlpart, at::kFloat, "mlpart");
   need(counters, at::kInt, "counters");
-  TORCH_CHECK(opart.numel() >= T * H * nsplit * 128 && mlpart.numel() >= T * H * nsplit * 2 && counters.numel() >= Hkv,
+  TORCH_CHECK(opart.numel() >= S * T * H * nsplit * 128 && mlpart.numel() >= S * T * H * nsplit * 2 &&
+                  counters.numel() >= S * Hkv,
               "attn_verify workspace too small");
   TORCH_CHECK(opart.numel() * 4 < 0x7fffffffLL, "opart must stay below 2 GiB (buffer descriptor range)");
-  check(lsa_attn_verify(q.data_ptr(), kc.data_ptr(), vc.data_ptr(), block_table.data_ptr<int>(), block_table.numel(),
-                        pos0.data_ptr<int>(), T, H, Hkv, (float)scale, chunk_blocks, nsplit, (int)unsplit_max,
+  check(lsa_attn_verify(q.data_ptr(), kc.data_ptr(), vc.data_ptr(), block_table.data_ptr<int>(), max_blocks,
+                        pos0.data_ptr<int>(), S, T, H, Hkv, (float)scale, chunk_blocks, nsplit, (int)unsplit_max,
                         out.data_ptr(), opart.data_ptr<float>(), mlpart.data_ptr<float>(), counters.data_ptr<int>(),
                         cur_stream(), ptr<const float>(ks), ptr<const float>(vs)),
         "attn_verify");
@@ -997,34 +1007,46 @@ void spec_draft(const at::Tensor& prompt_tok, const at::Tensor& prompt_len, cons
               "spec_draft: state rows");
   TORCH_CHECK(spec_ids.numel() >= rows * (k + 1) && spec_pos.numel() >= rows * (k + 1) && spec_draft_out.numel() >= rows * k,
               "spec_draft outputs too small");
-  int64_t nf = 0;
+  int64_t nf = 0, forced_ld = 0;
   if (forced.has_value()) {
     need(*forced, at::kInt, "forced");
     TORCH_CHECK(forced->is_contiguous() && forced->numel() >= k && forced->numel() % k == 0, "forced: contiguous [nf, k]");
     nf = forced->numel() / k;
+    if (forced->dim() == 3) {  // one table per row
+      TORCH_CHECK(forced->size(0) >= rows && forced->size(1) >= 1 && forced->size(2) == k,
+                  "forced: contiguous [rows, nf, k]");
+      nf = forced->size(1);
+      forced_ld = nf * k;
+    }
   }
   check(lsa_spec_draft(prompt_tok.data_ptr<int>(), prompt_tok.size(1), prompt_len.data_ptr<int>(),
                        out_tokens.data_ptr<int>(), out_tokens.size(1), gen_len.data_ptr<int>(), input_ids.data_ptr<int>(),
-                       positions.data_ptr<int>(), rows, k, n_max, n_min, ptr<const int>(forced), nf,
+                       positions.data_ptr<int>(), rows, k, n_max, n_min, ptr<const int>(forced), nf, forced_ld,
                        spec_ids.data_ptr<int>(), spec_pos.data_ptr<int>(), spec_draft_out.data_ptr<int>(), cur_stream()),
         "spec_draft");
 }
 
-// speculative decoding: argmax of the T verify rows + in-order commit of the accepted run into state row 0
+// speculative decoding: argmax of the verify rows + in-order commit of each sequence's accepted run into its state row.
+// stats [3]: logits [T, V] are the rows of the sequence in state row 0; stats [S, 3]: logits [S * T, V], draft [S, T - 1]
+// and state rows 0 .. S - 1
 void spec_commit(const at::Tensor& logits, at::Tensor& part, const at::Tensor& draft, at::Tensor& stats,
                  at::Tensor& out_tokens, at::Tensor& gen_len, at::Tensor& input_ids, at::Tensor& positions,
                  at::Tensor& finished, const at::Tensor& eos, const at::Tensor& limit, const at::Tensor& eos_on) {
   need(logits, at::kFloat, "logits");
-  TORCH_CHECK(logits.dim() == 2 && logits.is_contiguous() && logits.size(0) >= 2, "logits: contiguous [T >= 2, V]");
-  const int T = logits.size(0), V = logits.size(1);
-  check_state(1, out_tokens, gen_len, input_ids, positions, finished, eos, limit, eos_on);
-  need(part, at::kLong, "part");
-  TORCH_CHECK(part.numel() >= (int64_t)T * ((V + 4095) / 4096), "argmax partials too small");
-  need(draft, at::kInt, "draft");
+  TORCH_CHECK(logits.dim() == 2 && logits.is_contiguous() && logits.size(0) >= 2, "logits: contiguous [S * T >= 2, V]");
   need(stats, at::kLong, "stats");
-  TORCH_CHECK(draft.numel() >= T - 1 && draft.is_contiguous() && stats.numel() >= 3 && stats.is_contiguous(),
-              "spec_commit: draft [T - 1], stats [3]");
-  check(lsa_spec_commit(logits.data_ptr<float>(), T, V, reinterpret_cast<unsigned long long*>(part.data_ptr()),
+  TORCH_CHECK(stats.is_contiguous() && (stats.dim() == 2 ? stats.size(0) >= 1 && stats.size(1) == 3 : stats.numel() >= 3),
+              "spec_commit: stats [3] or [S, 3]");
+  const int S = stats.dim() == 2 ? stats.size(0) : 1;
+  TORCH_CHECK(logits.size(0) % S == 0 && logits.size(0) / S >= 2 && (S == 1 || logits.size(0) <= 32),
+              "spec_commit: logits [S * T, V] with T >= 2 and S * T <= 32");
+  const int T = logits.size(0) / S, V = logits.size(1);
+  check_state(S, out_tokens, gen_len, input_ids, positions, finished, eos, limit, eos_on);
+  need(part, at::kLong, "part");
+  TORCH_CHECK(part.numel() >= (int64_t)S * T * ((V + 4095) / 4096), "argmax partials too small");
+  need(draft, at::kInt, "draft");
+  TORCH_CHECK(draft.numel() >= (int64_t)S * (T - 1) && draft.is_contiguous(), "spec_commit: draft [S, T - 1]");
+  check(lsa_spec_commit(logits.data_ptr<float>(), S, T, V, reinterpret_cast<unsigned long long*>(part.data_ptr()),
                         draft.data_ptr<int>(), reinterpret_cast<long long*>(stats.data_ptr<int64_t>()),
                         out_tokens.data_ptr<int>(), out_tokens.size(1), gen_len.data_ptr<int>(),
                         input_ids.data_ptr<int>(), positions.data_ptr<int>(), finished.data_ptr<int>(),

@@ -1,7 +1,12 @@
-// Verify attention of speculative decoding: the T = k + 1 new tokens of ONE sequence against the paged KV cache
+// Verify attention of speculative decoding: the T = k + 1 new tokens of each of S sequences against the paged KV cache
 // (layout of attention.hip: [num_blocks, Hkv, 64 tokens, 128]; bf16, or -- KV8 -- the fp8 cache), head_dim 128.
 //
-//   attn_verify_kernel   split-KV like attn_decode_kernel, grid (Hkv, nsplit), 4 waves.  All R = T * G query rows
+//   attn_verify_kernel   split-KV like attn_decode_kernel, grid (Hkv, nsplit, S), 4 waves.  Sequence s = blockIdx.z
+//                        reads pos0[s], block-table row s and query rows s T .. s T + T - 1, and owns output rows,
+//                        split partials ((s T H + row) nsplit + split) and tickets (s Hkv + hk) of its own: no word is
+//                        read by a workgroup of another sequence, and each sequence takes eff_split from its own
+//                        context (unsplit, split and early return side by side in one launch).  S = 1 is the
+//                        one-sequence launch: same grid, same offsets.  Per sequence: all R = T * G query rows
 //                        (row r = t * G + g: token t, head hk * G + g; R <= 16) of a kv head are the 16-wide side of
 //                        the bf16 16x16x32 MFMA, so a workgroup reads every K / V byte of its block range once for
 //                        all rows -- the cost of a verify step's attention is close to one decode step's, not T.
@@ -35,10 +40,11 @@
 //                              the pair partner of the last visible key included) contributes p = 0 and its scales are
 //                              never used.
 //
-// hipcc --offload-arch=gfx950 -O3 -Rpass-analysis=kernel-resource-usage: 164 VGPRs + 32 AGPRs, 44 SGPRs, scratch 0,
-// no spills, LDS 49668 bytes per workgroup, occupancy 2 waves per SIMD (the grid is Hkv x nsplit <= ~256 workgroups of
-// 4 waves: at most one workgroup per CU is resident anyway).  KV8: 134 VGPRs + 32 AGPRs, 50 SGPRs, scratch 0, no
-// spills, LDS 49668 bytes, occupancy 3.
+// hipcc --offload-arch=gfx950 -O3 -Rpass-analysis=kernel-resource-usage: 164 VGPRs + 32 AGPRs, 51 SGPRs, scratch 0,
+// no spills, LDS 49668 bytes per workgroup, occupancy 2 waves per SIMD (the grid is Hkv x nsplit x S workgroups of
+// 4 waves, planned at about 256: at most one workgroup per CU is resident then; registers admit two, LDS three).
+// KV8: 134 VGPRs + 32 AGPRs, 56 SGPRs, scratch 0, no spills, LDS 49668 bytes, occupancy 3.  (The sequence index cost
+// 7 / 6 SGPRs and no vector register over the one-sequence kernel.)
 #include "common.h"
 
 #define LSA_NEG (-1.0e30f)
@@ -67,7 +73,7 @@ __device__ __forceinline__ uint2 av_ldg_nt8(const uint8_t* p) {
 template <bool KV8>
 __global__ __launch_bounds__(256) void attn_verify_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ kc,
                                                           const uint16_t* __restrict__ vc,
-                                                          const int* __restrict__ bt, int max_blocks,
+                                                          const int* __restrict__ bt_all, int max_blocks,
                                                           const int* __restrict__ pos0_p, int T, int G, int Hkv,
                                                           float scale_log2, int chunk_blocks, int nsplit, int unsplit_max,
                                                           uint16_t* __restrict__ out, float* __restrict__ opart,
@@ -78,12 +84,14 @@ __global__ __launch_bounds__(256) void attn_verify_kernel(const uint16_t* __rest
   __shared__ __attribute__((aligned(16))) float so[4][16][D];    // per-wave partial outputs
   __shared__ float sm[4][16], sl[4][16];
   __shared__ int s_last;
-  const int hk = blockIdx.x, split = blockIdx.y;
+  const int hk = blockIdx.x, split = blockIdx.y, seq = blockIdx.z;
   const int H = Hkv * G, R = T * G;
+  const size_t row0 = (size_t)seq * T * H;  // the sequence's first [S * T, H] row: queries, output and partials
+  const int* __restrict__ bt = bt_all + (size_t)seq * max_blocks;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4, r = lane & 15;
   const __amdgpu_buffer_rsrc_t rs_o = __builtin_amdgcn_make_buffer_rsrc(opart, 0, 0x7fffffff, 0x00020000);
 
-  const int pos0 = pos0_p[0];
+  const int pos0 = pos0_p[seq];
   const int ctx = pos0 + T;
   const int nblk = min((ctx + 63) >> 6, max_blocks);
   int ech, nse;
@@ -98,7 +106,7 @@ __global__ __launch_bounds__(256) void attn_verify_kernel(const uint16_t* __rest
   const int qpos = pos0 + qt;
   uint4 qf[4];
   {
-    const uint16_t* qrow = q + ((size_t)qt * H + hk * G + qg) * D;
+    const uint16_t* qrow = q + (row0 + (size_t)qt * H + hk * G + qg) * D;
 #pragma unroll
     for (int s = 0; s < 4; ++s) qf[s] = *reinterpret_cast<const uint4*>(qrow + 32 * s + 8 * g);
   }
@@ -244,7 +252,7 @@ __global__ __launch_bounds__(256) void attn_verify_kernel(const uint16_t* __rest
       O[0] += v.x * wgt; O[1] += v.y * wgt; O[2] += v.z * wgt; O[3] += v.w * wgt;
     }
     const int t = row / G;
-    const size_t orow = (size_t)t * H + hk * G + (row - t * G);  // [T, H] row of the output and of the partials
+    const size_t orow = row0 + (size_t)t * H + hk * G + (row - t * G);  // [S * T, H] row of the output and partials
     if (nse == 1) {
       const float inv = L > 0.f ? 1.f / L : 0.f;
       uint2 pk;
@@ -268,7 +276,7 @@ __global__ __launch_bounds__(256) void attn_verify_kernel(const uint16_t* __rest
   // agent ticket add; the reducer reads every partial with sc1 loads and resets the ticket for the next launch)
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  av_g_i32* ctr = (av_g_i32*)(counters) + hk;
+  av_g_i32* ctr = (av_g_i32*)(counters) + seq * Hkv + hk;
   if (tid == 0) s_last = __hip_atomic_fetch_add(ctr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == nse - 1;
   __syncthreads();
   if (!s_last) return;
@@ -276,7 +284,7 @@ __global__ __launch_bounds__(256) void attn_verify_kernel(const uint16_t* __rest
   for (int e = tid; e < R * 32; e += 256) {
     const int row = e >> 5, d0 = (e & 31) * 4;
     const int t = row / G;
-    const size_t orow = (size_t)t * H + hk * G + (row - t * G);
+    const size_t orow = row0 + (size_t)t * H + hk * G + (row - t * G);
     const size_t pi0 = orow * nsplit;
     float M = LSA_NEG, L = 0.f, O[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll 4
@@ -300,11 +308,12 @@ __global__ __launch_bounds__(256) void attn_verify_kernel(const uint16_t* __rest
   }
 }
 
-// q [T, H, 128] bf16 (rotated); bt: the sequence's block-table row [max_blocks]; pos0: device int32, position of row 0;
-// ks / vs: the fp8 cache's scale arrays [blocks, Hkv, 64] f32 (kc / vc are then e4m3 bytes), null for the bf16 cache;
-// out [T, H * 128] bf16; workspace for T * H rows x nsplit partials and Hkv zeroed tickets (ops.verify_workspace)
+// q [S, T, H, 128] bf16 (rotated); bt: the sequences' block-table rows [S, max_blocks]; pos0 [S]: device int32, position
+// of each sequence's row 0; ks / vs: the fp8 cache's scale arrays [blocks, Hkv, 64] f32 (kc / vc are then e4m3 bytes),
+// null for the bf16 cache; out [S * T, H * 128] bf16; workspace for S * T * H rows x nsplit partials and S * Hkv zeroed
+// tickets (ops.verify_workspace).  1 <= S <= 8 and S * T <= 32 rows.
 extern "C" int lsa_attn_verify(const void* q, const void* kc, const void* vc, const int* bt, int max_blocks,
-                               const int* pos0, int T, int H, int Hkv, float scale, int chunk_blocks, int nsplit,
+                               const int* pos0, int S, int T, int H, int Hkv, float scale, int chunk_blocks, int nsplit,
                                int unsplit_max, void* out, float* opart, float* mlpart, int* counters, hipStream_t s,
                                const float* ks = nullptr, const float* vs = nullptr) {
   if (Hkv <= 0 || H <= 0 || H % Hkv) return -1;
@@ -313,8 +322,10 @@ extern "C" int lsa_attn_verify(const void* q, const void* kc, const void* vc, co
   if (nsplit < 1 || nsplit > 256 || chunk_blocks < 1) return -3;
   if (max_blocks < 1) return -4;
   if ((ks == nullptr) != (vs == nullptr)) return -5;  // the fp8 cache needs both scale arrays
+  if (S < 1 || S > 8) return -6;
+  if (S * T > 32) return -7;
 #define LSA_AVL(KV8)                                                                                                  \
-  hipLaunchKernelGGL((attn_verify_kernel<KV8>), dim3(Hkv, nsplit), dim3(256), 0, s,                                   \
+  hipLaunchKernelGGL((attn_verify_kernel<KV8>), dim3(Hkv, nsplit, S), dim3(256), 0, s,                                \
                      reinterpret_cast<const uint16_t*>(q), reinterpret_cast<const uint16_t*>(kc),                     \
                      reinterpret_cast<const uint16_t*>(vc), bt, max_blocks, pos0, T, G, Hkv,                          \
                      scale * 1.4426950408889634f, chunk_blocks, nsplit, unsplit_max, reinterpret_cast<uint16_t*>(out), \

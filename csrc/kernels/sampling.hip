@@ -261,17 +261,23 @@ extern "C" int lsa_argmax_commit(const float* logits, int B, int V, unsigned lon
   return (int)hipGetLastError();
 }
 
-// Speculative decoding (spec.hip drafts): logits [T, V] are the T = k + 1 verify rows of ONE sequence (state row 0
-// of st).  tok_i = argmax(logits[i]); a = the number of leading i < k with draft[i] == tok_i (a -1 draft never
-// matches); tok_0 .. tok_a are committed in order through commit_token, so nothing follows a finishing token (EOS /
-// length).  stats[3] += (1 step, drafts >= 0, tokens committed beyond the first).  A finished row changes nothing.
+// Speculative decoding (spec.hip drafts): logits [S * T, V] are the T = k + 1 verify rows of each of S sequences;
+// workgroup s verifies rows s T .. s T + T - 1 against draft[s k ..] into state row s of st.  tok_i = argmax(logits[s T
+// + i]); a = the number of leading i < k with draft[i] == tok_i (a -1 draft never matches); tok_0 .. tok_a are
+// committed in order through commit_token, so nothing follows a finishing token (EOS / length).  stats [S, 3]: row s is
+// written by workgroup s alone (plain stores), stats[s] += (1 step, drafts >= 0, tokens committed beyond the first).
+// A finished row changes nothing and counts nothing.
 __global__ __launch_bounds__(64) void spec_commit_kernel(const unsigned long long* __restrict__ part, int nch, int k,
                                                          const int* __restrict__ draft, long long* __restrict__ stats,
                                                          DecodeState st) {
+  const int s = blockIdx.x;
+  part += (size_t)s * (k + 1) * nch;
+  draft += (size_t)s * k;
+  stats += (size_t)s * 3;
   int tok = 0;
   bool run = true;  // tok_0 .. tok_{i-1} matched their drafts
   int committed = 0, drafted = 0;
-  const bool live = !st.finished[0];
+  const bool live = !st.finished[s];
   for (int i = 0; i <= k; ++i) {
     unsigned long long best = 0ull;
     for (int c = threadIdx.x; c < nch; c += 64) {
@@ -280,8 +286,8 @@ __global__ __launch_bounds__(64) void spec_commit_kernel(const unsigned long lon
     }
     best = wave_max_u64(best);
     tok = (int)(0xffffffffu - (uint32_t)(best & 0xffffffffull));
-    if (threadIdx.x == 0 && run && live && !st.finished[0]) {
-      commit_token(st, 0, tok);
+    if (threadIdx.x == 0 && run && live && !st.finished[s]) {
+      commit_token(st, s, tok);
       ++committed;
     }
     if (i < k) {
@@ -297,16 +303,17 @@ __global__ __launch_bounds__(64) void spec_commit_kernel(const unsigned long lon
   }
 }
 
-extern "C" int lsa_spec_commit(const float* logits, int T, int V, unsigned long long* part, const int* draft,
+extern "C" int lsa_spec_commit(const float* logits, int S, int T, int V, unsigned long long* part, const int* draft,
                                long long* stats, int* out_tokens, int max_new, int* gen_len, int* input_ids,
                                int* positions, int* finished, const int* eos, int neos, const int* limit,
                                const int* eos_on, hipStream_t s) {
   if (T < 2) return -1;
+  if (S < 1 || (S > 1 && S * T > 32)) return -2;
   const int chunk = 4096;
   const int nch = (V + chunk - 1) / chunk;
-  hipLaunchKernelGGL(argmax_partial_kernel, dim3(nch, T), dim3(256), 0, s, logits, V, chunk, part, nch);
+  hipLaunchKernelGGL(argmax_partial_kernel, dim3(nch, S * T), dim3(256), 0, s, logits, V, chunk, part, nch);
   DecodeState st{out_tokens, max_new, gen_len, input_ids, positions, finished, eos, neos, limit, eos_on, nullptr, 0};
-  hipLaunchKernelGGL(spec_commit_kernel, dim3(1), dim3(64), 0, s, part, nch, T - 1, draft, stats, st);
+  hipLaunchKernelGGL(spec_commit_kernel, dim3(S), dim3(64), 0, s, part, nch, T - 1, draft, stats, st);
   return (int)hipGetLastError();
 }
 

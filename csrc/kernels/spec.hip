@@ -11,7 +11,9 @@
 //                       Writes spec_ids[T] = [input_ids[row], max(draft, 0) ...], spec_pos[T] = positions[row] + t and
 //                       spec_draft[k].  forced [nf, k] (optional) skips the search: the draft is row
 //                       min(gen_len[row], nf - 1) of it (nf = 1: one fixed draft; tests plant per-step drafts, and it
-//                       is the hook of a later drafter).  ops/reference.py spec_draft is the host twin.
+//                       is the hook of a later drafter).  Row r reads the table at forced + r * forced_ld: 0 for one
+//                       [nf, k] table that serves every row, nf * k for per-sequence tables [rows, nf, k].
+//                       ops/reference.py spec_draft is the host twin.
 #include "common.h"
 
 __global__ __launch_bounds__(256) void spec_draft_kernel(const int* __restrict__ prompt_tok, int prompt_ld,
@@ -20,7 +22,7 @@ __global__ __launch_bounds__(256) void spec_draft_kernel(const int* __restrict__
                                                          const int* __restrict__ gen_len,
                                                          const int* __restrict__ input_ids,
                                                          const int* __restrict__ positions, int k, int n_max, int n_min,
-                                                         const int* __restrict__ forced, int nf,
+                                                         const int* __restrict__ forced, int nf, int forced_ld,
                                                          int* __restrict__ spec_ids, int* __restrict__ spec_pos,
                                                          int* __restrict__ spec_draft) {
   const int row = blockIdx.x, tid = threadIdx.x;
@@ -60,7 +62,7 @@ __global__ __launch_bounds__(256) void spec_draft_kernel(const int* __restrict__
     if (tid > 0) {
       const int i = tid - 1;
       if (forced != nullptr) {
-        d = forced[(size_t)min(gl, nf - 1) * k + i];
+        d = forced[(size_t)row * forced_ld + (size_t)min(gl, nf - 1) * k + i];
       } else if (s_j >= 0 && s_j + 1 + i < L) {
         d = ctx(s_j + 1 + i);
       }
@@ -73,11 +75,12 @@ __global__ __launch_bounds__(256) void spec_draft_kernel(const int* __restrict__
 
 extern "C" int lsa_spec_draft(const int* prompt_tok, int prompt_ld, const int* prompt_len, const int* out_tokens,
                               int max_new, const int* gen_len, const int* input_ids, const int* positions, int rows,
-                              int k, int n_max, int n_min, const int* forced, int nf, int* spec_ids, int* spec_pos,
-                              int* spec_draft, hipStream_t s) {
+                              int k, int n_max, int n_min, const int* forced, int nf, int forced_ld, int* spec_ids,
+                              int* spec_pos, int* spec_draft, hipStream_t s) {
   if (rows < 1 || k < 1 || k > 255 || n_max < 1 || n_min < 1 || n_min > n_max) return -1;
-  if (forced != nullptr && nf < 1) return -2;
+  if (forced != nullptr && (nf < 1 || (forced_ld != 0 && forced_ld != nf * k))) return -2;
   hipLaunchKernelGGL(spec_draft_kernel, dim3(rows), dim3(256), 0, s, prompt_tok, prompt_ld, prompt_len, out_tokens,
-                     max_new, gen_len, input_ids, positions, k, n_max, n_min, forced, nf, spec_ids, spec_pos, spec_draft);
+                     max_new, gen_len, input_ids, positions, k, n_max, n_min, forced, nf, forced_ld, spec_ids, spec_pos,
+                     spec_draft);
   return (int)hipGetLastError();
 }

@@ -284,6 +284,7 @@ class EngineService(Backend):
                                 "waiting": lp.engine.sched.num_waiting, "kv_usage": lp.engine.sched.kv_usage,
                                 "prefix_cached_blocks": lp.engine.sched.cached_blocks,
                                 "restarts": lp.restarts, "rebuilds": self.rebuilds.get(m, 0),
+                                "spec_batch": getattr(lp.engine, "spec_batch", 1),
                                 **lp.engine.stats} for m, lp in self._loops.items()}}
 
 

@@ -75,6 +75,10 @@ class Settings:
     # plain steps whatever spec_tokens says).  Needs spec_tokens; verify row i makes the plain step's draw for its
     # token, so the tokens are those of the plain sampled steps of the same seed
     spec_sampled: bool = dataclasses.field(default_factory=lambda: _env("SPEC_SAMPLED", False, bool))
+    # the largest number of running greedy, unconstrained requests whose decode run may be a run of verify steps (1:
+    # only a request that runs alone speculates).  Needs spec_tokens; clamped to a power of two with spec_batch * T <= 32,
+    # at most 8 and at most the engine's slots (max_batch).  All or nothing: one running request that cannot speculate makes the run plain
+    spec_batch: int = dataclasses.field(default_factory=lambda: _env("SPEC_BATCH", 1, int))
     tp: int = dataclasses.field(default_factory=lambda: _env("TP", 1, int))
     dp: int = dataclasses.field(default_factory=lambda: _env("DP", 1, int))
     max_batch: int = dataclasses.field(default_factory=lambda: _env("MAX_BATCH", 32, int))

@@ -151,10 +151,12 @@ class LLMEngine:
     def __init__(self, runner: ModelRunner, tokenizer=None, max_prefill_tokens: int = 16384, sync_every: int = 8,
                  name: Optional[str] = None, prefill_chunk: Optional[int] = None, kv_reserve_tokens: int = BLOCK,
                  spec_tokens: int = 0, prefix_cache: bool = False, prefix_cow_min_tokens: Optional[int] = None,
-                 guided: bool = False):
+                 guided: bool = False, spec_batch: int = 0):
         self.runner = runner
         if spec_tokens:  # speculative decoding for batch-1 greedy requests (the runner clamps it to what it supports)
             runner.spec_tokens = int(spec_tokens)
+        if spec_batch:  # ... and for up to spec_batch greedy requests at once (``_spec_run``; the runner clamps it too)
+            runner.spec_batch = int(spec_batch)
         self.spec = runner.spec
         self.name = name or self.spec.name
         self.tok = tokenizer or tokenizer_for(self.spec)
@@ -199,6 +201,9 @@ class LLMEngine:
                       # prompt tokens not prefilled because of it (prompt_tokens counts the tokens that were)
                       "prefix_queries": 0, "prefix_hits": 0, "prefix_cached_tokens": 0}
         self._spec_seen = (0, 0, 0)  # runner.spec_counts() as of the last decode run
+        self._spec_rows_seen: list = []  # runner.spec_row_counts() as of the last decode run over several sequences
+        # the largest number of requests a run of verify steps may serve (the runner's clamped spec_batch; 1 = off)
+        self.spec_batch = runner.spec_s() if getattr(runner, "spec_tokens", 0) > 0 else 1
         # regex-constrained decoding (SamplingParams.regex): the tokenizer's byte table goes to the device once and the
         # runner allocates its per-slot DFA tables; off (the default) nothing is allocated, launched or counted
         self.guided = bool(guided) or bool(getattr(runner, "guided", False))
@@ -357,8 +362,9 @@ class LLMEngine:
                     return []
             B = r.bucket(self.sched.highest_slot + 1)
             # host-side bound on every row's context during the run (selects the decode graph's split plan)
+            spec_S = r.bucket(self.sched.highest_slot + 1) if (spec_T and len(reqs) > 1) else 1
             if spec_T:
-                max_ctx = len(reqs[0].ctx_ids) + reqs[0].gen_host + n_steps * spec_T + spec_T
+                max_ctx = max(len(q.ctx_ids) + q.gen_host for q in reqs) + n_steps * spec_T + spec_T
             else:
                 max_ctx = max(len(q.ctx_ids) + min(q.gen_host + n_steps, q.params.max_tokens) for q in reqs) + 1
         # the decode run needs no scheduler state: new requests may be added meanwhile
@@ -368,7 +374,9 @@ class LLMEngine:
             if self.device_timing:
                 ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
                 ev[0].record()
-            if spec_T:
+            if spec_T and spec_S > 1:  # spec_batch: greedy, unconstrained verify steps over slots 0 .. spec_S - 1
+                r.decode_spec(n_steps, max_ctx=max_ctx, S=spec_S)
+            elif spec_T:
                 if sample:  # spec_sampled: the verify graph that ends in the sampled commit (masked too, if guided)
                     r.decode_spec(n_steps, max_ctx=max_ctx, guided=guided, sample=True)
                 elif guided:  # spec_guided: the verify graph with the mask of the T verify rows
@@ -390,7 +398,7 @@ class LLMEngine:
                 self.stats["guided_steps"] += n_steps
                 REGISTRY.inc("lsa_guided_steps_total", n_steps, "decode steps run with the regex mask", model=self.name)
             if spec_T and n_steps:
-                self._spec_account(reqs[0])
+                self._spec_account(reqs)
             if ev is not None:
                 dev_s = ev[0].elapsed_time(ev[1]) / 1e3  # both recorded before read_rows' sync
                 self.stats["decode_device_s"] += dev_s
@@ -468,8 +476,10 @@ class LLMEngine:
         lookahead (also reserved so that a finished row, which rewrites its last T positions while the graph replays,
         stays in its own blocks)."""
         r = self.runner
-        if not (getattr(r, "spec_tokens", 0) > 0 and r.spec_supported()) or len(reqs) != 1:
+        if not (getattr(r, "spec_tokens", 0) > 0 and r.spec_supported()):
             return 0
+        if len(reqs) != 1:
+            return self._spec_run_batch(reqs, n_steps, remaining)
         q = reqs[0]
         sp = q.params
         if q.slot != 0 or self.sched.highest_slot != 0 or self.sched.num_running != 1 or not sp.speculate or q.spec_off:
@@ -490,15 +500,56 @@ class LLMEngine:
             r.extend_tables([(q.slot, self.sched.block_table(q.rid))])
         return T
 
+    def _spec_run_batch(self, reqs: list, n_steps: int, remaining: int) -> int:
+        """``_spec_run`` for n = len(reqs) > 1 running requests (``spec_batch``): T when the run is a run of verify
+        steps over the sequences of slots 0 .. S - 1, S = bucket(highest slot + 1) <= spec_batch, else 0.  All or
+        nothing -- a limit, not an oversight: one request that cannot speculate makes the whole run plain, because a
+        mixed run would need rows of two kinds in one graph.  Every condition must hold: the scheduler runs no other
+        request and none is mid-prefill; every request is greedy, unconstrained, has ``speculate`` on and has not been
+        dropped by the acceptance guard; every request has window room for steps * T + T more positions; and
+        ``sched.grow`` gives every request the blocks of those positions without preempting anyone (blocks grown before
+        a later request fails stay with their requests: the plain run that follows needs them too).  Slots below S
+        without a request are idle rows of the step (``ModelRunner._verify_step``)."""
+        r = self.runner
+        SB = r.spec_s()
+        if SB < 2 or len(reqs) > SB or self.sched.num_running != len(reqs) or self._prefilling:
+            return 0
+        if r.bucket(self.sched.highest_slot + 1) > SB or any(not 0 <= q.slot < SB for q in reqs):
+            return 0
+        if any(q.params.needs_sampler or q.dfa is not None or not q.params.speculate or q.spec_off for q in reqs):
+            return 0
+        T = r.spec_k() + 1
+        if SB * T > 32:
+            return 0
+        steps = min(n_steps, -(-remaining // T))
+        if any(len(q.ctx_ids) + q.gen_host + steps * T + T > r.max_model_len for q in reqs):
+            return 0
+        grown, ok = [], True
+        for q in reqs:
+            got = self.sched.grow(q.rid, len(q.ctx_ids) + q.gen_host - 1 + steps * T + T - 1)
+            if got < 0:
+                ok = False
+                break
+            if got > 0:
+                self.stats["kv_grown_blocks"] += got
+                grown.append((q.slot, self.sched.block_table(q.rid)))
+        if grown:
+            r.extend_tables(grown)
+        return T if ok else 0
+
     def _bytes_of(self, ids: Sequence[int]) -> bytes:
         """The bytes the token ids decode to (the table regex-constrained decoding walks on the device)."""
         off, blob = self._tok_bytes
         return b"".join(blob[off[t]:off[t + 1]] for t in ids if 0 <= t < len(off) - 1)
 
-    def _spec_account(self, q: Request) -> None:
-        """Fold the runner's verify-step counters into the engine's and the request's; apply the acceptance guard: a
-        request whose accepted-per-step mean is below break-even after 16 verify steps takes plain steps from now on."""
-        now = self.runner.spec_counts()
+    def _spec_account(self, reqs: list) -> None:
+        """Fold the runner's verify-step counters into the engine's and the requests'; apply the acceptance guard: a
+        request whose accepted-per-step mean is below break-even after 16 verify steps takes plain steps from now on.
+        A run over several sequences reads the per-row counters: row s belongs to the request in slot s."""
+        rows = self.runner.spec_row_counts()
+        seen = self._spec_rows_seen + [[0, 0, 0]] * (len(rows) - len(self._spec_rows_seen))
+        self._spec_rows_seen = rows
+        now = tuple(int(sum(c)) for c in zip(*rows))
         d = [a - b for a, b in zip(now, self._spec_seen)]
         self._spec_seen = now
         for key, v in zip(("spec_steps", "spec_drafted", "spec_accepted"), d):
@@ -506,10 +557,12 @@ class LLMEngine:
         REGISTRY.inc("lsa_spec_steps_total", d[0], "speculative-decoding verify steps", model=self.name)
         REGISTRY.inc("lsa_spec_drafted_tokens_total", d[1], "tokens drafted by the prompt-lookup drafter", model=self.name)
         REGISTRY.inc("lsa_spec_accepted_tokens_total", d[2], "drafted tokens accepted by verification", model=self.name)
-        q.spec_steps += d[0]
-        q.spec_accepted += d[2]
-        if q.spec_steps >= 16 and q.spec_accepted / q.spec_steps < self.runner.spec_min_accept:
-            q.spec_off = True
+        for q in reqs:
+            ds = [a - b for a, b in zip(rows[q.slot], seen[q.slot])]
+            q.spec_steps += ds[0]
+            q.spec_accepted += ds[2]
+            if q.spec_steps >= 16 and q.spec_accepted / q.spec_steps < self.runner.spec_min_accept:
+                q.spec_off = True
 
     def _preempt(self, q: Request) -> None:
         """Release a running request's slot and KV blocks and re-queue it first; its generated tokens become part

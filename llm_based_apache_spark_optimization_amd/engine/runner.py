@@ -50,7 +50,8 @@ class ModelRunner:
                  max_new_cap: Optional[int] = None, tp=None, use_graphs: bool = True,
                  fuse_rope: Optional[bool] = None, seq_parallel: Optional[bool] = None, sp_min_tokens: Optional[int] = None,
                  kv_dtype: Optional[str] = None, spec_tokens: int = 0, spec_ngram: tuple = (3, 1),
-                 spec_quantized: bool = False, spec_guided: bool = False, spec_sampled: bool = False):
+                 spec_quantized: bool = False, spec_guided: bool = False, spec_sampled: bool = False,
+                 spec_batch: int = 1):
         self.w = weights
         # prompt-lookup speculative decoding (``_verify_step``): tokens drafted per step (0 = off) and the drafter's
         # (longest, shortest) n-gram.  Plain attributes: an experiment may set them on a built runner.
@@ -66,16 +67,26 @@ class ModelRunner:
         # ``_verify_step(sample=True)``: verify row i makes the plain step's draw for generated token n + i, so the
         # tokens are those of the plain sampled steps of the same seed)
         self.spec_sampled = bool(spec_sampled)
+        # opt-in: the largest number S of running requests (slots 0 .. S - 1) whose decode run may be a run of verify
+        # steps (``_verify_step(S=)``: S * T rows, ``spec_s`` clamps it).  1 = one request in slot 0 only.  Greedy,
+        # unconstrained requests only: sampled and guided verify steps stay one-sequence.
+        self.spec_batch = int(spec_batch)
         # acceptance guard of the engine: a request whose accepted-per-verify-step mean falls below this after 16
         # verify steps takes plain steps for the rest of its life.  Break-even = verify-step time / plain-step time - 1.
         # Measured on MI355X (scripts/bench_spec.py, profiles/spec/spec_decode_mi355x.jsonl; plain vs verify step, k = 3):
         # duckdb-nsql-7B 128 + 128: 2.575 vs 2.845 ms -> 0.105; Llama-3.2-3B 2k + 128: 1.559 vs 1.828 ms -> 0.172
         # (k = 1: 0.085 / 0.098; k = max: 0.133 at k = 7 / 0.224 at k = 4).  The default stays 0.0 = never drop until the
         # guard has run against real (checkpoint) acceptance; set it per deployment (LSA_SPEC_MIN_ACCEPT).
+        # The figures above are the break-even of ONE sequence.  A verify step over S sequences (``spec_batch``) breaks
+        # even against the plain step of bucket S at, per step and request (scripts/bench_spec.py --batch,
+        # profiles/spec/spec_batch_mi355x.jsonl, k = 3): 7B 0.10 / 0.12 / 0.34 and 3B 0.13 / 0.18 / 0.25 at S = 2 / 4 / 8.
+        # The guard compares every request with this one value whatever S it ran at: set it to the row of the
+        # spec_batch in use.
         self.spec_min_accept = 0.0
         self._spec = None           # device buffers of the verify step (allocated on first use)
         self._spec_forced = None    # [nf, k] int32 planted drafts (tests / a later drafter), see set_spec_forced
         self._spec_clamp_logged = False
+        self._spec_batch_clamp_logged = False
         # paged KV cache dtype: "bf16" or "fp8" (e4m3 rows with per-(token, kv-head) scales, ops.KV_FP8)
         kv_dtype = kv_dtype or ("fp8" if ops.KV_FP8 else "bf16")
         assert kv_dtype in ("bf16", "fp8"), kv_dtype
@@ -753,6 +764,21 @@ class ModelRunner:
                                                 self.spec_tokens, k)
         return max(k, 0)
 
+    def spec_s(self) -> int:
+        """The most sequences a verify step may serve: ``spec_batch`` clamped to a power of two that is at most 8 (the
+        sequences ``attn_verify`` takes), at most ``max_slots``, and keeps spec_batch * T <= 32 rows (T = 8 allows 4)."""
+        want = max(1, int(self.spec_batch))
+        T = self.spec_k() + 1
+        s = 1
+        while s * 2 <= min(want, self.max_slots, 8) and s * 2 * T <= 32:
+            s *= 2
+        if s != want and not self._spec_batch_clamp_logged:
+            self._spec_batch_clamp_logged = True
+            import logging
+            logging.getLogger(__name__).warning("spec_batch=%d clamped to %d (a power of two, spec_batch * T <= 32, "
+                                                "<= max_slots)", self.spec_batch, s)
+        return s
+
     def spec_supported(self) -> bool:
         """Whether this runner can run verify steps: TP = 1, at least one drafted token, and either bf16 weights with
         the bf16 KV cache or -- ``spec_quantized`` -- bf16 / fp8 / MXFP4 weights with the bf16 or the fp8 cache."""
@@ -772,19 +798,24 @@ class ModelRunner:
         return dict(qkv=False, gate_up=False, o=False, down=False, rr=False)
 
     def _spec_bufs(self) -> dict:
-        """Device buffers of the verify step, sized for the largest T this runner can run (8 rows)."""
+        """Device buffers of the verify step, sized for the most rows a step can have (32 = S * T), and the context
+        history ``ctx`` / ``ctx_len`` of the ``spec_s()`` slots that may speculate."""
         if self._spec is not None:
+            assert self._spec["ctx"].shape[0] >= self.spec_s(), "spec_batch must be set before the first verify step"
             return self._spec
-        dev, TM = self.device, 8
+        dev, TM, SB = self.device, 32, self.spec_s()
         i32 = dict(dtype=torch.int32, device=dev)
         f32 = dict(dtype=torch.float32, device=dev)
         bf = dict(dtype=torch.bfloat16, device=dev)
         nqkv = (self.H + 2 * self.Hkv) * self.D
-        nsplit_max = max(4, ops.verify_split_plan(self.Hkv, self.max_model_len)[1])
+        nsplit_max = max([4] + [ops.verify_split_plan(self.Hkv, self.max_model_len, S)[1] for S in (1, 2, 4, 8)])
         self._spec = dict(
-            ctx=torch.zeros(1, self.max_model_len, **i32), ctx_len=torch.zeros(1, **i32),  # slot 0's prompt history
+            # the prompt history of slots 0 .. SB - 1
+            ctx=torch.zeros(SB, self.max_model_len, **i32), ctx_len=torch.zeros(SB, **i32),
             ids=torch.zeros(TM, **i32), pos=torch.zeros(TM, **i32), draft=torch.full((TM,), -1, **i32),
-            seq0=torch.zeros(TM, **i32), stats=torch.zeros(3, dtype=torch.int64, device=dev),
+            # seq0[T]: the sequence (block-table row) of verify row i = i // T
+            seq0={T: (torch.arange(TM, device=dev) // T).to(torch.int32) for T in range(1, 9)},
+            stats=torch.zeros(max(SB, 1), 3, dtype=torch.int64, device=dev),
             h=torch.zeros(TM, self.d, **f32), xn=torch.zeros(TM, self.d, **bf), q=torch.zeros(TM, self.H, self.D, **bf),
             attn=torch.zeros(TM, self.H * self.D, **bf), act=torch.zeros(TM, self.ffn_l, **bf),
             o_buf=torch.zeros(8 * TM * self.d, **f32), down_buf=torch.zeros(8 * TM * self.d, **f32),
@@ -794,12 +825,13 @@ class ModelRunner:
             # sampled verify steps (ops.spec_sample_commit): the rows' top-k candidates and their picked tokens
             cand=torch.zeros(TM * ((self.V + 2047) // 2048) * 64, dtype=torch.int64, device=dev),
             picks=torch.zeros(TM, **i32),
-            attn_ws=ops.verify_workspace(TM, self.H, self.Hkv, nsplit_max, dev))
+            attn_ws=ops.verify_workspace(TM, self.H, self.Hkv, nsplit_max, dev))  # (TM rows = S * T)
         return self._spec
 
     def set_spec_forced(self, table: Optional[torch.Tensor]) -> None:
         """Plant the drafts of the next verify steps instead of searching: ``table`` [nf, k] int32, a step whose row
-        has generated g tokens drafts row min(g, nf - 1) (None restores the n-gram search).  One device buffer per
+        has generated g tokens drafts row min(g, nf - 1) (None restores the n-gram search); ``table`` [S, nf, k] plants
+        table s in the sequence of slot s (S >= the S of the verify steps that read it).  One device buffer per
         table shape, rewritten in place: a captured verify graph is keyed by the buffer it reads."""
         if table is None:
             self._spec_forced = None
@@ -811,16 +843,24 @@ class ModelRunner:
         buf.copy_(table.to(torch.int32))
         self._spec_forced = buf
 
-    def _verify_step(self, plan: Optional[tuple] = None, guided: bool = False, sample: bool = False) -> None:
+    def _verify_step(self, plan: Optional[tuple] = None, guided: bool = False, sample: bool = False, S: int = 1) -> None:
         """One speculative-decoding step of the request in slot 0: a forward pass over T = k + 1 rows -- the row's input
         token and k drafted tokens at positions p .. p + T - 1 -- and the in-order commit of the tokens greedy decoding
         would have produced (``ops.spec_commit``): between 1 and T per step, the same sequence as plain steps.
+
+        ``S`` > 1 (``spec_batch``; greedy, unconstrained): the same launches over the S sequences of slots 0 .. S - 1,
+        S * T rows with row-major activations throughout -- rows s T .. s T + T - 1 are sequence s: its state row,
+        ``block_tables[s]``, ``positions[s]``; the GEMMs and their split-K are those of S * T rows, ``attn_verify`` runs
+        the S sequences in one launch and ``spec_commit`` commits each into its own state row and counts in its own
+        row of ``stats``.  A slot below S without a request is the row ``release_slot`` leaves -- finished, position 0,
+        a block table of zeros: it rewrites T rows of scratch block 0, commits nothing and counts nothing.
 
           spec_draft -> embed -> per layer: gemm qkv (f32 slabs) -> rope_append (RoPE + the T K/V rows into the cache)
           -> attn_verify (all T rows share one pass over the cache) -> gemm o -> norm -> gemm gate_up -> gemm down
           -> final norm -> lm_head over T rows -> spec_commit
 
-        KV invariant: a step writes cache positions p .. p + T - 1 and advances to p' = p + a + 1 (a accepted drafts).
+        KV invariant, per sequence (a sequence writes only the blocks of its own table, whatever its neighbours accept):
+        a step writes cache positions p .. p + T - 1 and advances to p' = p + a + 1 (a accepted drafts).
         The stale rows p' .. p + T - 1 lie inside the next step's write range p' .. p' + T - 1, so the next step (or
         the next plain step, which writes p' before reading it) overwrites them before any query can see them: row t
         sees only keys <= p' + t.  A finished row keeps its position and rewrites the same T positions when the graph
@@ -844,12 +884,16 @@ class ModelRunner:
         the committed tokens are the plain sampled tokens of the same seed.  A rejected row's draw counter is used
         again by the next step, as the plain path would use it.  With ``guided`` the mask runs before it (a -inf logit
         stays -inf under the penalty and is never kept by the sampler) and the DFA hand-over after it, unchanged."""
-        w, d, T = self.w, self.d, self.spec_k() + 1
+        w, d, Ts = self.w, self.d, self.spec_k() + 1
         sb = self._spec_bufs()
+        assert S == 1 or not (guided or sample), "guided and sampled verify steps are one-sequence"
+        assert 1 <= S <= sb["ctx"].shape[0] and S * Ts <= 32, "verify step: S <= spec_batch sequences, S * T <= 32 rows"
+        T = S * Ts  # rows of the step from here on
         n_max, n_min = self.spec_ngram
-        st = (self.out_tokens[:1], self.gen_len[:1], self.input_ids[:1], self.positions[:1], self.finished[:1])
-        ids, pos, bt = sb["ids"][:T], sb["pos"][:T], self.block_tables[:1]
-        ops.spec_draft(sb["ctx"], sb["ctx_len"], st[0], st[1], st[2], st[3], T - 1, ids, pos, sb["draft"][:T - 1],
+        st = (self.out_tokens[:S], self.gen_len[:S], self.input_ids[:S], self.positions[:S], self.finished[:S])
+        ids, pos, bt = sb["ids"][:T], sb["pos"][:T], self.block_tables[:S]
+        draft = sb["draft"][:S * (Ts - 1)]
+        ops.spec_draft(sb["ctx"][:S], sb["ctx_len"][:S], st[0], st[1], st[2], st[3], Ts - 1, ids, pos, draft,
                        n_max=n_max, n_min=n_min, forced=self._spec_forced)
         h, xn, attn, act, q = sb["h"][:T], sb["xn"][:T], sb["attn"][:T], sb["act"][:T], sb["q"][:T]
         nqkv = (self.H + 2 * self.Hkv) * self.D
@@ -880,10 +924,14 @@ class ModelRunner:
             pre = {} if (self.on_gpu or l) else dict(pre=True)
             lin(xn, lw.wqkv, "f32", out=qkv_parts, splitk=sk_q, **rn(2 * l), **pre)
             kc, vc = self.kv[l, 0], self.kv[l, 1]
-            ops.rope_append(qkv_parts, pos, sb["seq0"][:T], bt, self.cos, self.sin, q, kc, vc, self.H, self.Hkv,
+            ops.rope_append(qkv_parts, pos, sb["seq0"][Ts][:T], bt, self.cos, self.sin, q, kc, vc, self.H, self.Hkv,
                             kv_scales=kvs(l))
-            ops.attn_verify(q, kc, vc, bt, pos[:1], self.H, self.Hkv, self.scale, attn, workspace=sb["attn_ws"],
-                            plan=plan, kv_scales=kvs(l))
+            if S == 1:
+                ops.attn_verify(q, kc, vc, bt, pos[:1], self.H, self.Hkv, self.scale, attn, workspace=sb["attn_ws"],
+                                plan=plan, kv_scales=kvs(l))
+            else:  # (positions[:S] are the sequences' pos0: spec_draft copied them into pos[s * Ts])
+                ops.attn_verify(q.view(S, Ts, self.H, self.D), kc, vc, bt, st[3], self.H, self.Hkv, self.scale, attn,
+                                workspace=sb["attn_ws"], plan=plan, kv_scales=kvs(l))
             lin(attn, lw.wo, "f32", out=o_parts, splitk=sk_o)
             if wn:
                 ops.res_add_ss(h, o_parts, xn, T, ssq[2 * l + 1])
@@ -897,16 +945,16 @@ class ModelRunner:
         if guided:
             ops.dfa_mask_verify(logits, self.g_tok_off, self.g_tok_blob, self.g_cls, self.g_trans, self.g_accept,
                                 self.g_dim, self.g_on, self.g_state, self.g_base, st[1], st[2], st[4], self.eos,
-                                sb["draft"][:T - 1], self.g_spec)
+                                draft, self.g_spec)
         if sample:
-            ops.spec_sample_commit(logits, sb["draft"][:T - 1], sb["stats"], self.hist[:1], self.penalty[:1],
+            ops.spec_sample_commit(logits, draft, sb["stats"][0], self.hist[:1], self.penalty[:1],
                                    self.temperature[:1], self.top_k[:1], self.top_p[:1], self.seeds[:1], *st, self.eos,
                                    self.limit[:1], self.eos_on[:1],
                                    workspace=(sb["amax_part"], sb["cand"], sb["picks"]) if self.on_gpu else None,
                                    last_n=self.last_n[:1])
         else:
-            ops.spec_commit(logits, sb["draft"][:T - 1], sb["stats"], *st, self.eos, self.limit[:1], self.eos_on[:1],
-                            part=sb["amax_part"] if self.on_gpu else None)
+            ops.spec_commit(logits, draft, sb["stats"][0] if S == 1 else sb["stats"][:S], *st, self.eos, self.limit[:S],
+                            self.eos_on[:S], part=sb["amax_part"] if self.on_gpu else None)
         if guided:
             ops.dfa_spec_advance(self.g_on, self.g_state, self.g_spec, st[1], T - 1)
 
@@ -936,37 +984,48 @@ class ModelRunner:
             (out[0, i] if (epi == "f32" and out.dim() == 3) else out[i]).copy_(y.reshape(-1))
         return out
 
-    def spec_logits(self) -> torch.Tensor:
+    def spec_logits(self, S: int = 1) -> torch.Tensor:
         """[T, V] f32: the verify rows of the last verify step (the numerics check reads them).  After a guided and /
         or sampled verify step they are the rows as the commit read them: masked (-inf) and with the repetition
-        penalty of a sampled step applied."""
-        return self._spec_bufs()["logits"][: self.spec_k() + 1]
+        penalty of a sampled step applied.  ``S`` > 1: [S, T, V], the rows of a step over S sequences."""
+        T = self.spec_k() + 1
+        rows = self._spec_bufs()["logits"][: S * T]
+        return rows if S == 1 else rows.view(S, T, -1)
 
-    def spec_drafts(self) -> torch.Tensor:
-        """[k] int32: the drafts of the last verify step (-1 = none)."""
-        return self._spec_bufs()["draft"][: self.spec_k()]
+    def spec_drafts(self, S: int = 1) -> torch.Tensor:
+        """[k] int32: the drafts of the last verify step (-1 = none).  ``S`` > 1: [S, k]."""
+        k = self.spec_k()
+        d = self._spec_bufs()["draft"][: S * k]
+        return d if S == 1 else d.view(S, k)
 
     def decode_spec(self, steps: int, max_ctx: Optional[int] = None, guided: bool = False,
-                    sample: bool = False) -> None:
+                    sample: bool = False, S: int = 1) -> None:
         """Run ``steps`` verify steps of the request in slot 0 (the analogue of ``decode`` at bucket 1); ``max_ctx``
         bounds pos0 + T during the run (picks the split plan's tier).  ``guided``: the variant with the regex mask of
         the verify rows, for a constrained request (its graph key is the unguided one with a trailing True).
         ``sample``: the variant that ends in the sampled commit, for a request that needs the sampler (its graph key
-        is the greedy one with a trailing "sample"; the greedy graphs and their keys are untouched)."""
+        is the greedy one with a trailing "sample"; the greedy graphs and their keys are untouched).
+        ``S`` > 1: verify steps over the sequences of slots 0 .. S - 1 (``_verify_step(S=)``), one graph per (S, T,
+        plan, forced buffer): the split plan is the decode plan of bucket S, the key the one-sequence key with S
+        appended."""
         assert self.spec_supported(), ("speculative decoding: TP = 1, spec_tokens > 0, bf16 weights and KV cache "
                                        "(or spec_quantized)")
         assert not guided or (self.guided and self.spec_guided), "guided verify steps need enable_guided() and spec_guided"
         assert not sample or self.spec_sampled, "sampled verify steps need spec_sampled"
-        plan = tuple(self.ctx_plan(1, max_ctx))
+        assert S == 1 or (S <= self.spec_s() and not guided and not sample), \
+            "verify steps over several sequences: S <= spec_batch (clamped), greedy and unconstrained"
+        plan = tuple(self.ctx_plan(S, max_ctx))
         if not self.use_graphs:
             for _ in range(steps):
-                self._verify_step(plan, guided, sample)
+                self._verify_step(plan, guided, sample, S)
             return
         key = ("spec", self.spec_k() + 1, plan, 0 if self._spec_forced is None else self._spec_forced.data_ptr())
         if guided:
             key += (True,)
         if sample:
             key += ("sample",)
+        if S > 1:
+            key += (S,)
         if key not in self.graphs:
             self._spec_bufs()
             s = torch.cuda.Stream(device=self.device)
@@ -974,7 +1033,7 @@ class ModelRunner:
             g = torch.cuda.CUDAGraph()
             with torch.cuda.stream(s):
                 with torch.cuda.graph(g, stream=s):
-                    self._verify_step(plan, guided, sample)
+                    self._verify_step(plan, guided, sample, S)
             torch.cuda.current_stream(self.device).wait_stream(s)
             self.graphs[key] = g
         g = self.graphs[key]
@@ -982,12 +1041,16 @@ class ModelRunner:
             g.replay()
 
     def spec_counts(self) -> tuple[int, int, int]:
-        """(verify steps, drafted tokens, accepted tokens) since the runner was built (a device -> host read: call it
-        after the sync a decode run ends with)."""
-        if self._spec is None:
-            return (0, 0, 0)
-        a, b, c = self._spec["stats"].tolist()
+        """(verify steps, drafted tokens, accepted tokens) since the runner was built, summed over the sequences (a
+        device -> host read: call it after the sync a decode run ends with)."""
+        a, b, c = (sum(col) for col in zip(*self.spec_row_counts())) if self._spec is not None else (0, 0, 0)
         return int(a), int(b), int(c)
+
+    def spec_row_counts(self) -> list[list[int]]:
+        """[S, 3]: ``spec_counts`` per sequence (row s = the verify steps that ran with slot s live)."""
+        if self._spec is None:
+            return [[0, 0, 0] for _ in range(self.spec_s())]
+        return self._spec["stats"].tolist()
 
     # ------------------------------------------------------------------------------------ regex-constrained decoding
     def enable_guided(self, tok_off, tok_blob) -> None:
@@ -1069,9 +1132,10 @@ class ModelRunner:
         if not entries:
             return
         n, W, mb = len(entries), REPEAT_WINDOW, self.max_blocks
-        # speculative decoding: slot 0's context history (its length, then the tokens) rides in the same transfer
-        sx = (1 + self.max_model_len) if (self.spec_tokens > 0 and self.spec_supported()
-                                          and any(int(e["slot"]) == 0 for e in entries)) else 0
+        # speculative decoding: the context history (its length, then the tokens) of every slot < spec_batch rides in
+        # the same transfer
+        SB = self.spec_s() if (self.spec_tokens > 0 and self.spec_supported()) else 0
+        sx = (1 + self.max_model_len) if any(int(e["slot"]) < SB for e in entries) else 0
         ints = torch.zeros(n, mb + 5 + sx, dtype=torch.int32)  # block-table row | limit top_k eos_on last_n visible
         flts = torch.zeros(n, 3, dtype=torch.float32)     # temperature top_p penalty
         seeds = torch.zeros(n, dtype=torch.int64)
@@ -1083,7 +1147,7 @@ class ModelRunner:
             ints[i, mb:mb + 5] = torch.tensor([min(int(e["limit"]), self.max_new_cap), int(e.get("top_k", 40)),
                                                1 if e.get("eos_on", True) else 0, last_n,
                                                0 if e.get("defer_table", False) else 1], dtype=torch.int32)
-            if sx and int(e["slot"]) == 0:
+            if sx and int(e["slot"]) < SB:
                 pids = list(e.get("prompt_ids", ()))[: self.max_model_len]
                 ints[i, mb + 5] = len(pids)
                 ints[i, mb + 6: mb + 6 + len(pids)] = torch.tensor(pids, dtype=torch.int32)
@@ -1112,9 +1176,10 @@ class ModelRunner:
         self.block_tables.index_copy_(0, idx, dv[:, :mb] * dv[:, mb + 4:mb + 5])  # deferred rows stay zero
         if sx:
             sb = self._spec_bufs()
-            i0 = next(i for i, sl in enumerate(slots) if sl == 0)
-            sb["ctx_len"].copy_(dv[i0, mb + 5:mb + 6])
-            sb["ctx"].copy_(dv[i0:i0 + 1, mb + 6:])
+            for i, sl in enumerate(slots):
+                if sl < SB:
+                    sb["ctx_len"][sl:sl + 1].copy_(dv[i, mb + 5:mb + 6])
+                    sb["ctx"][sl:sl + 1].copy_(dv[i:i + 1, mb + 6:])
         self.limit.index_copy_(0, idx, dv[:, mb])
         self.top_k.index_copy_(0, idx, dv[:, mb + 1])
         self.eos_on.index_copy_(0, idx, dv[:, mb + 2])

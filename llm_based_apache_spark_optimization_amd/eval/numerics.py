@@ -261,11 +261,15 @@ def record_spec_logits(eng, prompt: Sequence[int], n_tokens: int, hidden: Option
     row_argmax ([T] argmax of every verify row).
     ``params``: the request's ``SamplingParams`` instead of the greedy ones (None) -- a sampled request on a
     ``spec_sampled`` engine; its max_tokens and ignore_eos are set as the greedy request's.  The recorded rows of a
-    sampled verify step are the rows its commit read: with the repetition penalty applied."""
+    sampled verify step are the rows its commit read: with the repetition penalty applied.
+    Several prompts (a list of token lists, ``spec_batch`` engines): ``record_spec_logits_batch``."""
     import dataclasses
 
     from ..engine import SamplingParams
 
+    if len(prompt) and isinstance(prompt[0], (list, tuple)):
+        assert params is None, "several requests speculate together only when greedy"
+        return record_spec_logits_batch(eng, prompt, n_tokens, hidden)
     r = eng.runner
     hidden = tied(r.w) if hidden is None else hidden
     old = eng.run_ahead
@@ -308,9 +312,82 @@ def record_spec_logits(eng, prompt: Sequence[int], n_tokens: int, hidden: Option
         eng.run_ahead = old
 
 
-def teacher_forced_check_spec(eng, prompt: Sequence[int], n_tokens: int = 64, weights=None) -> dict:
+def record_spec_logits_batch(eng, prompts: Sequence[Sequence[int]], n_tokens: int, hidden: Optional[bool] = None):
+    """``record_spec_logits`` of several greedy requests sent at once (``spec_batch``): one decode run of one step per
+    engine iteration, recorded per request.  Returns (tokens: one list per request, logits [n, n_tokens, V] f32, steps:
+    one list of step dicts per request).  A request's verify rows are rows slot * T .. slot * T + T - 1 of the step's
+    buffers whatever S the step ran at; an iteration that ran plain steps (the run was gated, or the request was left
+    alone in a slot other than 0) is recorded from the plain step's logits row, spec = False."""
+    from ..engine import SamplingParams
+
+    r = eng.runner
+    hidden = tied(r.w) if hidden is None else hidden
+    old = eng.run_ahead
+    eng.run_ahead = 1
+    try:
+        sp = SamplingParams(max_tokens=n_tokens + 1, temperature=0.0, ignore_eos=True)
+        qs = [eng.add_request(list(p), sp) for p in prompts]
+        n = len(qs)
+        out = torch.zeros(n, n_tokens, r.V, dtype=torch.float32, device=r.device)
+        hid = torch.zeros(n, n_tokens, r.d, dtype=torch.float32, device=r.device) if hidden else None
+        steps, have, slots = [[] for _ in qs], [0] * n, [-1] * n
+        T = r.spec_k() + 1
+        while not all(q.done.is_set() for q in qs):
+            before = r.spec_row_counts()
+            slots = [q.slot if q.slot >= 0 else s_ for q, s_ in zip(qs, slots)]
+            live = [not q.done.is_set() for q in qs]
+            eng.step()
+            after = r.spec_row_counts()
+            slots = [q.slot if (live[i] and q.slot >= 0) else slots[i] for i, q in enumerate(qs)]
+            Bp = r.bucket(max([s_ for s_, lv in zip(slots, live) if lv and s_ >= 0] + [0]) + 1)  # a plain run's bucket
+            for i, q in enumerate(qs):
+                if not live[i]:
+                    continue
+                now = len(q.output_ids) if q.done.is_set() else q.gen_host
+                c = now - have[i]
+                if have[i] == 0:  # the prefill's token; a decode run may have followed in the same iteration
+                    if now == 0:
+                        continue
+                    c, have[i] = now - 1, 1
+                if c <= 0:
+                    continue
+                slot = slots[i]
+                spec = slot < len(after) and after[slot][0] > (before[slot][0] if slot < len(before) else 0)
+                sb = r._spec_bufs()
+                rows = sb["logits"][slot * T:slot * T + T] if spec else r.logits[slot:slot + 1]
+                xh = ((sb["xn"][slot * T:slot * T + T] if spec else r.final_hidden(Bp)[slot:slot + 1]) if hidden
+                      else None)
+                assert c <= rows.shape[0], (c, rows.shape)
+                for t in range(c):
+                    j = have[i] + t  # token index chosen by row t
+                    if 1 <= j <= n_tokens:
+                        out[i, j - 1].copy_(rows[t].float())
+                        if hidden:
+                            hid[i, j - 1].copy_(xh[t].float())
+                rec = dict(first=have[i], committed=c, spec=bool(spec))
+                if spec:
+                    rec.update(draft=sb["draft"][slot * (T - 1):(slot + 1) * (T - 1)].tolist(),
+                               row_argmax=rows.float().argmax(-1).tolist())
+                steps[i].append(rec)
+                have[i] = now
+        return [q.output_ids for q in qs], ((out, hid) if hidden else out), steps
+    finally:
+        eng.run_ahead = old
+
+
+def teacher_forced_check_spec(eng, prompt: Sequence[int], n_tokens: int = 64, weights=None):
     """``teacher_forced_check`` of the verify steps: every token a verify step committed, its verify-row logits against
-    the oracle under the verify rows' plan and threshold class (``check_recorded(spec_steps=)``)."""
+    the oracle under the verify rows' plan and threshold class (``check_recorded(spec_steps=)``).  Several prompts (a
+    list of token lists, sent at once to a ``spec_batch`` engine): one result per request, each over its own tokens."""
+    if len(prompt) and isinstance(prompt[0], (list, tuple)):
+        toks, elog, steps = record_spec_logits_batch(eng, prompt, n_tokens)
+        out = []
+        for i, p in enumerate(prompt):
+            one = tuple(e[i:i + 1] for e in elog) if isinstance(elog, tuple) else elog[i:i + 1]
+            res = check_recorded(eng, [list(p)], [toks[i]], one, n_tokens, (0,), weights, spec_steps=steps[i])
+            res["verify_steps"] = sum(1 for s_ in steps[i] if s_["spec"])
+            out.append(res)
+        return out
     toks, elog, steps = record_spec_logits(eng, prompt, n_tokens)
     res = check_recorded(eng, [list(prompt)], [toks], elog, n_tokens, (0,), weights, spec_steps=steps)
     res["verify_steps"] = sum(1 for s_ in steps if s_["spec"])

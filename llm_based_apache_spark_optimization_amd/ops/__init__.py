@@ -1549,16 +1549,16 @@ def sample_commit(logits, hist, penalty, temperature, top_k, top_p, seeds, out_t
 
 
 # ----------------------------------------------------------------------------------- speculative decoding
-def verify_split_plan(Hkv: int, max_ctx: int) -> tuple[int, int, int]:
-    """(chunk_blocks, nsplit, unsplit_max) of ``attn_verify`` for contexts (pos0 + T) up to max_ctx: the batch-1
-    decode plan -- one workgroup per (kv head, split) either way."""
-    return decode_split_plan(1, Hkv, max_ctx)
+def verify_split_plan(Hkv: int, max_ctx: int, S: int = 1) -> tuple[int, int, int]:
+    """(chunk_blocks, nsplit, unsplit_max) of ``attn_verify`` over S sequences for contexts (pos0 + T) up to max_ctx:
+    the batch-S decode plan -- one workgroup per (sequence, kv head, split) either way."""
+    return decode_split_plan(S, Hkv, max_ctx)
 
 
-def verify_workspace(T: int, H: int, Hkv: int, nsplit: int, device) -> tuple:
-    """(opart, mlpart, counters) of ``attn_verify``: the split partials of T * H query rows and Hkv arrival tickets
-    (start zeroed; the kernel leaves them zeroed)."""
-    return decode_workspace(T, H, Hkv, nsplit, device)
+def verify_workspace(T: int, H: int, Hkv: int, nsplit: int, device, S: int = 1) -> tuple:
+    """(opart, mlpart, counters) of ``attn_verify``: the split partials of S * T * H query rows and (at least) S * Hkv
+    arrival tickets (start zeroed; the kernel leaves them zeroed)."""
+    return decode_workspace(S * T, H, Hkv, nsplit, device)
 
 
 def attn_verify(q, kc, vc, block_table, pos0, H, Hkv, scale, out, workspace=None, plan=None, kv_scales=None):
@@ -1566,15 +1566,21 @@ def attn_verify(q, kc, vc, block_table, pos0, H, Hkv, scale, out, workspace=None
     table row is ``block_table``, at positions pos0 .. pos0 + T - 1 (``pos0``: int32 tensor, read on the device); their
     K / V are already in the cache (``rope_append``): bf16, or -- ``kv_scales`` = (ks, vs) -- the fp8 cache's e4m3
     bytes with their per-(token, kv-head) scales.  Row t sees keys j <= pos0 + t.  out [T, H * 128] bf16.
-    T <= 8 and T * H / Hkv <= 16."""
-    T = q.shape[0]
+    T <= 8 and T * H / Hkv <= 16.
+    Several sequences in one launch: q [S, T, H, 128], block_table [S, max_blocks], pos0 [S], out [S * T, H * 128], with
+    1 <= S <= 8 and S * T <= 32; every sequence computes exactly what its own one-sequence launch computes."""
+    S, T = (q.shape[0], q.shape[1]) if q.dim() == 4 else (1, q.shape[0])
+    if q.dim() not in (3, 4) or not 1 <= S <= 8 or S * T > 32:
+        raise ValueError("attn_verify: q [T, H, 128] or [S, T, H, 128] with 1 <= S <= 8 and S * T <= 32")
+    if q.dim() == 4 and (block_table.dim() != 2 or block_table.shape[0] != S or pos0.numel() < S):
+        raise ValueError("attn_verify: q [S, T, H, 128] needs block_table [S, max_blocks] and pos0 [S]")
     if not _gpu(q):
         return ref.attn_verify(q, kc, vc, block_table, pos0, H, Hkv, scale, out, kv_scales)
-    plan = plan if plan is not None else verify_split_plan(Hkv, block_table.numel() * 64)
+    plan = plan if plan is not None else verify_split_plan(Hkv, block_table.numel() // S * 64, S)
     chunk, nsplit = plan[0], plan[1]
     unsplit_max = plan[2] if len(plan) > 2 else 4
     if workspace is None:
-        workspace = verify_workspace(T, H, Hkv, nsplit, q.device)
+        workspace = verify_workspace(T, H, Hkv, nsplit, q.device, S)
     opart, mlpart, counters = workspace
     ks, vs = kv_scales if kv_scales is not None else (None, None)
     ext().attn_verify(q, kc, vc, block_table, pos0, H, Hkv, scale, chunk, nsplit, unsplit_max, out, opart, mlpart,
@@ -1608,7 +1614,9 @@ def kv_copy_blocks(kv: torch.Tensor, kv_scale: Optional[torch.Tensor], pairs) ->
 def spec_draft(prompt_tok, prompt_len, out_tokens, gen_len, input_ids, positions, k, spec_ids, spec_pos, spec_draft_out,
                n_max: int = 3, n_min: int = 1, forced=None):
     """Prompt-lookup drafter, one row per entry of ``prompt_len`` (kernels/spec.hip).  forced [nf, k] int32 replaces
-    the search: the draft is its row min(gen_len, nf - 1)."""
+    the search: the draft is its row min(gen_len, nf - 1); forced [rows, nf, k] plants table s in row s."""
+    if forced is not None and forced.dim() == 3 and (forced.shape[0] < prompt_len.numel() or forced.shape[2] != k):
+        raise ValueError("spec_draft: forced [rows, nf, k] needs one table per row")
     if not _gpu(prompt_tok):
         return ref.spec_draft(prompt_tok, prompt_len, out_tokens, gen_len, input_ids, positions, k, n_max, n_min,
                               forced, spec_ids, spec_pos, spec_draft_out)
@@ -1620,9 +1628,13 @@ def spec_commit(logits, draft, stats, out_tokens, gen_len, input_ids, positions,
                 eos_on=None, part=None):
     """Greedy verification of the T = k + 1 verify rows ``logits`` of the sequence in state row 0 and the in-order
     commit of the accepted tokens (kernels/sampling.hip spec_commit_kernel); stats int64 [3] += (steps, drafted,
-    accepted)."""
-    T, V = logits.shape
-    limit, eos_on = _row_defaults(1, out_tokens, limit, eos_on)
+    accepted).  stats [S, 3]: ``logits`` [S * T, V] and ``draft`` [S, k] are the rows of S sequences (S * T <= 32),
+    sequence s commits into state row s and counts in stats[s]."""
+    T, V = logits.shape  # (all S * T rows)
+    S = stats.shape[0] if stats.dim() == 2 else 1
+    if T % S or T // S < 2 or (S > 1 and T > 32):
+        raise ValueError("spec_commit: logits [S * T, V] with T >= 2 and S * T <= 32")
+    limit, eos_on = _row_defaults(S, out_tokens, limit, eos_on)
     if not _gpu(logits):
         return ref.spec_commit(logits, draft, stats, out_tokens, gen_len, input_ids, positions, finished, eos, limit,
                                eos_on)

@@ -342,13 +342,17 @@ def kv_copy_blocks(kv, kv_scale, pairs):
 
 # ----------------------------------------------------------------------------------- speculative decoding
 def attn_verify(q, kc, vc, block_table, pos0, H, Hkv, scale, out, kv_scales=None):
-    """Attention of the T = q.shape[0] new tokens of ONE sequence (their K / V already appended): row t is a decode
-    query at position pos0 + t, so it sees keys j <= pos0 + t.  ``kv_scales``: the fp8 cache's (ks, vs)."""
-    T = q.shape[0]
-    p0 = int(pos0.reshape(-1)[0])
-    pos = torch.arange(p0, p0 + T, dtype=torch.int32, device=q.device)
-    bt = block_table.reshape(1, -1).expand(T, -1)
-    return attn_decode(q, kc, vc, bt, pos, H, Hkv, scale, out.view(T, H, -1), kv_scales)
+    """Attention of the T new tokens of each sequence (their K / V already appended): q [T, H, D] with one block-table
+    row, or q [S, T, H, D] with block_table [S, max_blocks] and pos0 [S].  Row t of sequence s is a decode query at
+    position pos0[s] + t, so it sees keys j <= pos0[s] + t.  ``kv_scales``: the fp8 cache's (ks, vs)."""
+    S, T = (q.shape[0], q.shape[1]) if q.dim() == 4 else (1, q.shape[0])
+    qs, o = q.reshape(S, T, H, -1), out.view(-1)[: q.numel()].view(S, T, H, -1)
+    for s in range(S):  # one sequence after the other: nothing of a sequence depends on its neighbours
+        p0 = int(pos0.reshape(-1)[s])
+        pos = torch.arange(p0, p0 + T, dtype=torch.int32, device=q.device)
+        bt = block_table.reshape(S, -1)[s:s + 1].expand(T, -1)
+        attn_decode(qs[s], kc, vc, bt, pos, H, Hkv, scale, o[s], kv_scales)
+    return out
 
 
 def spec_draft(prompt_tok, prompt_len, out_tokens, gen_len, input_ids, positions, k, n_max, n_min, forced,
@@ -363,7 +367,7 @@ def spec_draft(prompt_tok, prompt_len, out_tokens, gen_len, input_ids, positions
         gl = min(max(int(gen_len[row]), 0), out_tokens.shape[1])
         draft = [-1] * k
         if forced is not None:
-            f = forced.reshape(-1, k)
+            f = forced[row] if forced.dim() == 3 else forced.reshape(-1, k)  # [rows, nf, k]: row s plants table s
             draft = [int(x) for x in f[min(gl, f.shape[0] - 1)]]
         else:
             ctx = torch.cat([prompt_tok[row, :pl], out_tokens[row, :gl]]).long()
@@ -389,24 +393,32 @@ def spec_draft(prompt_tok, prompt_len, out_tokens, gen_len, input_ids, positions
 
 def spec_commit(logits, draft, stats, out_tokens, gen_len, input_ids, positions, finished, eos, limit=None,
                 eos_on=None):
-    """logits [T, V]: the verify rows of the sequence in state row 0.  Commits tok_0 .. tok_a in order (a = leading
-    drafts equal to the argmax of their row), stopping after a finishing token; stats += (1, drafts >= 0, tokens
-    committed beyond the first).  A finished row changes nothing."""
-    if int(finished[0]):
-        return
-    T = logits.shape[0]
+    """stats [3]: logits [T, V] are the verify rows of the sequence in state row 0; stats [S, 3]: logits [S * T, V],
+    rows s T .. s T + T - 1 belong to state row s and are verified against draft[s (T - 1) ..].  Per sequence: commits
+    tok_0 .. tok_a in order (a = leading drafts equal to the argmax of their row), stopping after a finishing token;
+    stats[s] += (1, drafts >= 0, tokens committed beyond the first).  A finished row changes and counts nothing."""
+    S = stats.shape[0] if stats.dim() == 2 else 1
+    T = logits.shape[0] // S
+    k = T - 1
     toks = logits.float().argmax(-1)
-    committed = 0
-    for i in range(T):
-        if int(finished[0]):
-            break
-        commit(toks[i:i + 1], out_tokens, gen_len, input_ids, positions, finished, eos, limit, eos_on)
-        committed += 1
-        if i >= T - 1 or int(draft[i]) < 0 or int(draft[i]) != int(toks[i]):
-            break
-    stats[0] += 1
-    stats[1] += int((draft[:T - 1] >= 0).sum())
-    stats[2] += max(committed - 1, 0)
+    for s in range(S):
+        if int(finished[s]):
+            continue
+        row = lambda t: t[s:s + 1] if t is not None else None  # noqa: E731  (commit works on row 0 of what it is given)
+        dr = draft.reshape(-1)[s * k:(s + 1) * k]
+        committed = 0
+        for i in range(T):
+            if int(finished[s]):
+                break
+            commit(toks[s * T + i:s * T + i + 1], out_tokens[s:s + 1], gen_len[s:s + 1], input_ids[s:s + 1],
+                   positions[s:s + 1], finished[s:s + 1], eos, row(limit), row(eos_on))
+            committed += 1
+            if i >= T - 1 or int(dr[i]) < 0 or int(dr[i]) != int(toks[s * T + i]):
+                break
+        st = stats.view(-1, 3)[s]
+        st[0] += 1
+        st[1] += int((dr >= 0).sum())
+        st[2] += max(committed - 1, 0)
 
 
 def sample_probs(logits_row: torch.Tensor, temperature: float, top_k: int, top_p: float, topk_cap: int = 64):

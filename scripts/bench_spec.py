@@ -19,12 +19,23 @@ profiles/spec/spec_sampled_mi355x.jsonl:
            against on with the n-gram drafter (its acceptance counts recorded) and with planted acceptance 0, about
            half, and all.
 
+With --batch 2,4,8: speculative decoding of several greedy requests at once (``spec_batch``), k = 3, appended to
+profiles/spec/spec_batch_mi355x.jsonl:
+
+  kernel   attn_verify over S sequences in one launch beside S one-sequence launches and beside attn_decode at
+           batch S (one row per sequence).
+  step     device time of a verify step over S sequences (S x 4 rows, planted all-wrong drafts) against the plain
+           step of bucket S decoding the same S requests; ratio - 1 = the accepted drafts per step and request at
+           which the verify step breaks even.
+  e2e      decode tokens/s of the S requests together: plain, and planted acceptance none / about half / all.
+
 Every graph is warmed, times are device events, the arms alternate within one process.  Appends JSON lines to
 profiles/spec/spec_decode_mi355x.jsonl, or -- with quantised weights or the fp8 cache (``spec_quantized`` engines) --
 to profiles/spec/spec_decode_quant_mi355x.jsonl (--out overrides).  Needs a GPU.
 
   python scripts/bench_spec.py [--layers N] [--skip kernel,step,e2e] [--reps 5] [--dtype bf16|fp8|mxfp4]
                                [--kv-dtype bf16|fp8] [--models duckdb-nsql,llama3.2] [--out FILE] [--sampled]
+                               [--batch 2,4,8]
 """
 from __future__ import annotations
 
@@ -49,6 +60,7 @@ from llm_based_apache_spark_optimization_amd.ops import reference as ref  # noqa
 OUT = os.path.join(ROOT, "profiles", "spec", "spec_decode_mi355x.jsonl")
 OUT_QUANT = os.path.join(ROOT, "profiles", "spec", "spec_decode_quant_mi355x.jsonl")
 OUT_SAMPLED = os.path.join(ROOT, "profiles", "spec", "spec_sampled_mi355x.jsonl")
+OUT_BATCH = os.path.join(ROOT, "profiles", "spec", "spec_batch_mi355x.jsonl")
 OLLAMA = dict(temperature=0.8, top_k=40, top_p=0.9, repeat_penalty=1.1)  # Ollama's default option set
 
 
@@ -301,6 +313,113 @@ def bench_sampled_engine(dev, layers, reps: int, models=(), k: int = 3, seed: in
         torch.cuda.empty_cache()
 
 
+def bench_batch_kernel(dev, reps: int, Ss, T: int = 4) -> None:
+    """attn_verify over S sequences of T rows: one launch, S one-sequence launches, and attn_decode at batch S."""
+    D = 128
+    for name, H, Hkv, ctx in (("duckdb-nsql-7b", 32, 32, 256), ("llama3.2-3b", 24, 8, 2176)):
+        for S in Ss:
+            mb = (ctx + 63) // 64 + 1
+            g = torch.Generator().manual_seed(ctx + S)
+            kc = (torch.randn(S * mb + 1, Hkv, 64, D, generator=g) * 0.5).to(torch.bfloat16).to(dev)
+            vc = (torch.randn(S * mb + 1, Hkv, 64, D, generator=g) * 0.5).to(torch.bfloat16).to(dev)
+            bts = (torch.arange(S * mb, dtype=torch.int32) + 1).view(S, mb).to(dev)  # S disjoint sequences
+            q = (torch.randn(S, T, H, D, generator=g) * 0.7).to(torch.bfloat16).to(dev)
+            out = torch.zeros(S * T, H * D, dtype=torch.bfloat16, device=dev)
+            pos0 = torch.full((S,), ctx - T, dtype=torch.int32, device=dev)
+            posS = torch.full((S,), ctx - 1, dtype=torch.int32, device=dev)
+            planS, plan1 = ops.verify_split_plan(Hkv, ctx, S), ops.verify_split_plan(Hkv, ctx)
+            wsS = ops.verify_workspace(T, H, Hkv, planS[1], dev, S=S)
+            ws1 = ops.verify_workspace(T, H, Hkv, plan1[1], dev)
+            planD = ops.decode_split_plan(S, Hkv, ctx)
+            wsD = ops.decode_workspace(S, H, Hkv, planD[1], dev)
+            q1 = q[:, 0].contiguous()
+
+            def one_by_one():
+                for s_ in range(S):
+                    ops.attn_verify(q[s_], kc, vc, bts[s_:s_ + 1], pos0[s_:s_ + 1], H, Hkv, D ** -0.5,
+                                    out[s_ * T:(s_ + 1) * T], workspace=ws1, plan=plan1)
+
+            arms = {
+                "verify_S": lambda: ops.attn_verify(q, kc, vc, bts, pos0, H, Hkv, D ** -0.5, out, workspace=wsS, plan=planS),
+                "verify_1_x_S": one_by_one,
+                "decode_batch_S": lambda: ops.attn_decode(q1, kc, vc, bts, posS, H, Hkv, D ** -0.5,
+                                                          out[:S].view(S, H, D), workspace=wsD, plan=planD),
+            }
+            us = {k: [] for k in arms}
+            for _ in range(reps):  # alternate the arms
+                for k, fn in arms.items():
+                    us[k].append(time_graph(fn))
+            med = {k: round(statistics.median(v), 2) for k, v in us.items()}
+            emit(dict(bench="batch_kernel", model=name, H=H, Hkv=Hkv, ctx=ctx, S=S, T=T, plan=list(planS), us=med,
+                      verify_S_over_1_x_S=round(med["verify_S"] / med["verify_1_x_S"], 3),
+                      verify_S_over_decode_S=round(med["verify_S"] / med["decode_batch_S"], 3)))
+
+
+def bench_batch_engine(dev, layers, reps: int, skip, Ss, models=(), k: int = 3) -> None:
+    """The verify step over S sequences against the plain step of bucket S, and the planted-draft envelope."""
+    for base, plen, new in (("duckdb-nsql", 128, 128), ("llama3.2", 2048, 128)):
+        if models and base not in models:
+            continue
+        spec = get_spec(base)
+        if layers:
+            spec = dataclasses.replace(spec, n_layers=layers, name=f"{base}-{layers}l")
+        w = init_random(spec, dev, seed=5)
+        SM = max(Ss)
+        r = ModelRunner(w, max_slots=SM, max_model_len=plen + new + 64, num_kv_blocks=SM * ((plen + new) // 64 + 3) + 1,
+                        spec_tokens=k, spec_batch=SM)
+        eng = LLMEngine(r, name=spec.name, max_prefill_tokens=SM * plen + 64)
+        T = r.spec_k() + 1
+        g = torch.Generator().manual_seed(7)
+        prompts = [[1] + torch.randint(3, 30000, (plen - 1,), generator=g).tolist() for _ in range(SM)]
+        for S in Ss:
+            if S > r.spec_s():
+                continue
+            ids = prompts[:S]
+
+            def run(kind: str, toks=None):
+                """(tokens per request, decode device s, decode steps, decode tokens / s of the S requests)."""
+                sp = SamplingParams(max_tokens=new, ignore_eos=True, speculate=bool(kind))
+                if kind:
+                    tab = torch.zeros(r.spec_s(), new + 1, T - 1, dtype=torch.int32)
+                    for s_ in range(S):
+                        tab[s_] = forced(toks[s_], kind, T - 1, spec.vocab_size)
+                    r.set_spec_forced(tab)
+                d0, n0 = eng.stats["decode_device_s"], eng.stats["decode_steps"]
+                out = [o.token_ids for o in eng.generate(ids, sp)]
+                ds, ns = eng.stats["decode_device_s"] - d0, eng.stats["decode_steps"] - n0
+                return out, ds, ns, sum(len(o) - 1 for o in out) / ds
+
+            plain_toks = run("")[0]               # warms the plain graphs of bucket S
+            toks = run("none", plain_toks)[0]     # warms the verify graph; the verify path's own greedy tokens
+            if "step" not in skip:
+                plain, ver, steps, same = [], [], 0, True
+                for _ in range(reps):
+                    _, ds, ns, _ = run("")
+                    plain.append(ds / ns)
+                    out, ds, steps, _ = run("none", toks)
+                    ver.append(ds / steps)
+                    same = same and out == toks
+                p, v = statistics.median(plain), statistics.median(ver)
+                emit(dict(bench="batch_step", model=spec.name, layers=spec.n_layers, prompt=plen, new=new, k=T - 1, S=S,
+                          rows=S * T, plain_step_ms=round(p * 1e3, 4), verify_step_ms=round(v * 1e3, 4),
+                          break_even_accept=round(v / p - 1, 3), verify_steps=steps, tokens_repeat=same,
+                          verify_tokens_equal_plain=toks == plain_toks))
+            if "e2e" not in skip:
+                res = {}
+                for _ in range(reps):
+                    res.setdefault("plain", []).append(run("")[3])
+                    for kind in ("none", "half", "all"):
+                        _, _, ns, tps = run(kind, toks)
+                        res.setdefault(kind, []).append(tps)
+                        res[kind + "_steps"] = ns
+                tok_s = {n: round(statistics.median(v), 1) for n, v in res.items() if not n.endswith("_steps")}
+                emit(dict(bench="batch_e2e", model=spec.name, layers=spec.n_layers, prompt=plen, new=new, k=T - 1, S=S,
+                          decode_tok_s=tok_s, speedup_over_plain={n: round(v / tok_s["plain"], 3) for n, v in tok_s.items()},
+                          verify_steps={n[:-6]: v for n, v in res.items() if n.endswith("_steps")}))
+        del eng, r, w
+        torch.cuda.empty_cache()
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--layers", type=int, default=0, help="truncate the models to this many layers (0 = full depth)")
@@ -311,14 +430,22 @@ def main() -> None:
     ap.add_argument("--models", default="", help="comma list of duckdb-nsql,llama3.2 (default both)")
     ap.add_argument("--out", default="", help="JSON-lines file to append to")
     ap.add_argument("--sampled", action="store_true", help="measure spec_sampled (sampled verify commit, sampled request)")
+    ap.add_argument("--batch", default="", help="comma list of S: measure spec_batch at S concurrent greedy requests")
     a = ap.parse_args()
     global OUT
-    OUT = a.out or (OUT_SAMPLED if a.sampled else OUT if (a.dtype, a.kv_dtype) == ("bf16", "bf16") else OUT_QUANT)
+    OUT = a.out or (OUT_BATCH if a.batch else OUT_SAMPLED if a.sampled else OUT if (a.dtype, a.kv_dtype) == ("bf16", "bf16") else OUT_QUANT)
     if not torch.cuda.is_available():
         raise SystemExit("bench_spec.py needs a GPU")
     ops.ext()
     dev = torch.device("cuda:0")
     skip = set(a.skip.split(",")) if a.skip else set()
+    if a.batch:
+        Ss = [int(x) for x in a.batch.split(",") if x]
+        if "kernel" not in skip:
+            bench_batch_kernel(dev, a.reps, Ss)
+        if not {"step", "e2e"} <= skip:
+            bench_batch_engine(dev, a.layers, a.reps, skip, Ss, tuple(m for m in a.models.split(",") if m))
+        return
     if a.sampled:
         models = tuple(m for m in a.models.split(",") if m)
         if "kernel" not in skip:
