@@ -82,7 +82,7 @@ int lsa_sample_commit(float* logits, int B, int V, unsigned long long* part, uns
                       const float* top_p, const unsigned long long* seeds, int* out_tokens, int max_new, int* gen_len,
                       int* input_ids, int* positions, int* finished, const int* eos, int neos, const int* limit,
                       const int* eos_on, hipStream_t s);
-int lsa_spec_sample_commit(float* logits, int T, int V, const int* draft, long long* stats, int* hist, int window,
+int lsa_spec_sample_commit(float* logits, int S, int T, int V, const int* draft, long long* stats, int* hist, int window,
                            const float* penalty, const int* last_n, const float* temperature, const int* top_k,
                            const float* top_p, const unsigned long long* seeds, int* out_tokens, int max_new,
                            int* gen_len, int* input_ids, int* positions, int* finished, const int* eos, int neos,
@@ -1198,9 +1198,11 @@ void sample_commit(at::Tensor& logits, at::Tensor& part, at::Tensor& cand, const
         "sample_commit");
 }
 
-// speculative decoding of a sampled request: penalty + sampled (or, temperature <= 0, argmax) pick of each of the T
-// verify rows at draw counter gen_len[0] + row, then the in-order commit of the accepted run into state row 0 (ring
-// included).  The per-row parameters are row 0's.  picks int32 [T] receives the rows' tokens.
+// speculative decoding of sampled requests: penalty + sampled (or, temperature <= 0, argmax) pick of each of the T
+// verify rows of a sequence at draw counter gen_len[s] + row, then the in-order commit of the accepted run into state
+// row s (ring included).  stats [3]: one sequence, logits [T, V], the parameters are row 0's, picks int32 [T].  stats
+// [S, 3]: S sequences as in spec_commit, logits [S * T, V], draft [S, T - 1], hist [>= S, W], every per-sequence
+// parameter of >= S entries, the workspace (part, cand, picks) sized for S * T <= 32 rows.
 void spec_sample_commit(at::Tensor& logits, const at::Tensor& draft, at::Tensor& stats,
                         const c10::optional<at::Tensor>& hist, const c10::optional<at::Tensor>& penalty,
                         const c10::optional<at::Tensor>& last_n, const at::Tensor& temperature, const at::Tensor& top_k,
@@ -1209,38 +1211,45 @@ void spec_sample_commit(at::Tensor& logits, const at::Tensor& draft, at::Tensor&
                         const at::Tensor& limit, const at::Tensor& eos_on, at::Tensor& part, at::Tensor& cand,
                         at::Tensor& picks) {
   need(logits, at::kFloat, "logits");
-  TORCH_CHECK(logits.dim() == 2 && logits.is_contiguous() && logits.size(0) >= 2 && logits.size(0) <= 8 &&
-                  logits.size(1) >= 1 && logits.numel() < 0x7fffffffLL, "logits: contiguous [2 <= T <= 8, V >= 1]");
-  const int T = logits.size(0), V = logits.size(1);
-  check_state(1, out_tokens, gen_len, input_ids, positions, finished, eos, limit, eos_on);
+  need(stats, at::kLong, "stats");
+  const bool rows = stats.dim() == 2 && stats.size(0) > 1;  // the S-sequence form
+  TORCH_CHECK(!rows || stats.size(1) == 3, "spec_sample_commit: stats [3] or [S, 3]");
+  const int S = rows ? stats.size(0) : 1;
+  TORCH_CHECK(logits.dim() == 2 && logits.is_contiguous() && logits.size(1) >= 1 && logits.numel() < 0x7fffffffLL &&
+                  logits.size(0) % S == 0 && logits.size(0) / S >= 2 && logits.size(0) / S <= 8 &&
+                  logits.size(0) <= (rows ? 32 : 8),
+              "logits: contiguous [S * T, V >= 1] with 2 <= T <= 8 and S * T <= 32");
+  const int T = logits.size(0) / S, V = logits.size(1);
+  check_state(S, out_tokens, gen_len, input_ids, positions, finished, eos, limit, eos_on);
   need(part, at::kLong, "part");
   need(cand, at::kLong, "cand");
   need(picks, at::kInt, "picks");
-  TORCH_CHECK(part.numel() >= (int64_t)T * ((V + 4095) / 4096) && cand.numel() >= (int64_t)T * ((V + 2047) / 2048) * 64 &&
-                  picks.numel() >= T && part.is_contiguous() && cand.is_contiguous() && picks.is_contiguous(),
+  TORCH_CHECK(part.numel() >= (int64_t)S * T * ((V + 4095) / 4096) &&
+                  cand.numel() >= (int64_t)S * T * ((V + 2047) / 2048) * 64 && picks.numel() >= S * T &&
+                  part.is_contiguous() && cand.is_contiguous() && picks.is_contiguous(),
               "spec_sample_commit workspace too small");
   need(draft, at::kInt, "draft");
-  need(stats, at::kLong, "stats");
-  TORCH_CHECK(draft.numel() >= T - 1 && draft.is_contiguous() && stats.numel() >= 3 && stats.is_contiguous(),
-              "spec_sample_commit: draft [T - 1], stats [3]");
+  TORCH_CHECK(draft.numel() >= (int64_t)S * (T - 1) && draft.is_contiguous() && stats.numel() >= 3 * S &&
+                  stats.is_contiguous(),
+              "spec_sample_commit: draft [S, T - 1], stats [3] or [S, 3]");
   need(temperature, at::kFloat, "temperature");
   need(top_p, at::kFloat, "top_p");
   need(top_k, at::kInt, "top_k");
   need(seeds, at::kLong, "seeds");
-  TORCH_CHECK(temperature.numel() >= 1 && top_p.numel() >= 1 && top_k.numel() >= 1 && seeds.numel() >= 1,
-              "sampling parameters: row 0");
+  TORCH_CHECK(temperature.numel() >= S && top_p.numel() >= S && top_k.numel() >= S && seeds.numel() >= S,
+              "sampling parameters: one per sequence");
   if (hist.has_value()) {
     need(*hist, at::kInt, "hist");
-    TORCH_CHECK(hist->dim() == 2 && hist->size(0) >= 1 && hist->size(1) >= 1 && hist->is_contiguous(), "hist [1, W]");
-    TORCH_CHECK(penalty.has_value() && penalty->numel() >= 1, "repetition penalty: row 0");
+    TORCH_CHECK(hist->dim() == 2 && hist->size(0) >= S && hist->size(1) >= 1 && hist->is_contiguous(), "hist [S, W]");
+    TORCH_CHECK(penalty.has_value() && penalty->numel() >= S, "repetition penalty: one per sequence");
     need(*penalty, at::kFloat, "penalty");
   }
   if (last_n.has_value()) {
     need(*last_n, at::kInt, "last_n");
-    TORCH_CHECK(last_n->numel() >= 1, "last_n: row 0");
+    TORCH_CHECK(last_n->numel() >= S, "last_n: one per sequence");
   }
   const int window = hist.has_value() ? hist->size(1) : 0;
-  check(lsa_spec_sample_commit(logits.data_ptr<float>(), T, V, draft.data_ptr<int>(),
+  check(lsa_spec_sample_commit(logits.data_ptr<float>(), S, T, V, draft.data_ptr<int>(),
                                reinterpret_cast<long long*>(stats.data_ptr<int64_t>()), ptr<int>(hist), window,
                                ptr<const float>(penalty), ptr<const int>(last_n), temperature.data_ptr<float>(),
                                top_k.data_ptr<int>(), top_p.data_ptr<float>(),

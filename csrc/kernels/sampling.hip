@@ -317,13 +317,16 @@ extern "C" int lsa_spec_commit(const float* logits, int S, int T, int V, unsigne
   return (int)hipGetLastError();
 }
 
-// ---------------------------------------------------------------- speculative decoding of a sampled request
-// lsa_spec_sample_commit: logits [T, V] are the T = k + 1 verify rows of ONE sequence (state row 0), p = positions[0]
-// and n = gen_len[0] at the launch.  Verify row i makes the very draw the plain step would make for generated token
-// n + i -- penalised over the ring as it would stand had drafts 0 .. i-1 been committed, drawn at counter n + i -- and
-// a draft is accepted exactly when it equals that draw, so the committed sequence is the plain sampled sequence of the
-// same seed.  Four launches after the partials: penalty (grid T) -> argmax / top-k partials (B = T) -> pick (grid T,
-// picks[i]) -> in-order commit (one wave).  No workgroup reads a word another workgroup of its launch writes.
+// ---------------------------------------------------------------- speculative decoding of sampled requests
+// lsa_spec_sample_commit: logits [S * T, V] are the T = k + 1 verify rows of each of S sequences.  Sequence s owns rows
+// s T .. s T + T - 1 of logits / part / cand / picks, draft + s k, ring row s, entry s of every sampling parameter,
+// state row s and stats + 3 s; p = positions[s] and n = gen_len[s] at the launch.  Verify row i of a sequence makes the
+// very draw the plain step would make for its generated token n + i -- penalised over the ring as it would stand had
+// drafts 0 .. i-1 been committed, drawn at counter n + i -- and a draft is accepted exactly when it equals that draw,
+// so the committed sequence is the plain sampled sequence of the same seed, whatever slot it runs in and whatever its
+// neighbours are (a greedy request is a sequence with temperature 0 and penalty 1).  Four launches after the partials:
+// penalty (grid T x S) -> argmax / top-k partials (B = S T) -> pick (grid T x S, picks[s T + i]) -> in-order commit
+// (one wave per sequence).  No workgroup reads a word another workgroup of its launch writes.
 
 // Repetition penalty of verify row i, in place, with repeat_penalty_kernel's rule over the tokens at context positions
 // (p + i - m, p + i], m = min(last_n, window, p + i + 1): the token at position p + j, 1 <= j <= i, is draft[j - 1];
@@ -335,12 +338,14 @@ __global__ __launch_bounds__(64) void spec_repeat_penalty_kernel(float* __restri
                                                                  const int* __restrict__ last_n,
                                                                  const int* __restrict__ positions,
                                                                  const int* __restrict__ draft) {
-  const int row = blockIdx.x;
-  const float pen = penalty[0];
+  const int row = blockIdx.x, s = blockIdx.y, T = gridDim.x;
+  const float pen = penalty[s];
   if (pen == 1.0f) return;
-  const int p = positions[0];
+  hist += (size_t)s * window;
+  draft += (size_t)s * (T - 1);
+  const int p = positions[s];
   const int P = p + row;
-  const int n = min(min(last_n ? last_n[0] : window, window), P + 1);
+  const int n = min(min(last_n ? last_n[s] : window, window), P + 1);
   auto tok_at = [&](int pos) { return pos > p ? draft[pos - p - 1] : hist[pos % window]; };
   for (int i = threadIdx.x; i < n; i += 64) {
     const int t = tok_at(P - i);
@@ -348,14 +353,14 @@ __global__ __launch_bounds__(64) void spec_repeat_penalty_kernel(float* __restri
     bool first = true;  // the most recent occurrence applies the penalty, once per distinct token
     for (int k = 0; k < i; ++k) first &= (tok_at(P - k) != t);
     if (!first) continue;
-    float* q = logits + (size_t)row * V + t;
+    float* q = logits + ((size_t)s * T + row) * V + t;
     const float v = *q;
     *q = v > 0.f ? v / pen : v * pen;
   }
 }
 
-// per verify row: the token the plain step would commit for generated token n + row (the sampler of
-// sample_commit_kernel at draw counter n + row; temperature <= 0: the row's argmax) -> picks[row]
+// per verify row of sequence s: the token the plain step would commit for its generated token n + row (the sampler of
+// sample_commit_kernel at draw counter n + row; temperature <= 0: the row's argmax) -> picks[s T + row]
 __global__ __launch_bounds__(1024) void spec_sample_pick_kernel(const unsigned long long* __restrict__ cand,
                                                                 int ncand_pow2, int ncand,
                                                                 const unsigned long long* __restrict__ amax_part,
@@ -365,33 +370,39 @@ __global__ __launch_bounds__(1024) void spec_sample_pick_kernel(const unsigned l
                                                                 const unsigned long long* __restrict__ seeds,
                                                                 const int* __restrict__ gen_len, int* __restrict__ picks) {
   extern __shared__ unsigned long long a[];
-  const int row = blockIdx.x;
-  const float T = temperature[0];
-  if (T <= 0.f) {  // greedy with a repetition penalty
+  const int s = blockIdx.y;
+  const int row = s * gridDim.x + blockIdx.x;  // of logits / part / cand / picks
+  const float T = temperature[s];
+  if (T <= 0.f) {  // greedy, with or without a repetition penalty
     if (threadIdx.x < 64) {
       const int tok = argmax_pick(amax_part + (size_t)row * nch_amax, nch_amax);
       if (threadIdx.x == 0) picks[row] = tok;
     }
     return;
   }
-  const int tok = sample_pick(a, cand + (size_t)row * ncand, ncand_pow2, ncand, T, top_k[0], top_p[0], seeds[0],
-                              (unsigned long long)(gen_len[0] + row));
+  const int tok = sample_pick(a, cand + (size_t)row * ncand, ncand_pow2, ncand, T, top_k[s], top_p[s], seeds[s],
+                              (unsigned long long)(gen_len[s] + blockIdx.x));
   if (threadIdx.x == 0) picks[row] = tok;
 }
 
-// one wave: a = the number of leading i < k with draft[i] >= 0 && draft[i] == picks[i]; picks[0 .. a] are committed in
-// order through commit_token (ring included), so nothing follows a finishing token; stats as spec_commit_kernel
+// one wave per sequence s: a = the number of leading i < k with draft[i] >= 0 && draft[i] == picks[i] (its own k drafts
+// and k + 1 picks); picks[0 .. a] are committed in order through commit_token (ring included), so nothing follows a
+// finishing token; stats row s as spec_commit_kernel.  A finished sequence changes nothing and counts nothing.
 __global__ __launch_bounds__(64) void spec_sample_commit_kernel(const int* __restrict__ picks, int k,
                                                                 const int* __restrict__ draft,
                                                                 long long* __restrict__ stats, DecodeState st) {
   if (threadIdx.x != 0) return;
-  const bool live = !st.finished[0];
+  const int s = blockIdx.x;
+  picks += (size_t)s * (k + 1);
+  draft += (size_t)s * k;
+  stats += (size_t)s * 3;
+  const bool live = !st.finished[s];
   bool run = true;  // picks[0 .. i-1] matched their drafts
   int committed = 0, drafted = 0;
   for (int i = 0; i <= k; ++i) {
     const int tok = picks[i];
-    if (run && live && !st.finished[0]) {
-      commit_token(st, 0, tok);
+    if (run && live && !st.finished[s]) {
+      commit_token(st, s, tok);
       ++committed;
     }
     if (i < k) {
@@ -407,32 +418,34 @@ __global__ __launch_bounds__(64) void spec_sample_commit_kernel(const int* __res
   }
 }
 
-// workspace: part (T * ceil(V/4096) u64) + cand (T * ceil(V/2048) * 64 u64) + picks (T int)
-extern "C" int lsa_spec_sample_commit(float* logits, int T, int V, const int* draft, long long* stats, int* hist,
+// workspace: part (S T * ceil(V/4096) u64) + cand (S T * ceil(V/2048) * 64 u64) + picks (S T int)
+extern "C" int lsa_spec_sample_commit(float* logits, int S, int T, int V, const int* draft, long long* stats, int* hist,
                                       int window, const float* penalty, const int* last_n, const float* temperature,
                                       const int* top_k, const float* top_p, const unsigned long long* seeds,
                                       int* out_tokens, int max_new, int* gen_len, int* input_ids, int* positions,
                                       int* finished, const int* eos, int neos, const int* limit, const int* eos_on,
                                       unsigned long long* part, unsigned long long* cand, int* picks, hipStream_t s) {
-  // sizes refused before anything is launched or written: 2 <= T <= 8 verify rows, V <= 262144 (lsa_sample_commit)
+  // sizes refused before anything is launched or written: 2 <= T <= 8 verify rows per sequence, S T <= 32 rows (the
+  // verify buffers), V <= 262144 (lsa_sample_commit)
   if (T < 2 || T > 8 || V < 1) return -1;
+  if (S < 1 || S * T > 32) return -2;
   const int nch2 = (V + LSA_CHUNK - 1) / LSA_CHUNK;
   const int ncand = nch2 * LSA_TOPK;
   int p2 = 64;
   while (p2 < ncand) p2 <<= 1;
   if (p2 > 8192) return -1;
   if (hist && window > 0 && penalty)
-    hipLaunchKernelGGL(spec_repeat_penalty_kernel, dim3(T), dim3(64), 0, s, logits, V, hist, window, penalty, last_n,
-                       positions, draft);
+    hipLaunchKernelGGL(spec_repeat_penalty_kernel, dim3(T, S), dim3(64), 0, s, logits, V, hist, window, penalty,
+                       last_n, positions, draft);
   const int chunk = 4096;
   const int nch = (V + chunk - 1) / chunk;
-  hipLaunchKernelGGL(argmax_partial_kernel, dim3(nch, T), dim3(256), 0, s, logits, V, chunk, part, nch);
-  hipLaunchKernelGGL(topk_partial_kernel, dim3(nch2, T), dim3(256), 0, s, logits, V, cand, nch2);
-  hipLaunchKernelGGL(spec_sample_pick_kernel, dim3(T), dim3(1024), p2 * sizeof(unsigned long long), s, cand, p2, ncand,
-                     part, nch, temperature, top_k, top_p, seeds, gen_len, picks);
+  hipLaunchKernelGGL(argmax_partial_kernel, dim3(nch, S * T), dim3(256), 0, s, logits, V, chunk, part, nch);
+  hipLaunchKernelGGL(topk_partial_kernel, dim3(nch2, S * T), dim3(256), 0, s, logits, V, cand, nch2);
+  hipLaunchKernelGGL(spec_sample_pick_kernel, dim3(T, S), dim3(1024), p2 * sizeof(unsigned long long), s, cand, p2,
+                     ncand, part, nch, temperature, top_k, top_p, seeds, gen_len, picks);
   DecodeState st{out_tokens, max_new, gen_len, input_ids, positions, finished, eos, neos, limit, eos_on,
                  window > 0 ? hist : nullptr, window};
-  hipLaunchKernelGGL(spec_sample_commit_kernel, dim3(1), dim3(64), 0, s, picks, T - 1, draft, stats, st);
+  hipLaunchKernelGGL(spec_sample_commit_kernel, dim3(S), dim3(64), 0, s, picks, T - 1, draft, stats, st);
   return (int)hipGetLastError();
 }
 

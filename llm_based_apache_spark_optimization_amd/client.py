@@ -285,6 +285,8 @@ class EngineService(Backend):
                                 "prefix_cached_blocks": lp.engine.sched.cached_blocks,
                                 "restarts": lp.restarts, "rebuilds": self.rebuilds.get(m, 0),
                                 "spec_batch": getattr(lp.engine, "spec_batch", 1),
+                                "spec_batch_sampled": bool(getattr(getattr(lp.engine, "runner", None),
+                                                                   "spec_batch_sampled", False)),
                                 **lp.engine.stats} for m, lp in self._loops.items()}}
 
 

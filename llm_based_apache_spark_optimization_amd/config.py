@@ -79,6 +79,9 @@ class Settings:
     # only a request that runs alone speculates).  Needs spec_tokens; clamped to a power of two with spec_batch * T <= 32,
     # at most 8 and at most the engine's slots (max_batch).  All or nothing: one running request that cannot speculate makes the run plain
     spec_batch: int = dataclasses.field(default_factory=lambda: _env("SPEC_BATCH", 1, int))
+    # requests that need the sampler speculate in such a run too, beside greedy ones (off: one of them makes the run
+    # plain).  Needs spec_tokens, spec_sampled and spec_batch > 1; every request's tokens are those it generates alone
+    spec_batch_sampled: bool = dataclasses.field(default_factory=lambda: _env("SPEC_BATCH_SAMPLED", False, bool))
     tp: int = dataclasses.field(default_factory=lambda: _env("TP", 1, int))
     dp: int = dataclasses.field(default_factory=lambda: _env("DP", 1, int))
     max_batch: int = dataclasses.field(default_factory=lambda: _env("MAX_BATCH", 32, int))

@@ -374,7 +374,9 @@ class LLMEngine:
             if self.device_timing:
                 ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
                 ev[0].record()
-            if spec_T and spec_S > 1:  # spec_batch: greedy, unconstrained verify steps over slots 0 .. spec_S - 1
+            if spec_T and spec_S > 1 and sample:  # spec_batch_sampled: the sampled commit over the spec_S sequences
+                r.decode_spec(n_steps, max_ctx=max_ctx, sample=True, S=spec_S)
+            elif spec_T and spec_S > 1:  # spec_batch: greedy, unconstrained verify steps over slots 0 .. spec_S - 1
                 r.decode_spec(n_steps, max_ctx=max_ctx, S=spec_S)
             elif spec_T:
                 if sample:  # spec_sampled: the verify graph that ends in the sampled commit (masked too, if guided)
@@ -505,8 +507,12 @@ class LLMEngine:
         steps over the sequences of slots 0 .. S - 1, S = bucket(highest slot + 1) <= spec_batch, else 0.  All or
         nothing -- a limit, not an oversight: one request that cannot speculate makes the whole run plain, because a
         mixed run would need rows of two kinds in one graph.  Every condition must hold: the scheduler runs no other
-        request and none is mid-prefill; every request is greedy, unconstrained, has ``speculate`` on and has not been
-        dropped by the acceptance guard; every request has window room for steps * T + T more positions; and
+        request and none is mid-prefill; every request is unconstrained, has ``speculate`` on and has not been
+        dropped by the acceptance guard; every request is greedy -- or, with ``spec_batch_sampled`` and
+        ``spec_sampled``, any mix of greedy requests and requests that need the sampler: the run then takes the
+        sampled verify graph exactly when at least one running request needs the sampler (a greedy request in it is a
+        sequence with temperature 0 and penalty 1), and the greedy batched graph otherwise; every request has window
+        room for steps * T + T more positions; and
         ``sched.grow`` gives every request the blocks of those positions without preempting anyone (blocks grown before
         a later request fails stay with their requests: the plain run that follows needs them too).  Slots below S
         without a request are idle rows of the step (``ModelRunner._verify_step``)."""
@@ -516,7 +522,9 @@ class LLMEngine:
             return 0
         if r.bucket(self.sched.highest_slot + 1) > SB or any(not 0 <= q.slot < SB for q in reqs):
             return 0
-        if any(q.params.needs_sampler or q.dfa is not None or not q.params.speculate or q.spec_off for q in reqs):
+        sampled_ok = getattr(r, "spec_batch_sampled", False) and getattr(r, "spec_sampled", False)
+        if any((q.params.needs_sampler and not sampled_ok) or q.dfa is not None or not q.params.speculate or q.spec_off
+               for q in reqs):
             return 0
         T = r.spec_k() + 1
         if SB * T > 32:

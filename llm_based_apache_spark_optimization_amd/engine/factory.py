@@ -21,7 +21,7 @@ def build_engine(model: str, device: Optional[str] = None, checkpoint: Optional[
                  kv_reserve_tokens: int = 64, spec_tokens: int = 0, prefix_cache: bool = False,
                  prefix_cow_min_tokens: Optional[int] = None, spec_quantized: bool = False,
                  guided: bool = False, spec_guided: bool = False, spec_sampled: bool = False,
-                 spec_batch: int = 1) -> LLMEngine:
+                 spec_batch: int = 1, spec_batch_sampled: bool = False) -> LLMEngine:
     """kv_dtype: paged KV cache dtype, "bf16" | "fp8" (None: LSA_KV_FP8, default bf16).
     max_new_cap: generated-token cap per request (None: the context window).
     kv_reserve_tokens: generated tokens whose KV is reserved at admission (the rest grows lazily; < 0 reserves
@@ -42,7 +42,12 @@ def build_engine(model: str, device: Optional[str] = None, checkpoint: Optional[
     spec_batch: the largest number of running greedy, unconstrained requests (in slots below it) whose decode run may
     be a run of verify steps (1, the default: one request in slot 0 only); clamped to a power of two with
     spec_batch * (spec_tokens + 1) <= 32 and <= max_slots.  All or nothing: one running request that cannot speculate
-    makes the run plain."""
+    makes the run plain.
+    spec_batch_sampled: requests that need the sampler may be among the requests of such a run (off: one of them makes
+    the run plain).  The run then ends each verify step in the sampled commit over its sequences, where a greedy
+    request is a sequence with temperature 0 and penalty 1; every request's tokens are those it generates alone.  An
+    all-greedy run keeps the greedy batched graph.  Needs spec_tokens, spec_sampled and spec_batch > 1, and is inert
+    without any of them."""
     if device is None:
         device = f"cuda:{torch.cuda.current_device()}" if torch.cuda.is_available() else "cpu"
     t0 = time.perf_counter()
@@ -57,7 +62,8 @@ def build_engine(model: str, device: Optional[str] = None, checkpoint: Optional[
     runner = ModelRunner(w, max_slots=max_slots, max_model_len=max_model_len, tp=tp, use_graphs=use_graphs,
                          num_kv_blocks=num_kv_blocks, kv_memory_fraction=kv_memory_fraction, kv_dtype=kv_dtype,
                          max_new_cap=max_new_cap, spec_tokens=spec_tokens, spec_quantized=spec_quantized,
-                         spec_guided=spec_guided, spec_sampled=spec_sampled, spec_batch=spec_batch)
+                         spec_guided=spec_guided, spec_sampled=spec_sampled, spec_batch=spec_batch,
+                         spec_batch_sampled=spec_batch_sampled)
     eng = LLMEngine(runner, tok, sync_every=sync_every, max_prefill_tokens=max_prefill_tokens, name=model,
                     prefill_chunk=prefill_chunk or None, kv_reserve_tokens=kv_reserve_tokens, spec_tokens=spec_tokens,
                     prefix_cache=prefix_cache, prefix_cow_min_tokens=prefix_cow_min_tokens, guided=guided)

@@ -51,7 +51,7 @@ class ModelRunner:
                  fuse_rope: Optional[bool] = None, seq_parallel: Optional[bool] = None, sp_min_tokens: Optional[int] = None,
                  kv_dtype: Optional[str] = None, spec_tokens: int = 0, spec_ngram: tuple = (3, 1),
                  spec_quantized: bool = False, spec_guided: bool = False, spec_sampled: bool = False,
-                 spec_batch: int = 1):
+                 spec_batch: int = 1, spec_batch_sampled: bool = False):
         self.w = weights
         # prompt-lookup speculative decoding (``_verify_step``): tokens drafted per step (0 = off) and the drafter's
         # (longest, shortest) n-gram.  Plain attributes: an experiment may set them on a built runner.
@@ -69,8 +69,12 @@ class ModelRunner:
         self.spec_sampled = bool(spec_sampled)
         # opt-in: the largest number S of running requests (slots 0 .. S - 1) whose decode run may be a run of verify
         # steps (``_verify_step(S=)``: S * T rows, ``spec_s`` clamps it).  1 = one request in slot 0 only.  Greedy,
-        # unconstrained requests only: sampled and guided verify steps stay one-sequence.
+        # unconstrained requests only: guided verify steps stay one-sequence, sampled ones too without the next flag.
         self.spec_batch = int(spec_batch)
+        # opt-in: requests that need the sampler in the verify steps over S sequences too (``_verify_step(sample=True,
+        # S=)``: the sampled commit over S sequences; a greedy request in such a step is a sequence with temperature 0
+        # and penalty 1).  Inert without ``spec_sampled`` and ``spec_batch`` > 1.
+        self.spec_batch_sampled = bool(spec_batch_sampled)
         # acceptance guard of the engine: a request whose accepted-per-verify-step mean falls below this after 16
         # verify steps takes plain steps for the rest of its life.  Break-even = verify-step time / plain-step time - 1.
         # Measured on MI355X (scripts/bench_spec.py, profiles/spec/spec_decode_mi355x.jsonl; plain vs verify step, k = 3):
@@ -81,7 +85,9 @@ class ModelRunner:
         # even against the plain step of bucket S at, per step and request (scripts/bench_spec.py --batch,
         # profiles/spec/spec_batch_mi355x.jsonl, k = 3): 7B 0.10 / 0.12 / 0.34 and 3B 0.13 / 0.18 / 0.25 at S = 2 / 4 / 8.
         # The guard compares every request with this one value whatever S it ran at: set it to the row of the
-        # spec_batch in use.
+        # spec_batch in use.  Sampled requests in such a step (``spec_batch_sampled``, against the plain sampled step of
+        # bucket S; --batch --sampled, profiles/spec/spec_batch_sampled_mi355x.jsonl): 7B 0.08 / 0.12 / 0.33, 3B 0.14 /
+        # 0.16 / 0.25.
         self.spec_min_accept = 0.0
         self._spec = None           # device buffers of the verify step (allocated on first use)
         self._spec_forced = None    # [nf, k] int32 planted drafts (tests / a later drafter), see set_spec_forced
@@ -848,7 +854,7 @@ class ModelRunner:
         token and k drafted tokens at positions p .. p + T - 1 -- and the in-order commit of the tokens greedy decoding
         would have produced (``ops.spec_commit``): between 1 and T per step, the same sequence as plain steps.
 
-        ``S`` > 1 (``spec_batch``; greedy, unconstrained): the same launches over the S sequences of slots 0 .. S - 1,
+        ``S`` > 1 (``spec_batch``; unconstrained): the same launches over the S sequences of slots 0 .. S - 1,
         S * T rows with row-major activations throughout -- rows s T .. s T + T - 1 are sequence s: its state row,
         ``block_tables[s]``, ``positions[s]``; the GEMMs and their split-K are those of S * T rows, ``attn_verify`` runs
         the S sequences in one launch and ``spec_commit`` commits each into its own state row and counts in its own
@@ -883,10 +889,18 @@ class ModelRunner:
         plain step's draw for generated token gen_len + i; a draft is accepted exactly when it equals that draw, so
         the committed tokens are the plain sampled tokens of the same seed.  A rejected row's draw counter is used
         again by the next step, as the plain path would use it.  With ``guided`` the mask runs before it (a -inf logit
-        stays -inf under the penalty and is never kept by the sampler) and the DFA hand-over after it, unchanged."""
+        stays -inf under the penalty and is never kept by the sampler) and the DFA hand-over after it, unchanged.
+
+        ``sample`` with ``S`` > 1 (``spec_batch_sampled``): the sampled commit over the S sequences -- sequence s reads
+        ring row s and entry s of every sampling parameter and draws at its own counter gen_len[s] + i, so each
+        request's tokens are those it generates alone; a greedy request among them is a sequence with temperature 0
+        and penalty 1, whose rows the commit leaves as they are and whose picks are their argmax.  ``guided`` with
+        ``S`` > 1 stays refused."""
         w, d, Ts = self.w, self.d, self.spec_k() + 1
         sb = self._spec_bufs()
-        assert S == 1 or not (guided or sample), "guided and sampled verify steps are one-sequence"
+        assert S == 1 or not guided, "guided verify steps are one-sequence"
+        assert S == 1 or not sample or (self.spec_sampled and self.spec_batch_sampled), \
+            "sampled verify steps over several sequences need spec_sampled and spec_batch_sampled"
         assert 1 <= S <= sb["ctx"].shape[0] and S * Ts <= 32, "verify step: S <= spec_batch sequences, S * T <= 32 rows"
         T = S * Ts  # rows of the step from here on
         n_max, n_min = self.spec_ngram
@@ -947,11 +961,11 @@ class ModelRunner:
                                 self.g_dim, self.g_on, self.g_state, self.g_base, st[1], st[2], st[4], self.eos,
                                 draft, self.g_spec)
         if sample:
-            ops.spec_sample_commit(logits, draft, sb["stats"][0], self.hist[:1], self.penalty[:1],
-                                   self.temperature[:1], self.top_k[:1], self.top_p[:1], self.seeds[:1], *st, self.eos,
-                                   self.limit[:1], self.eos_on[:1],
+            ops.spec_sample_commit(logits, draft, sb["stats"][0] if S == 1 else sb["stats"][:S], self.hist[:S],
+                                   self.penalty[:S], self.temperature[:S], self.top_k[:S], self.top_p[:S],
+                                   self.seeds[:S], *st, self.eos, self.limit[:S], self.eos_on[:S],
                                    workspace=(sb["amax_part"], sb["cand"], sb["picks"]) if self.on_gpu else None,
-                                   last_n=self.last_n[:1])
+                                   last_n=self.last_n[:S])
         else:
             ops.spec_commit(logits, draft, sb["stats"][0] if S == 1 else sb["stats"][:S], *st, self.eos, self.limit[:S],
                             self.eos_on[:S], part=sb["amax_part"] if self.on_gpu else None)
@@ -1007,13 +1021,15 @@ class ModelRunner:
         is the greedy one with a trailing "sample"; the greedy graphs and their keys are untouched).
         ``S`` > 1: verify steps over the sequences of slots 0 .. S - 1 (``_verify_step(S=)``), one graph per (S, T,
         plan, forced buffer): the split plan is the decode plan of bucket S, the key the one-sequence key with S
-        appended."""
+        appended.  ``sample`` with ``S`` > 1 needs ``spec_batch_sampled``; its key is the greedy key, then "sample",
+        then S."""
         assert self.spec_supported(), ("speculative decoding: TP = 1, spec_tokens > 0, bf16 weights and KV cache "
                                        "(or spec_quantized)")
         assert not guided or (self.guided and self.spec_guided), "guided verify steps need enable_guided() and spec_guided"
         assert not sample or self.spec_sampled, "sampled verify steps need spec_sampled"
-        assert S == 1 or (S <= self.spec_s() and not guided and not sample), \
-            "verify steps over several sequences: S <= spec_batch (clamped), greedy and unconstrained"
+        assert S == 1 or (S <= self.spec_s() and not guided and (not sample or self.spec_batch_sampled)), \
+            "verify steps over several sequences: S <= spec_batch (clamped), unconstrained, sampled only with " \
+            "spec_batch_sampled"
         plan = tuple(self.ctx_plan(S, max_ctx))
         if not self.use_graphs:
             for _ in range(steps):

@@ -262,14 +262,14 @@ def record_spec_logits(eng, prompt: Sequence[int], n_tokens: int, hidden: Option
     ``params``: the request's ``SamplingParams`` instead of the greedy ones (None) -- a sampled request on a
     ``spec_sampled`` engine; its max_tokens and ignore_eos are set as the greedy request's.  The recorded rows of a
     sampled verify step are the rows its commit read: with the repetition penalty applied.
-    Several prompts (a list of token lists, ``spec_batch`` engines): ``record_spec_logits_batch``."""
+    Several prompts (a list of token lists, ``spec_batch`` engines): ``record_spec_logits_batch``; ``params`` is then
+    one ``SamplingParams`` (or None = greedy) per request, for a ``spec_batch_sampled`` engine."""
     import dataclasses
 
     from ..engine import SamplingParams
 
     if len(prompt) and isinstance(prompt[0], (list, tuple)):
-        assert params is None, "several requests speculate together only when greedy"
-        return record_spec_logits_batch(eng, prompt, n_tokens, hidden)
+        return record_spec_logits_batch(eng, prompt, n_tokens, hidden, params)
     r = eng.runner
     hidden = tied(r.w) if hidden is None else hidden
     old = eng.run_ahead
@@ -312,12 +312,19 @@ def record_spec_logits(eng, prompt: Sequence[int], n_tokens: int, hidden: Option
         eng.run_ahead = old
 
 
-def record_spec_logits_batch(eng, prompts: Sequence[Sequence[int]], n_tokens: int, hidden: Optional[bool] = None):
-    """``record_spec_logits`` of several greedy requests sent at once (``spec_batch``): one decode run of one step per
+def record_spec_logits_batch(eng, prompts: Sequence[Sequence[int]], n_tokens: int, hidden: Optional[bool] = None,
+                             params=None):
+    """``record_spec_logits`` of several requests sent at once (``spec_batch``): one decode run of one step per
     engine iteration, recorded per request.  Returns (tokens: one list per request, logits [n, n_tokens, V] f32, steps:
     one list of step dicts per request).  A request's verify rows are rows slot * T .. slot * T + T - 1 of the step's
     buffers whatever S the step ran at; an iteration that ran plain steps (the run was gated, or the request was left
-    alone in a slot other than 0) is recorded from the plain step's logits row, spec = False."""
+    alone in a slot other than 0) is recorded from the plain step's logits row, spec = False.
+    ``params``: one ``SamplingParams`` per request (None = greedy, for all or for one) -- requests that need the
+    sampler speculate together on a ``spec_batch_sampled`` engine; max_tokens and ignore_eos are set as the greedy
+    request's.  The recorded rows of a sampled step, verify or plain, are the rows its commit read: with the request's
+    repetition penalty applied."""
+    import dataclasses
+
     from ..engine import SamplingParams
 
     r = eng.runner
@@ -325,8 +332,11 @@ def record_spec_logits_batch(eng, prompts: Sequence[Sequence[int]], n_tokens: in
     old = eng.run_ahead
     eng.run_ahead = 1
     try:
-        sp = SamplingParams(max_tokens=n_tokens + 1, temperature=0.0, ignore_eos=True)
-        qs = [eng.add_request(list(p), sp) for p in prompts]
+        greedy = SamplingParams(max_tokens=n_tokens + 1, temperature=0.0, ignore_eos=True)
+        sps = [greedy if sp is None else dataclasses.replace(sp, max_tokens=n_tokens + 1, ignore_eos=True)
+               for sp in (params if params is not None else [None] * len(prompts))]
+        assert len(sps) == len(prompts), "one SamplingParams (or None) per request"
+        qs = [eng.add_request(list(p), sp) for p, sp in zip(prompts, sps)]
         n = len(qs)
         out = torch.zeros(n, n_tokens, r.V, dtype=torch.float32, device=r.device)
         hid = torch.zeros(n, n_tokens, r.d, dtype=torch.float32, device=r.device) if hidden else None
@@ -375,12 +385,16 @@ def record_spec_logits_batch(eng, prompts: Sequence[Sequence[int]], n_tokens: in
         eng.run_ahead = old
 
 
-def teacher_forced_check_spec(eng, prompt: Sequence[int], n_tokens: int = 64, weights=None):
+def teacher_forced_check_spec(eng, prompt: Sequence[int], n_tokens: int = 64, weights=None, params=None):
     """``teacher_forced_check`` of the verify steps: every token a verify step committed, its verify-row logits against
     the oracle under the verify rows' plan and threshold class (``check_recorded(spec_steps=)``).  Several prompts (a
-    list of token lists, sent at once to a ``spec_batch`` engine): one result per request, each over its own tokens."""
+    list of token lists, sent at once to a ``spec_batch`` engine): one result per request, each over its own tokens.
+    ``params``: the requests' ``SamplingParams`` as ``record_spec_logits`` takes them (one, or one per request) -- the
+    sampled verify steps of ``spec_sampled`` and, over S sequences, ``spec_batch_sampled`` run the same forward pass
+    under the same oracle plan (``spec_oracle_plan``); the recorded rows carry the repetition penalty, so the
+    comparison with the oracle's unpenalised rows is meaningful for requests with penalty 1."""
     if len(prompt) and isinstance(prompt[0], (list, tuple)):
-        toks, elog, steps = record_spec_logits_batch(eng, prompt, n_tokens)
+        toks, elog, steps = record_spec_logits_batch(eng, prompt, n_tokens, params=params)
         out = []
         for i, p in enumerate(prompt):
             one = tuple(e[i:i + 1] for e in elog) if isinstance(elog, tuple) else elog[i:i + 1]
@@ -388,7 +402,7 @@ def teacher_forced_check_spec(eng, prompt: Sequence[int], n_tokens: int = 64, we
             res["verify_steps"] = sum(1 for s_ in steps[i] if s_["spec"])
             out.append(res)
         return out
-    toks, elog, steps = record_spec_logits(eng, prompt, n_tokens)
+    toks, elog, steps = record_spec_logits(eng, prompt, n_tokens, params=params)
     res = check_recorded(eng, [list(prompt)], [toks], elog, n_tokens, (0,), weights, spec_steps=steps)
     res["verify_steps"] = sum(1 for s_ in steps if s_["spec"])
     return res

@@ -1652,19 +1652,34 @@ def spec_sample_commit(logits, draft, stats, hist, penalty, temperature, top_k, 
     exactly when it equals that draw, and the accepted run is committed in order, ring included, so the tokens are
     those of the plain sampled steps of the same seed.  The parameters are row 0's; stats int64 [3] += (steps, drafted,
     accepted).  ``workspace`` = (part, cand, picks): int64 [T * ceil(V / 4096)], int64 [T * ceil(V / 2048) * 64],
-    int32 [T] (the rows' tokens)."""
-    T, V = logits.shape
-    limit, eos_on = _row_defaults(1, out_tokens, limit, eos_on)
+    int32 [T] (the rows' tokens).
+
+    stats [S, 3]: ``logits`` [S * T, V] and ``draft`` [S, T - 1] are the rows of S sequences (S * T <= 32, as
+    ``spec_commit``); sequence s reads ring row s and entry s of every parameter, commits into state row s and counts
+    in stats[s]; the workspace is sized for S * T rows.  A sequence with temperature 0 and penalty 1 commits what
+    ``spec_commit`` commits for its rows."""
+    R, V = logits.shape  # (all S * T rows)
+    S = stats.shape[0] if stats.dim() == 2 else 1
+    if S > 1 and (stats.shape[1] != 3 or R % S or R > 32):
+        raise RuntimeError("spec_sample_commit: stats [S, 3], logits [S * T, V] with S * T <= 32")
+    T = R // S
+    limit, eos_on = _row_defaults(S, out_tokens, limit, eos_on)
     if not _gpu(logits):
         if not 2 <= T <= 8 or V > 262144:  # as the binding and the launcher refuse them
             raise RuntimeError("spec_sample_commit: 2 <= T <= 8 verify rows, V <= 262144")
+        if S > 1:  # as the binding: one ring row, one parameter and one state row per sequence
+            per_seq = [temperature, top_k, top_p, seeds, gen_len, input_ids, positions, finished] + \
+                [t for t in (penalty, last_n) if t is not None]
+            if any(t.numel() < S for t in per_seq) or draft.numel() < S * (T - 1) or out_tokens.shape[0] < S or \
+                    (hist is not None and hist.shape[0] < S):
+                raise RuntimeError("spec_sample_commit: one row of every per-sequence operand per sequence")
         return ref.spec_sample_commit(logits, draft, stats, hist, penalty, temperature, top_k, top_p, seeds,
                                       out_tokens, gen_len, input_ids, positions, finished, eos, limit, eos_on,
                                       last_n=last_n)
     if workspace is None:
-        workspace = (torch.empty(T * ((V + 4095) // 4096), device=logits.device, dtype=torch.int64),
-                     torch.empty(T * ((V + 2047) // 2048) * 64, device=logits.device, dtype=torch.int64),
-                     torch.empty(T, device=logits.device, dtype=torch.int32))
+        workspace = (torch.empty(R * ((V + 4095) // 4096), device=logits.device, dtype=torch.int64),
+                     torch.empty(R * ((V + 2047) // 2048) * 64, device=logits.device, dtype=torch.int64),
+                     torch.empty(R, device=logits.device, dtype=torch.int32))
     part, cand, picks = workspace
     ext().spec_sample_commit(logits, draft, stats, hist, penalty, last_n, temperature, top_k, top_p, seeds, out_tokens,
                              gen_len, input_ids, positions, finished, eos, limit, eos_on, part, cand, picks)

@@ -607,15 +607,37 @@ def _spec_rows(logits, draft, hist, penalty, last_n, positions):
     return rows
 
 
+def _seq_views(s, T, logits, draft, stats, per_seq):
+    """Sequence ``s`` of an S-sequence sampled verify step as the one-sequence operands: its T logits rows, its T - 1
+    drafts, its stats row and row ``s`` (kept as a [1, ...] view, so writes land in the caller's tensors) of every
+    per-sequence tensor of ``per_seq`` (None stays None)."""
+    row = lambda t: t[s:s + 1] if t is not None else None  # noqa: E731
+    return (logits[s * T:(s + 1) * T], draft.reshape(-1)[s * (T - 1):(s + 1) * (T - 1)], stats.view(-1, 3)[s],
+            [row(t) for t in per_seq])
+
+
 def spec_sample_commit(logits, draft, stats, hist, penalty, temperature, top_k, top_p, seeds, out_tokens, gen_len,
                        input_ids, positions, finished, eos, limit=None, eos_on=None, last_n=None):
-    """The CPU engine's twin of lsa_spec_sample_commit.  logits [T, V]: the verify rows of the sequence in state row 0,
-    n = gen_len[0] at the call.  Row i is penalised as ``spec_penalised_row`` says (written back into ``logits``) and
+    """The CPU engine's twin of lsa_spec_sample_commit.  stats [S, 3], S > 1: logits [S * T, V] are the rows of S
+    sequences, and the call is a loop of the one-sequence call below over the row views of sequence s (rows s T .. s T
+    + T - 1, draft[s (T - 1) ..], ring / parameter / state row s, stats[s]).  Otherwise logits [T, V]: the verify rows
+    of the sequence in state row 0, n = gen_len[0] at the call.  Row i is penalised as ``spec_penalised_row`` says
+    (written back into ``logits``) and
     draws as ``sample_commit`` draws for gen_len = n + i (``sample_probs`` and ``torch.multinomial`` under
     ``draw_seed(seed, n + i)``; temperature <= 0: the argmax), so a verify step is bit-equal to the plain sampled
     steps.  Commits picks[0 .. a] in order, ring included (a = leading drafts >= 0 equal to their row's pick),
     stopping after a finishing token; stats += (1, drafts >= 0, tokens committed beyond the first).  A finished row
     changes no state."""
+    S = stats.shape[0] if stats.dim() == 2 else 1
+    if S > 1:
+        T = logits.shape[0] // S
+        for s in range(S):
+            lg, dr, st, (h, pen, tmp, tk, tp, sd, ot, gl, ii, ps, fin, lim, eon, ln) = _seq_views(
+                s, T, logits, draft, stats, (hist, penalty, temperature, top_k, top_p, seeds, out_tokens, gen_len,
+                                             input_ids, positions, finished, limit, eos_on, last_n))
+            spec_sample_commit(lg, dr, st, h, pen, tmp, tk, tp, sd, ot, gl, ii, ps, fin, eos, lim, eon, last_n=ln)
+        return
+    stats = stats.view(-1)
     T = logits.shape[0]
     n = int(gen_len[0])
     rows = _spec_rows(logits, draft, hist, penalty, last_n, positions)
@@ -646,10 +668,20 @@ def spec_sample_commit(logits, draft, stats, hist, penalty, temperature, top_k, 
 
 
 def spec_sample_pick_sets(logits, draft, hist, penalty, temperature, top_k, top_p, seeds, gen_len, positions,
-                          last_n=None, m: float = SAMPLE_MARGIN) -> list:
+                          last_n=None, m: float = SAMPLE_MARGIN, S: int = 1) -> list:
     """The exact device twin of the picks of lsa_spec_sample_commit: per verify row i the set of tokens the device
     may write to picks[i] -- ``sample_pick_set`` of the penalised row at ``device_uniform(seed, gen_len[0] + i)``, or
-    the plain argmax for temperature <= 0.  A one-element set is a decided draw."""
+    the plain argmax for temperature <= 0.  A one-element set is a decided draw.  ``S`` > 1: logits [S * T, V], draft
+    [S, T - 1] and row s of every other operand belong to sequence s; the list has S * T sets, sequence s at s T ..."""
+    if S > 1:
+        T = logits.shape[0] // S
+        out = []
+        for s in range(S):
+            lg, dr, _, (h, pen, tmp, tk, tp, sd, gl, ps, ln) = _seq_views(
+                s, T, logits, draft, torch.zeros(S, 3), (hist, penalty, temperature, top_k, top_p, seeds, gen_len,
+                                                         positions, last_n))
+            out += spec_sample_pick_sets(lg, dr, h, pen, tmp, tk, tp, sd, gl, ps, last_n=ln, m=m)
+        return out
     n = int(gen_len[0])
     Tmp = float(temperature[0])
     out = []

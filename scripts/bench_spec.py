@@ -29,13 +29,23 @@ profiles/spec/spec_batch_mi355x.jsonl:
            which the verify step breaks even.
   e2e      decode tokens/s of the S requests together: plain, and planted acceptance none / about half / all.
 
+With --batch 2,4,8 --sampled: the same for requests that need the sampler (``spec_batch_sampled``), k = 3, Ollama's
+default options and one seed per request, appended to profiles/spec/spec_batch_sampled_mi355x.jsonl:
+
+  commit   device time of the sampled verify commit over S sequences (S x 4 rows) against the greedy ``spec_commit``
+           at the same rows and against the plain step's ``sample_commit`` at batch S.
+  step     device time of the sampled verify step over S sequences (planted all-wrong drafts) against the plain sampled
+           step of bucket S; ratio - 1 = the break-even accepted drafts per step and request.
+  e2e      decode tokens/s of the S sampled requests together: plain, and planted acceptance none / about half / all,
+           planted from the verify path's own tokens.
+
 Every graph is warmed, times are device events, the arms alternate within one process.  Appends JSON lines to
 profiles/spec/spec_decode_mi355x.jsonl, or -- with quantised weights or the fp8 cache (``spec_quantized`` engines) --
 to profiles/spec/spec_decode_quant_mi355x.jsonl (--out overrides).  Needs a GPU.
 
   python scripts/bench_spec.py [--layers N] [--skip kernel,step,e2e] [--reps 5] [--dtype bf16|fp8|mxfp4]
                                [--kv-dtype bf16|fp8] [--models duckdb-nsql,llama3.2] [--out FILE] [--sampled]
-                               [--batch 2,4,8]
+                               [--batch 2,4,8 [--sampled]]
 """
 from __future__ import annotations
 
@@ -61,6 +71,7 @@ OUT = os.path.join(ROOT, "profiles", "spec", "spec_decode_mi355x.jsonl")
 OUT_QUANT = os.path.join(ROOT, "profiles", "spec", "spec_decode_quant_mi355x.jsonl")
 OUT_SAMPLED = os.path.join(ROOT, "profiles", "spec", "spec_sampled_mi355x.jsonl")
 OUT_BATCH = os.path.join(ROOT, "profiles", "spec", "spec_batch_mi355x.jsonl")
+OUT_BATCH_SAMPLED = os.path.join(ROOT, "profiles", "spec", "spec_batch_sampled_mi355x.jsonl")
 OLLAMA = dict(temperature=0.8, top_k=40, top_p=0.9, repeat_penalty=1.1)  # Ollama's default option set
 
 
@@ -355,8 +366,63 @@ def bench_batch_kernel(dev, reps: int, Ss, T: int = 4) -> None:
                       verify_S_over_decode_S=round(med["verify_S"] / med["decode_batch_S"], 3)))
 
 
-def bench_batch_engine(dev, layers, reps: int, skip, Ss, models=(), k: int = 3) -> None:
-    """The verify step over S sequences against the plain step of bucket S, and the planted-draft envelope."""
+def bench_batch_sampled_commit(dev, reps: int, Ss, models=(), T: int = 4) -> None:
+    """The commits alone, over static rows: every launch commits one token per sequence (the drafts are -1)."""
+    W, max_new = 64, 8192  # ~520 launches per arm and measurement: no row reaches its limit
+    for base in ("duckdb-nsql", "llama3.2"):
+        if models and base not in models:
+            continue
+        V = get_spec(base).vocab_size
+        g = torch.Generator().manual_seed(V)
+        SM = max(Ss)
+        logits0 = (torch.randn(SM * T, V, generator=g) * 2).to(dev)
+        i32 = dict(dtype=torch.int32, device=dev)
+        hist = torch.randint(0, V, (SM, W), generator=g, dtype=torch.int32).to(dev)
+        pen, last_n = torch.full((SM,), OLLAMA["repeat_penalty"], device=dev), torch.full((SM,), W, **i32)
+        temp = torch.full((SM,), OLLAMA["temperature"], device=dev)
+        top_p = torch.full((SM,), OLLAMA["top_p"], device=dev)
+        top_k = torch.full((SM,), OLLAMA["top_k"], **i32)
+        seeds = torch.tensor([ref.pack_seed(17 + s_, 0) for s_ in range(SM)], dtype=torch.int64, device=dev)
+        eos = torch.tensor([-1], **i32)
+        draft = torch.full((SM * T,), -1, **i32)
+        part = torch.zeros(SM * T * ((V + 4095) // 4096), dtype=torch.int64, device=dev)
+        cand = torch.zeros(SM * T * ((V + 2047) // 2048) * 64, dtype=torch.int64, device=dev)
+        picks = torch.zeros(SM * T, **i32)
+        for S in Ss:
+            def state():
+                return (torch.zeros(S, max_new, **i32), torch.zeros(S, **i32), torch.zeros(S, **i32),
+                        torch.full((S,), 100, **i32), torch.zeros(S, **i32))
+
+            def arm(kind: str):
+                st, stats = state(), torch.zeros(S, 3, dtype=torch.int64, device=dev)
+                if kind == "spec_sampled":
+                    lg = logits0[:S * T].clone()
+                    return lambda: ops.spec_sample_commit(lg, draft[:S * (T - 1)], stats if S > 1 else stats[0],
+                                                          hist[:S], pen[:S], temp[:S], top_k[:S], top_p[:S], seeds[:S], *st, eos,
+                                                          workspace=(part, cand, picks), last_n=last_n[:S])
+                if kind == "spec_greedy":
+                    lg = logits0[:S * T].clone()
+                    return lambda: ops.spec_commit(lg, draft[:S * (T - 1)], stats if S > 1 else stats[0], *st, eos,
+                                                   part=part)
+                lg = logits0[:S].clone()
+                return lambda: ops.sample_commit(lg, hist[:S], pen[:S], temp[:S], top_k[:S], top_p[:S], seeds[:S], *st,
+                                                 eos, workspace=(part, cand), last_n=last_n[:S])
+
+            us = {}
+            for _ in range(reps):  # alternate the arms
+                for kind in ("spec_greedy", "spec_sampled", "plain_sampled"):
+                    us.setdefault(kind, []).append(time_graph(arm(kind)))
+            med = {k_: round(statistics.median(v), 2) for k_, v in us.items()}
+            emit(dict(bench="batch_sampled_commit", model=base, V=V, S=S, T=T, rows=S * T, us=med,
+                      sampled_over_greedy_us=round(med["spec_sampled"] - med["spec_greedy"], 2),
+                      sampled_over_plain_batch_S_us=round(med["spec_sampled"] - med["plain_sampled"], 2)))
+
+
+def bench_batch_engine(dev, layers, reps: int, skip, Ss, models=(), k: int = 3, sampled: bool = False,
+                       seed: int = 11) -> None:
+    """The verify step over S sequences against the plain step of bucket S, and the planted-draft envelope.  ``sampled``:
+    every request runs with Ollama's default options and its own seed (``spec_batch_sampled``): the sampled verify step
+    against the plain sampled step."""
     for base, plen, new in (("duckdb-nsql", 128, 128), ("llama3.2", 2048, 128)):
         if models and base not in models:
             continue
@@ -366,7 +432,7 @@ def bench_batch_engine(dev, layers, reps: int, skip, Ss, models=(), k: int = 3) 
         w = init_random(spec, dev, seed=5)
         SM = max(Ss)
         r = ModelRunner(w, max_slots=SM, max_model_len=plen + new + 64, num_kv_blocks=SM * ((plen + new) // 64 + 3) + 1,
-                        spec_tokens=k, spec_batch=SM)
+                        spec_tokens=k, spec_batch=SM, spec_sampled=sampled, spec_batch_sampled=sampled)
         eng = LLMEngine(r, name=spec.name, max_prefill_tokens=SM * plen + 64)
         T = r.spec_k() + 1
         g = torch.Generator().manual_seed(7)
@@ -378,14 +444,17 @@ def bench_batch_engine(dev, layers, reps: int, skip, Ss, models=(), k: int = 3) 
 
             def run(kind: str, toks=None):
                 """(tokens per request, decode device s, decode steps, decode tokens / s of the S requests)."""
-                sp = SamplingParams(max_tokens=new, ignore_eos=True, speculate=bool(kind))
+                sps = [SamplingParams(max_tokens=new, ignore_eos=True, speculate=bool(kind),
+                                      **(dict(seed=seed + s_, **OLLAMA) if sampled else {})) for s_ in range(S)]
                 if kind:
                     tab = torch.zeros(r.spec_s(), new + 1, T - 1, dtype=torch.int32)
                     for s_ in range(S):
                         tab[s_] = forced(toks[s_], kind, T - 1, spec.vocab_size)
                     r.set_spec_forced(tab)
                 d0, n0 = eng.stats["decode_device_s"], eng.stats["decode_steps"]
-                out = [o.token_ids for o in eng.generate(ids, sp)]
+                reqs = [eng.add_request(p_, sp) for p_, sp in zip(ids, sps)]
+                eng.run_until_done(reqs)
+                out = [q.output_ids for q in reqs]
                 ds, ns = eng.stats["decode_device_s"] - d0, eng.stats["decode_steps"] - n0
                 return out, ds, ns, sum(len(o) - 1 for o in out) / ds
 
@@ -400,7 +469,8 @@ def bench_batch_engine(dev, layers, reps: int, skip, Ss, models=(), k: int = 3) 
                     ver.append(ds / steps)
                     same = same and out == toks
                 p, v = statistics.median(plain), statistics.median(ver)
-                emit(dict(bench="batch_step", model=spec.name, layers=spec.n_layers, prompt=plen, new=new, k=T - 1, S=S,
+                emit(dict(bench="batch_sampled_step" if sampled else "batch_step", model=spec.name,
+                          layers=spec.n_layers, prompt=plen, new=new, k=T - 1, S=S,
                           rows=S * T, plain_step_ms=round(p * 1e3, 4), verify_step_ms=round(v * 1e3, 4),
                           break_even_accept=round(v / p - 1, 3), verify_steps=steps, tokens_repeat=same,
                           verify_tokens_equal_plain=toks == plain_toks))
@@ -413,7 +483,8 @@ def bench_batch_engine(dev, layers, reps: int, skip, Ss, models=(), k: int = 3) 
                         res.setdefault(kind, []).append(tps)
                         res[kind + "_steps"] = ns
                 tok_s = {n: round(statistics.median(v), 1) for n, v in res.items() if not n.endswith("_steps")}
-                emit(dict(bench="batch_e2e", model=spec.name, layers=spec.n_layers, prompt=plen, new=new, k=T - 1, S=S,
+                emit(dict(bench="batch_sampled_e2e" if sampled else "batch_e2e", model=spec.name,
+                          layers=spec.n_layers, prompt=plen, new=new, k=T - 1, S=S,
                           decode_tok_s=tok_s, speedup_over_plain={n: round(v / tok_s["plain"], 3) for n, v in tok_s.items()},
                           verify_steps={n[:-6]: v for n, v in res.items() if n.endswith("_steps")}))
         del eng, r, w
@@ -433,7 +504,8 @@ def main() -> None:
     ap.add_argument("--batch", default="", help="comma list of S: measure spec_batch at S concurrent greedy requests")
     a = ap.parse_args()
     global OUT
-    OUT = a.out or (OUT_BATCH if a.batch else OUT_SAMPLED if a.sampled else OUT if (a.dtype, a.kv_dtype) == ("bf16", "bf16") else OUT_QUANT)
+    OUT = a.out or (OUT_BATCH_SAMPLED if a.batch and a.sampled else OUT_BATCH if a.batch
+                    else OUT_SAMPLED if a.sampled else OUT if (a.dtype, a.kv_dtype) == ("bf16", "bf16") else OUT_QUANT)
     if not torch.cuda.is_available():
         raise SystemExit("bench_spec.py needs a GPU")
     ops.ext()
@@ -441,10 +513,13 @@ def main() -> None:
     skip = set(a.skip.split(",")) if a.skip else set()
     if a.batch:
         Ss = [int(x) for x in a.batch.split(",") if x]
-        if "kernel" not in skip:
+        models = tuple(m for m in a.models.split(",") if m)
+        if "kernel" not in skip and a.sampled:
+            bench_batch_sampled_commit(dev, a.reps, Ss, models)
+        elif "kernel" not in skip:
             bench_batch_kernel(dev, a.reps, Ss)
         if not {"step", "e2e"} <= skip:
-            bench_batch_engine(dev, a.layers, a.reps, skip, Ss, tuple(m for m in a.models.split(",") if m))
+            bench_batch_engine(dev, a.layers, a.reps, skip, Ss, models, sampled=a.sampled)
         return
     if a.sampled:
         models = tuple(m for m in a.models.split(",") if m)
