@@ -72,6 +72,13 @@ int lsa_dfa_mask_verify(float* logits, int T, int V, const int* tok_off, const u
                         const uint16_t* trans, const uint8_t* accept, const int* g_dim, const int* g_on, int* g_state,
                         const int* g_base, int r, const int* gen_len, const int* input_ids, const int* finished,
                         const int* eos, int neos, const int* draft, int* g_spec, hipStream_t s);
+int lsa_dfa_mask_verify_batch(float* logits, int S, int T, int V, const int* tok_off, const uint8_t* tok_blob,
+                              const uint8_t* cls, const uint16_t* trans, const uint8_t* accept, const int* g_dim,
+                              const int* g_on, int* g_state, const int* g_base, int r, const int* gen_len,
+                              const int* input_ids, const int* finished, const int* eos, int neos, const int* draft,
+                              int* g_spec, hipStream_t s);
+int lsa_dfa_spec_advance_batch(const int* g_on, int* g_state, const int* g_spec, const int* gen_len, int r, int S, int k,
+                               hipStream_t s);
 int lsa_dfa_spec_advance(const int* g_on, int* g_state, const int* g_spec, const int* gen_len, int r, int k,
                          hipStream_t s);
 int lsa_spec_commit(const float* logits, int S, int T, int V, unsigned long long* part, const int* draft,
@@ -1103,15 +1110,22 @@ void dfa_mask(at::Tensor& logits, const at::Tensor& tok_off, const at::Tensor& t
 // Speculative decoding of a constrained request: the mask of the T = k + 1 verify rows of the sequence in state row 0
 // (table row r); row t is masked in the DFA state after the input token and drafts 1..t.  g_spec int32 [>= 9]:
 // gen_len at the launch, then the T states (kernels/guided.hip dfa_mask_verify_kernel).
+// A 2-D g_spec [S, 9] selects the form over S sequences (as the 2-D stats of spec_commit): logits [S * T, V], draft
+// [>= S * (T - 1)], sequence s = state row s = table row s (r must be 0), g_spec row s.
 void dfa_mask_verify(at::Tensor& logits, const at::Tensor& tok_off, const at::Tensor& tok_blob, const at::Tensor& cls,
                      const at::Tensor& trans, const at::Tensor& accept, const at::Tensor& g_dim, const at::Tensor& g_on,
                      at::Tensor& g_state, const at::Tensor& g_base, int64_t r, const at::Tensor& gen_len,
                      const at::Tensor& input_ids, const at::Tensor& finished, const at::Tensor& eos,
                      const at::Tensor& draft, at::Tensor& g_spec) {
   need(logits, at::kFloat, "logits");
-  TORCH_CHECK(logits.dim() == 2 && logits.is_contiguous() && logits.size(0) >= 2 && logits.size(0) <= 8 &&
-                  logits.size(1) >= 1 && logits.numel() < 0x7fffffffLL, "logits: contiguous [2 <= T <= 8, V >= 1]");
-  const int64_t T = logits.size(0), V = logits.size(1);
+  const bool batch = g_spec.dim() == 2;
+  const int64_t S = batch ? g_spec.size(0) : 1;
+  TORCH_CHECK(!batch || (S >= 1 && S <= 8 && g_spec.size(1) == 9), "dfa_mask_verify: g_spec [1 <= S <= 8, 1 + 8]");
+  TORCH_CHECK(logits.dim() == 2 && logits.is_contiguous() && logits.size(0) % S == 0 && logits.size(0) >= 2 * S &&
+                  logits.size(0) <= 8 * S && logits.size(0) <= 32 && logits.size(1) >= 1 &&
+                  logits.numel() < 0x7fffffffLL,
+              "logits: contiguous [S * T, V >= 1], 2 <= T <= 8 rows per sequence, S * T <= 32");
+  const int64_t T = logits.size(0) / S, V = logits.size(1);
   need(tok_off, at::kInt, "tok_off");
   need(tok_blob, at::kByte, "tok_blob");
   need(cls, at::kByte, "cls");
@@ -1134,8 +1148,22 @@ void dfa_mask_verify(at::Tensor& logits, const at::Tensor& tok_off, const at::Te
   TORCH_CHECK(g_dim.numel() == 2 * Bmax && g_state.numel() == 2 * Bmax && g_on.numel() == Bmax && g_base.numel() == Bmax,
               "dfa_mask_verify: g_dim / g_state [Bmax, 2], g_on / g_base [Bmax]");
   TORCH_CHECK(r >= 0 && r < Bmax, "dfa_mask_verify: table row out of range");
-  TORCH_CHECK(gen_len.numel() >= 1 && input_ids.numel() >= 1 && finished.numel() >= 1, "dfa_mask_verify: state row 0");
-  TORCH_CHECK(draft.numel() >= T - 1 && g_spec.numel() >= 9, "dfa_mask_verify: draft [T - 1], g_spec [1 + 8]");
+  TORCH_CHECK(!batch || (r == 0 && S <= Bmax), "dfa_mask_verify over S sequences: r = 0, S <= Bmax table rows");
+  TORCH_CHECK(gen_len.numel() >= S && input_ids.numel() >= S && finished.numel() >= S,
+              "dfa_mask_verify: one state row per sequence");
+  TORCH_CHECK(draft.numel() >= S * (T - 1) && g_spec.numel() >= 9 * S,
+              "dfa_mask_verify: draft [S * (T - 1)], g_spec [S, 1 + 8]");
+  if (batch) {
+    check(lsa_dfa_mask_verify_batch(logits.data_ptr<float>(), (int)S, (int)T, V, tok_off.data_ptr<int>(),
+                                    tok_blob.data_ptr<uint8_t>(), cls.data_ptr<uint8_t>(),
+                                    reinterpret_cast<const uint16_t*>(trans.data_ptr<int16_t>()),
+                                    accept.data_ptr<uint8_t>(), g_dim.data_ptr<int>(), g_on.data_ptr<int>(),
+                                    g_state.data_ptr<int>(), g_base.data_ptr<int>(), 0, gen_len.data_ptr<int>(),
+                                    input_ids.data_ptr<int>(), finished.data_ptr<int>(), eos.data_ptr<int>(),
+                                    eos.numel(), draft.data_ptr<int>(), g_spec.data_ptr<int>(), cur_stream()),
+          "dfa_mask_verify (S sequences)");
+    return;
+  }
   check(lsa_dfa_mask_verify(logits.data_ptr<float>(), T, V, tok_off.data_ptr<int>(), tok_blob.data_ptr<uint8_t>(),
                             cls.data_ptr<uint8_t>(), reinterpret_cast<const uint16_t*>(trans.data_ptr<int16_t>()),
                             accept.data_ptr<uint8_t>(), g_dim.data_ptr<int>(), g_on.data_ptr<int>(),
@@ -1156,6 +1184,17 @@ void dfa_spec_advance(const at::Tensor& g_on, at::Tensor& g_state, const at::Ten
   TORCH_CHECK(k >= 1 && k <= 7, "dfa_spec_advance: 1 <= k <= 7");
   TORCH_CHECK(r >= 0 && r < g_on.numel() && g_state.numel() == 2 * g_on.numel(),
               "dfa_spec_advance: g_on [Bmax], g_state [Bmax, 2], 0 <= r < Bmax");
+  if (g_spec.dim() == 2) {  // the form over S sequences: sequence s = gen_len[s], g_spec row s, table row s
+    const int64_t S = g_spec.size(0);
+    TORCH_CHECK(S >= 1 && S <= 8 && g_spec.size(1) == 9 && S * (k + 1) <= 32,
+                "dfa_spec_advance: g_spec [1 <= S <= 8, 1 + 8], S * (k + 1) <= 32");
+    TORCH_CHECK(r == 0 && S <= g_on.numel() && gen_len.numel() >= S,
+                "dfa_spec_advance over S sequences: r = 0, S <= Bmax table rows, gen_len [S]");
+    check(lsa_dfa_spec_advance_batch(g_on.data_ptr<int>(), g_state.data_ptr<int>(), g_spec.data_ptr<int>(),
+                                     gen_len.data_ptr<int>(), 0, (int)S, (int)k, cur_stream()),
+          "dfa_spec_advance (S sequences)");
+    return;
+  }
   TORCH_CHECK(g_spec.numel() >= 9 && gen_len.numel() >= 1, "dfa_spec_advance: g_spec [1 + 8], gen_len row 0");
   check(lsa_dfa_spec_advance(g_on.data_ptr<int>(), g_state.data_ptr<int>(), g_spec.data_ptr<int>(),
                              gen_len.data_ptr<int>(), (int)r, (int)k, cur_stream()),

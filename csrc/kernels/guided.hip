@@ -24,27 +24,43 @@
 //   outside the mask can cause: the row may then only stop).  Every other logit becomes -inf; an allowed one is not
 //   touched.  ops/reference.py dfa_mask is the host twin.
 //
-// Speculative decoding of a constrained request (the verify step's T = k + 1 logits rows of the sequence in state row 0):
+// Speculative decoding of constrained requests (the verify step's T = k + 1 logits rows of each of S sequences):
 //
-//   dfa_mask_verify_kernel   grid (ceil(V / 2048), T), 256 threads; table row r is an argument (0: the speculating slot).
+//   dfa_mask_verify_kernel   grid (ceil(V / 2048), T, S), 256 threads.  Sequence s = blockIdx.z is the sequence of state
+//                     row s (gen_len[s], input_ids[s], finished[s]) and table row r + s; it reads its drafts at
+//                     draft + s * k, masks logits rows s * T + t and writes g_spec + 9 * s (g_spec is [S, 1 + 8]).  The
+//                     one-sequence form is S = 1 with any r (state row 0, table row r: the speculating slot is 0); the
+//                     form over S sequences is r = 0, so table row = state row = slot, as in the plain decode mask.  The
+//                     workgroups of a sequence return at once when g_on[r + s] == 0 or finished[s] != 0 (uniform per
+//                     workgroup: one scalar load each for an unconstrained, finished or released slot, whose logits
+//                     rows, state words and g_spec row stay untouched).
 //                     Row t is masked exactly as dfa_mask_kernel masks a row whose current state is s_t, with
-//                     s_0 = cur of the lazy advance above (workgroup (0, 0) stores it to slot n & 1 when n != g_base[r])
-//                     and s_t = walk(s_{t-1}, bytes(draft[t - 1])).  A draft of -1, outside [0, V), of 0 or more than
+//                     s_0 = cur of the lazy advance above (workgroup (0, 0, s) stores it to slot n & 1 of table row
+//                     r + s when n != g_base[r + s]) and s_t = walk(s_{t-1}, bytes(draft[t - 1])).
+//                     A draft of -1, outside [0, V), of 0 or more than
 //                     32 bytes, or one whose walk dies makes s_t and every later state DEAD: such a row can only be
 //                     reached through a draft the previous row's mask already set to -inf, and it is masked by the same
 //                     rule (EOS only) instead of skipped.  The draft bytes (at most 7 x 32 B) are parked in LDS beside
-//                     the input token's and walked by every lane with broadcast reads.  Workgroup (0, t) stores s_t to
-//                     g_spec[1 + t], workgroup (0, 0) stores n to g_spec[0]: plain vector stores, and no workgroup reads
-//                     a word that another workgroup of the launch writes.  ops/reference.py dfa_mask_verify is the twin.
+//                     the input token's and walked by every lane with broadcast reads.  Workgroup (0, t, s) stores s_t
+//                     to g_spec[9 s + 1 + t], workgroup (0, 0, s) stores n to g_spec[9 s].
+//                     What the S-form keeps of the one-sequence kernel: the shared __device__ helpers (dfa_stage,
+//                     dfa_tok_spans, dfa_walk_mask); the static LDS footprint of 64 KiB + 256 B + the input token's and
+//                     the drafts' bytes (32 B + 7 x 32 B); plain vector stores only; no workgroup reads a word that
+//                     another workgroup of the same launch writes (a sequence touches only its own state row, table
+//                     row, logits rows and g_spec row, and within a sequence the rule above holds as before); nothing
+//                     ever waits on another workgroup.  Sequence s runs the instructions of its own one-sequence
+//                     launch on the same operands, so it computes the same bits.
+//                     ops/reference.py dfa_mask_verify / dfa_mask_verify_batch are the twins.
 //
-//   dfa_spec_advance_kernel  one wave, after spec_commit.  n' = gen_len[0], n0 = g_spec[0], a = n' - n0 - 1 accepted drafts:
-//                     with g_on[r] set and 0 <= a <= k it stores g_spec[1 + a] to g_state[r][(n' - 1) & 1].  So after a
-//                     verify step slot (n' - 1) & 1 holds the state after n' - 1 generated tokens, and the next launch's
-//                     lazy advance over input_ids[0] is right whether it is dfa_mask_verify or the plain dfa_mask (after
-//                     the acceptance guard's fallback, or when a second request arrives).  A replay on a finished row
-//                     (the mask returned at once, gen_len stands still) rewrites the same value, or -- with a g_spec left
-//                     by an earlier request -- a dead word into a row nobody masks; admission and resume rewrite both
-//                     slots (ModelRunner._set_guided).
+//   dfa_spec_advance_kernel  after spec_commit: grid (S), one wave per sequence.  n' = gen_len[s], n0 = g_spec[9 s],
+//                     a = n' - n0 - 1 accepted drafts: with g_on[r + s] set and 0 <= a <= k it stores
+//                     g_spec[9 s + 1 + a] & 0xFFFF to g_state[r + s][(n' - 1) & 1].  So after a verify step slot
+//                     (n' - 1) & 1 holds the state after n' - 1 generated tokens, and the next launch's lazy advance over
+//                     input_ids[s] is right whether it is dfa_mask_verify -- over one sequence or several -- or the
+//                     plain dfa_mask (after the acceptance guard's fallback, or when another request arrives or
+//                     leaves).  A replay on a finished row (the mask returned at once, gen_len stands still) rewrites
+//                     the same value, or -- with a g_spec row left by an earlier request -- a dead word into a row
+//                     nobody masks; admission and resume rewrite both slots (ModelRunner._set_guided).
 #include "common.h"
 
 #define DFA_DEAD 0xFFFFu
@@ -52,7 +68,9 @@
 #define DFA_MAX_TOKEN_BYTES 32
 #define DFA_CHUNK 2048
 #define DFA_TPT 8  // tokens per thread
-#define DFA_MAX_VERIFY 8  // verify rows T = k + 1 of dfa_mask_verify_kernel
+#define DFA_MAX_VERIFY 8  // verify rows T = k + 1 of a sequence in dfa_mask_verify_kernel
+#define DFA_MAX_SEQS 8    // sequences of one dfa_mask_verify_kernel launch ...
+#define DFA_MAX_ROWS 32   // ... and their rows S * T (the verify step's limits)
 
 // The table of one row in LDS: step() is one transition; s == DEAD lands past SC and stays DEAD.
 struct DfaLds {
@@ -206,7 +224,11 @@ __global__ __launch_bounds__(256) void dfa_mask_verify_kernel(
     const int* __restrict__ finished, const int* __restrict__ eos, int neos, const int* __restrict__ draft,
     int* __restrict__ g_spec) {
   const int row = blockIdx.y, tid = threadIdx.x;  // verify row t = row: masked in the state after drafts 1..row
-  if (g_on[r] == 0 || finished[0] != 0) return;   // uniform per launch
+  const int T = gridDim.y, seq = blockIdx.z;      // sequence seq: state row seq, table row r + seq
+  r += seq;
+  if (g_on[r] == 0 || finished[seq] != 0) return;  // uniform per workgroup
+  draft += seq * (T - 1);
+  g_spec += 9 * seq;
 
   __shared__ __attribute__((aligned(16))) uint16_t s_trans[DFA_MAX_TABLE];
   __shared__ uint8_t s_cls[256];
@@ -216,10 +238,10 @@ __global__ __launch_bounds__(256) void dfa_mask_verify_kernel(
   const int S = min(max(g_dim[2 * r], 0), DFA_MAX_TABLE);
   const uint32_t C = (uint32_t)min(max(g_dim[2 * r + 1], 1), 256);
   const uint32_t SC = min((uint32_t)S * C, (uint32_t)DFA_MAX_TABLE);
-  const int n = gen_len[0];
+  const int n = gen_len[seq];
   const bool at_base = n == g_base[r] || n <= 0;
   const uint32_t slot_even = (uint32_t)g_state[2 * r] & 0xFFFFu, slot_odd = (uint32_t)g_state[2 * r + 1] & 0xFFFFu;
-  const int in_tok = input_ids[0];
+  const int in_tok = input_ids[seq];
 
   const int tok0 = blockIdx.x * DFA_CHUNK + tid;
   int off[DFA_TPT], len[DFA_TPT];
@@ -279,14 +301,18 @@ __global__ __launch_bounds__(256) void dfa_mask_verify_kernel(
     if (row == 0) g_spec[0] = n;
   }
   const bool eos_ok = cur == DFA_DEAD || (cur < (uint32_t)S && accept[(size_t)r * DFA_MAX_TABLE + cur] != 0);
-  dfa_walk_mask(t, cur, eos_ok, logits + (size_t)row * V, V, tok0, tok_blob, off, len, maxlen, byte, eos, neos);
+  dfa_walk_mask(t, cur, eos_ok, logits + ((size_t)seq * T + row) * V, V, tok0, tok_blob, off, len, maxlen, byte, eos,
+                neos);
 }
 
 __global__ __launch_bounds__(64) void dfa_spec_advance_kernel(const int* __restrict__ g_on, int* __restrict__ g_state,
                                                               const int* __restrict__ g_spec,
                                                               const int* __restrict__ gen_len, int r, int k) {
+  const int seq = blockIdx.x;  // sequence seq: gen_len[seq], g_spec row seq, table row r + seq
+  r += seq;
   if (threadIdx.x != 0 || g_on[r] == 0) return;
-  const int n1 = gen_len[0], a = n1 - g_spec[0] - 1;
+  g_spec += 9 * seq;
+  const int n1 = gen_len[seq], a = n1 - g_spec[0] - 1;
   if (a >= 0 && a <= k) g_state[2 * r + ((n1 - 1) & 1)] = g_spec[1 + a] & 0xFFFF;
 }
 
@@ -301,6 +327,19 @@ extern "C" int lsa_dfa_mask(float* logits, int B, int V, const int* tok_off, con
   return (int)hipGetLastError();
 }
 
+// logits [S * T, V]: the verify rows of the sequences in state rows 0 .. S - 1, table rows r .. r + S - 1; draft
+// [S * (T - 1)]; g_spec [S, 1 + 8].  The callers have checked the sizes.
+static int dfa_mask_verify_launch(float* logits, int S, int T, int V, const int* tok_off, const uint8_t* tok_blob,
+                                  const uint8_t* cls, const uint16_t* trans, const uint8_t* accept, const int* g_dim,
+                                  const int* g_on, int* g_state, const int* g_base, int r, const int* gen_len,
+                                  const int* input_ids, const int* finished, const int* eos, int neos,
+                                  const int* draft, int* g_spec, hipStream_t s) {
+  hipLaunchKernelGGL(dfa_mask_verify_kernel, dim3((V + DFA_CHUNK - 1) / DFA_CHUNK, T, S), dim3(256), 0, s, logits, V,
+                     tok_off, tok_blob, cls, trans, accept, g_dim, g_on, g_state, g_base, r, gen_len, input_ids,
+                     finished, eos, neos, draft, g_spec);
+  return (int)hipGetLastError();
+}
+
 // logits [T, V]: the verify rows of the sequence in state row 0, table row r; draft [T - 1]; g_spec [1 + 8].
 extern "C" int lsa_dfa_mask_verify(float* logits, int T, int V, const int* tok_off, const uint8_t* tok_blob,
                                    const uint8_t* cls, const uint16_t* trans, const uint8_t* accept, const int* g_dim,
@@ -308,15 +347,36 @@ extern "C" int lsa_dfa_mask_verify(float* logits, int T, int V, const int* tok_o
                                    const int* input_ids, const int* finished, const int* eos, int neos,
                                    const int* draft, int* g_spec, hipStream_t s) {
   if (T < 2 || T > DFA_MAX_VERIFY || V < 1 || neos < 0 || r < 0) return -1;
-  hipLaunchKernelGGL(dfa_mask_verify_kernel, dim3((V + DFA_CHUNK - 1) / DFA_CHUNK, T), dim3(256), 0, s, logits, V,
-                     tok_off, tok_blob, cls, trans, accept, g_dim, g_on, g_state, g_base, r, gen_len, input_ids,
-                     finished, eos, neos, draft, g_spec);
-  return (int)hipGetLastError();
+  return dfa_mask_verify_launch(logits, 1, T, V, tok_off, tok_blob, cls, trans, accept, g_dim, g_on, g_state, g_base, r,
+                                gen_len, input_ids, finished, eos, neos, draft, g_spec, s);
+}
+
+// The form over S sequences (sequence s: state row s, table row r + s, logits rows s T .., drafts s (T - 1) .., g_spec
+// row s).  Refused before any launch: S outside 1..8, T outside 2..8, S * T > 32.
+extern "C" int lsa_dfa_mask_verify_batch(float* logits, int S, int T, int V, const int* tok_off,
+                                         const uint8_t* tok_blob, const uint8_t* cls, const uint16_t* trans,
+                                         const uint8_t* accept, const int* g_dim, const int* g_on, int* g_state,
+                                         const int* g_base, int r, const int* gen_len, const int* input_ids,
+                                         const int* finished, const int* eos, int neos, const int* draft, int* g_spec,
+                                         hipStream_t s) {
+  if (S < 1 || S > DFA_MAX_SEQS || T < 2 || T > DFA_MAX_VERIFY || S * T > DFA_MAX_ROWS || V < 1 || neos < 0 || r < 0) {
+    return -1;
+  }
+  return dfa_mask_verify_launch(logits, S, T, V, tok_off, tok_blob, cls, trans, accept, g_dim, g_on, g_state, g_base, r,
+                                gen_len, input_ids, finished, eos, neos, draft, g_spec, s);
 }
 
 extern "C" int lsa_dfa_spec_advance(const int* g_on, int* g_state, const int* g_spec, const int* gen_len, int r, int k,
                                     hipStream_t s) {
   if (k < 1 || k > DFA_MAX_VERIFY - 1 || r < 0) return -1;
   hipLaunchKernelGGL(dfa_spec_advance_kernel, dim3(1), dim3(64), 0, s, g_on, g_state, g_spec, gen_len, r, k);
+  return (int)hipGetLastError();
+}
+
+// The form over S sequences: g_spec [S, 1 + 8], gen_len [S], table rows r .. r + S - 1.
+extern "C" int lsa_dfa_spec_advance_batch(const int* g_on, int* g_state, const int* g_spec, const int* gen_len, int r,
+                                          int S, int k, hipStream_t s) {
+  if (S < 1 || S > DFA_MAX_SEQS || k < 1 || k > DFA_MAX_VERIFY - 1 || S * (k + 1) > DFA_MAX_ROWS || r < 0) return -1;
+  hipLaunchKernelGGL(dfa_spec_advance_kernel, dim3(S), dim3(64), 0, s, g_on, g_state, g_spec, gen_len, r, k);
   return (int)hipGetLastError();
 }

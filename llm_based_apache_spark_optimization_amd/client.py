@@ -287,6 +287,8 @@ class EngineService(Backend):
                                 "spec_batch": getattr(lp.engine, "spec_batch", 1),
                                 "spec_batch_sampled": bool(getattr(getattr(lp.engine, "runner", None),
                                                                    "spec_batch_sampled", False)),
+                                "spec_batch_guided": bool(getattr(getattr(lp.engine, "runner", None),
+                                                                  "spec_batch_guided", False)),
                                 **lp.engine.stats} for m, lp in self._loops.items()}}
 
 

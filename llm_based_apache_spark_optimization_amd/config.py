@@ -82,6 +82,10 @@ class Settings:
     # requests that need the sampler speculate in such a run too, beside greedy ones (off: one of them makes the run
     # plain).  Needs spec_tokens, spec_sampled and spec_batch > 1; every request's tokens are those it generates alone
     spec_batch_sampled: bool = dataclasses.field(default_factory=lambda: _env("SPEC_BATCH_SAMPLED", False, bool))
+    # regex-constrained requests speculate in such a run too, beside unconstrained ones (off: one of them makes the run
+    # plain).  Needs guided, spec_guided, spec_tokens and spec_batch > 1 (and spec_batch_sampled for a constrained
+    # request that needs the sampler); every request's tokens are those of its plain guided steps
+    spec_batch_guided: bool = dataclasses.field(default_factory=lambda: _env("SPEC_BATCH_GUIDED", False, bool))
     tp: int = dataclasses.field(default_factory=lambda: _env("TP", 1, int))
     dp: int = dataclasses.field(default_factory=lambda: _env("DP", 1, int))
     max_batch: int = dataclasses.field(default_factory=lambda: _env("MAX_BATCH", 32, int))

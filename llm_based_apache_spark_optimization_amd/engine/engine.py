@@ -374,7 +374,10 @@ class LLMEngine:
             if self.device_timing:
                 ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
                 ev[0].record()
-            if spec_T and spec_S > 1 and sample:  # spec_batch_sampled: the sampled commit over the spec_S sequences
+            if spec_T and spec_S > 1 and guided:  # spec_batch_guided: the mask of every constrained sequence's rows,
+                # only while a running request is constrained (then the sampled commit, if one needs the sampler)
+                r.decode_spec(n_steps, max_ctx=max_ctx, guided=True, sample=sample, S=spec_S)
+            elif spec_T and spec_S > 1 and sample:  # spec_batch_sampled: the sampled commit over the spec_S sequences
                 r.decode_spec(n_steps, max_ctx=max_ctx, sample=True, S=spec_S)
             elif spec_T and spec_S > 1:  # spec_batch: greedy, unconstrained verify steps over slots 0 .. spec_S - 1
                 r.decode_spec(n_steps, max_ctx=max_ctx, S=spec_S)
@@ -396,7 +399,7 @@ class LLMEngine:
         with self._lock:
             self.stats["decode_s"] += time.perf_counter() - t0
             self.stats["decode_steps"] += n_steps
-            if guided and n_steps:  # plain masked steps and (spec_guided) masked verify steps
+            if guided and n_steps:  # plain masked steps and (spec_guided, spec_batch_guided) masked verify steps
                 self.stats["guided_steps"] += n_steps
                 REGISTRY.inc("lsa_guided_steps_total", n_steps, "decode steps run with the regex mask", model=self.name)
             if spec_T and n_steps:
@@ -507,8 +510,10 @@ class LLMEngine:
         steps over the sequences of slots 0 .. S - 1, S = bucket(highest slot + 1) <= spec_batch, else 0.  All or
         nothing -- a limit, not an oversight: one request that cannot speculate makes the whole run plain, because a
         mixed run would need rows of two kinds in one graph.  Every condition must hold: the scheduler runs no other
-        request and none is mid-prefill; every request is unconstrained, has ``speculate`` on and has not been
-        dropped by the acceptance guard; every request is greedy -- or, with ``spec_batch_sampled`` and
+        request and none is mid-prefill; every request has ``speculate`` on and has not been dropped by the acceptance
+        guard; every request is unconstrained -- or, with ``spec_batch_guided``, ``spec_guided`` and a guided runner,
+        any mix of constrained and unconstrained requests: the run then takes the guided verify graph exactly when at
+        least one running request is constrained; every request is greedy -- or, with ``spec_batch_sampled`` and
         ``spec_sampled``, any mix of greedy requests and requests that need the sampler: the run then takes the
         sampled verify graph exactly when at least one running request needs the sampler (a greedy request in it is a
         sequence with temperature 0 and penalty 1), and the greedy batched graph otherwise; every request has window
@@ -523,8 +528,10 @@ class LLMEngine:
         if r.bucket(self.sched.highest_slot + 1) > SB or any(not 0 <= q.slot < SB for q in reqs):
             return 0
         sampled_ok = getattr(r, "spec_batch_sampled", False) and getattr(r, "spec_sampled", False)
-        if any((q.params.needs_sampler and not sampled_ok) or q.dfa is not None or not q.params.speculate or q.spec_off
-               for q in reqs):
+        guided_ok = getattr(r, "spec_batch_guided", False) and getattr(r, "spec_guided", False) and \
+            getattr(r, "guided", False)
+        if any((q.params.needs_sampler and not sampled_ok) or (q.dfa is not None and not guided_ok)
+               or not q.params.speculate or q.spec_off for q in reqs):
             return 0
         T = r.spec_k() + 1
         if SB * T > 32:

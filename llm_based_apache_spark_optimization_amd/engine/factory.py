@@ -21,7 +21,8 @@ def build_engine(model: str, device: Optional[str] = None, checkpoint: Optional[
                  kv_reserve_tokens: int = 64, spec_tokens: int = 0, prefix_cache: bool = False,
                  prefix_cow_min_tokens: Optional[int] = None, spec_quantized: bool = False,
                  guided: bool = False, spec_guided: bool = False, spec_sampled: bool = False,
-                 spec_batch: int = 1, spec_batch_sampled: bool = False) -> LLMEngine:
+                 spec_batch: int = 1, spec_batch_sampled: bool = False,
+                 spec_batch_guided: bool = False) -> LLMEngine:
     """kv_dtype: paged KV cache dtype, "bf16" | "fp8" (None: LSA_KV_FP8, default bf16).
     max_new_cap: generated-token cap per request (None: the context window).
     kv_reserve_tokens: generated tokens whose KV is reserved at admission (the rest grows lazily; < 0 reserves
@@ -47,7 +48,13 @@ def build_engine(model: str, device: Optional[str] = None, checkpoint: Optional[
     the run plain).  The run then ends each verify step in the sampled commit over its sequences, where a greedy
     request is a sequence with temperature 0 and penalty 1; every request's tokens are those it generates alone.  An
     all-greedy run keeps the greedy batched graph.  Needs spec_tokens, spec_sampled and spec_batch > 1, and is inert
-    without any of them."""
+    without any of them.
+    spec_batch_guided: regex-constrained requests may be among the requests of such a run (off: one of them makes the
+    run plain).  The run then masks the verify rows of every constrained sequence in that sequence's own DFA states
+    and leaves an unconstrained sequence untouched; every request's tokens are those of its plain (guided) steps.  An
+    all-unconstrained run keeps the unguided batched graph.  Needs guided, spec_guided, spec_tokens and spec_batch > 1
+    (a constrained request that needs the sampler: spec_sampled and spec_batch_sampled too), and is inert without any
+    of them."""
     if device is None:
         device = f"cuda:{torch.cuda.current_device()}" if torch.cuda.is_available() else "cpu"
     t0 = time.perf_counter()
@@ -63,7 +70,7 @@ def build_engine(model: str, device: Optional[str] = None, checkpoint: Optional[
                          num_kv_blocks=num_kv_blocks, kv_memory_fraction=kv_memory_fraction, kv_dtype=kv_dtype,
                          max_new_cap=max_new_cap, spec_tokens=spec_tokens, spec_quantized=spec_quantized,
                          spec_guided=spec_guided, spec_sampled=spec_sampled, spec_batch=spec_batch,
-                         spec_batch_sampled=spec_batch_sampled)
+                         spec_batch_sampled=spec_batch_sampled, spec_batch_guided=spec_batch_guided)
     eng = LLMEngine(runner, tok, sync_every=sync_every, max_prefill_tokens=max_prefill_tokens, name=model,
                     prefill_chunk=prefill_chunk or None, kv_reserve_tokens=kv_reserve_tokens, spec_tokens=spec_tokens,
                     prefix_cache=prefix_cache, prefix_cow_min_tokens=prefix_cow_min_tokens, guided=guided)

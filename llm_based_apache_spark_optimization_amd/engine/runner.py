@@ -51,7 +51,7 @@ class ModelRunner:
                  fuse_rope: Optional[bool] = None, seq_parallel: Optional[bool] = None, sp_min_tokens: Optional[int] = None,
                  kv_dtype: Optional[str] = None, spec_tokens: int = 0, spec_ngram: tuple = (3, 1),
                  spec_quantized: bool = False, spec_guided: bool = False, spec_sampled: bool = False,
-                 spec_batch: int = 1, spec_batch_sampled: bool = False):
+                 spec_batch: int = 1, spec_batch_sampled: bool = False, spec_batch_guided: bool = False):
         self.w = weights
         # prompt-lookup speculative decoding (``_verify_step``): tokens drafted per step (0 = off) and the drafter's
         # (longest, shortest) n-gram.  Plain attributes: an experiment may set them on a built runner.
@@ -69,12 +69,17 @@ class ModelRunner:
         self.spec_sampled = bool(spec_sampled)
         # opt-in: the largest number S of running requests (slots 0 .. S - 1) whose decode run may be a run of verify
         # steps (``_verify_step(S=)``: S * T rows, ``spec_s`` clamps it).  1 = one request in slot 0 only.  Greedy,
-        # unconstrained requests only: guided verify steps stay one-sequence, sampled ones too without the next flag.
+        # unconstrained requests only: sampled and guided verify steps stay one-sequence without the next two flags.
         self.spec_batch = int(spec_batch)
         # opt-in: requests that need the sampler in the verify steps over S sequences too (``_verify_step(sample=True,
         # S=)``: the sampled commit over S sequences; a greedy request in such a step is a sequence with temperature 0
         # and penalty 1).  Inert without ``spec_sampled`` and ``spec_batch`` > 1.
         self.spec_batch_sampled = bool(spec_batch_sampled)
+        # opt-in: regex-constrained requests in the verify steps over S sequences too (``_verify_step(guided=True,
+        # S=)``: every constrained sequence's T rows are masked in that sequence's own DFA states, an unconstrained
+        # sequence beside it is untouched).  Inert without ``enable_guided``, ``spec_guided`` and ``spec_batch`` > 1; a
+        # constrained request that needs the sampler needs ``spec_batch_sampled`` as well.
+        self.spec_batch_guided = bool(spec_batch_guided)
         # acceptance guard of the engine: a request whose accepted-per-verify-step mean falls below this after 16
         # verify steps takes plain steps for the rest of its life.  Break-even = verify-step time / plain-step time - 1.
         # Measured on MI355X (scripts/bench_spec.py, profiles/spec/spec_decode_mi355x.jsonl; plain vs verify step, k = 3):
@@ -87,7 +92,9 @@ class ModelRunner:
         # The guard compares every request with this one value whatever S it ran at: set it to the row of the
         # spec_batch in use.  Sampled requests in such a step (``spec_batch_sampled``, against the plain sampled step of
         # bucket S; --batch --sampled, profiles/spec/spec_batch_sampled_mi355x.jsonl): 7B 0.08 / 0.12 / 0.33, 3B 0.14 /
-        # 0.16 / 0.25.
+        # 0.16 / 0.25.  Constrained requests in such a step (``spec_batch_guided``, against the plain guided step of bucket
+        # S; scripts/bench_guided.py --spec-batch, profiles/spec/spec_batch_guided_mi355x.jsonl): 7B 0.08 / 0.11, 3B 0.14 /
+        # 0.16 at S = 2 / 4.
         self.spec_min_accept = 0.0
         self._spec = None           # device buffers of the verify step (allocated on first use)
         self._spec_forced = None    # [nf, k] int32 planted drafts (tests / a later drafter), see set_spec_forced
@@ -894,11 +901,18 @@ class ModelRunner:
         ``sample`` with ``S`` > 1 (``spec_batch_sampled``): the sampled commit over the S sequences -- sequence s reads
         ring row s and entry s of every sampling parameter and draws at its own counter gen_len[s] + i, so each
         request's tokens are those it generates alone; a greedy request among them is a sequence with temperature 0
-        and penalty 1, whose rows the commit leaves as they are and whose picks are their argmax.  ``guided`` with
-        ``S`` > 1 stays refused."""
+        and penalty 1, whose rows the commit leaves as they are and whose picks are their argmax.
+
+        ``guided`` with ``S`` > 1 (``spec_batch_guided``): the mask over the S sequences in one launch -- sequence s is
+        masked in the states of table row s (= its slot, as in the plain decode mask) from its own drafts, and leaves
+        gen_len and its T states in row s of ``g_spec`` for the hand-over after the commit; a sequence without a
+        constraint (or finished, or an idle slot) is untouched, as an unconstrained row is in the plain ``dfa_mask``.
+        Each request's tokens are those of its plain guided steps.  With ``sample`` the mask runs before the sampled
+        commit over the S sequences, as in the one-sequence step."""
         w, d, Ts = self.w, self.d, self.spec_k() + 1
         sb = self._spec_bufs()
-        assert S == 1 or not guided, "guided verify steps are one-sequence"
+        assert S == 1 or not guided or (self.spec_batch_guided and self.spec_guided and self.guided), \
+            "guided verify steps are one-sequence"
         assert S == 1 or not sample or (self.spec_sampled and self.spec_batch_sampled), \
             "sampled verify steps over several sequences need spec_sampled and spec_batch_sampled"
         assert 1 <= S <= sb["ctx"].shape[0] and S * Ts <= 32, "verify step: S <= spec_batch sequences, S * T <= 32 rows"
@@ -959,7 +973,7 @@ class ModelRunner:
         if guided:
             ops.dfa_mask_verify(logits, self.g_tok_off, self.g_tok_blob, self.g_cls, self.g_trans, self.g_accept,
                                 self.g_dim, self.g_on, self.g_state, self.g_base, st[1], st[2], st[4], self.eos,
-                                draft, self.g_spec)
+                                draft, self.g_spec[0] if S == 1 else self.g_spec[:S])
         if sample:
             ops.spec_sample_commit(logits, draft, sb["stats"][0] if S == 1 else sb["stats"][:S], self.hist[:S],
                                    self.penalty[:S], self.temperature[:S], self.top_k[:S], self.top_p[:S],
@@ -970,7 +984,7 @@ class ModelRunner:
             ops.spec_commit(logits, draft, sb["stats"][0] if S == 1 else sb["stats"][:S], *st, self.eos, self.limit[:S],
                             self.eos_on[:S], part=sb["amax_part"] if self.on_gpu else None)
         if guided:
-            ops.dfa_spec_advance(self.g_on, self.g_state, self.g_spec, st[1], T - 1)
+            ops.dfa_spec_advance(self.g_on, self.g_state, self.g_spec[0] if S == 1 else self.g_spec[:S], st[1], Ts - 1)
 
     def _verify_linear_cpu(self, x, wt, epi, out, splitk=1, rownorm=None, pre=False):
         """CPU twin of the verify step's GEMMs, one row at a time with the rounding points of the plain batch-1 step's
@@ -1022,14 +1036,16 @@ class ModelRunner:
         ``S`` > 1: verify steps over the sequences of slots 0 .. S - 1 (``_verify_step(S=)``), one graph per (S, T,
         plan, forced buffer): the split plan is the decode plan of bucket S, the key the one-sequence key with S
         appended.  ``sample`` with ``S`` > 1 needs ``spec_batch_sampled``; its key is the greedy key, then "sample",
-        then S."""
+        then S.  ``guided`` with ``S`` > 1 needs ``spec_batch_guided``; its key is the one-sequence key, then True, then
+        "sample" if sampled, then S."""
         assert self.spec_supported(), ("speculative decoding: TP = 1, spec_tokens > 0, bf16 weights and KV cache "
                                        "(or spec_quantized)")
         assert not guided or (self.guided and self.spec_guided), "guided verify steps need enable_guided() and spec_guided"
         assert not sample or self.spec_sampled, "sampled verify steps need spec_sampled"
-        assert S == 1 or (S <= self.spec_s() and not guided and (not sample or self.spec_batch_sampled)), \
-            "verify steps over several sequences: S <= spec_batch (clamped), unconstrained, sampled only with " \
-            "spec_batch_sampled"
+        assert S == 1 or (S <= self.spec_s() and (not guided or self.spec_batch_guided)
+                          and (not sample or self.spec_batch_sampled)), \
+            "verify steps over several sequences: S <= spec_batch (clamped), constrained only with " \
+            "spec_batch_guided, sampled only with spec_batch_sampled"
         plan = tuple(self.ctx_plan(S, max_ctx))
         if not self.use_graphs:
             for _ in range(steps):
@@ -1073,7 +1089,9 @@ class ModelRunner:
         """Allocate the device side of regex-constrained decoding: the tokenizer's byte table (CSR: ``tok_off`` int32
         [>= V + 1], ``tok_blob`` uint8; numpy or torch, uploaded once) and one DFA table row per slot -- cls 256 B,
         trans 64 KiB, accept 32 KiB -- plus g_on, the two state slots, g_base and the (S, C) dims (ops.dfa_mask), and
-        g_spec: gen_len and the states of the T <= 8 verify rows of a guided verify step (ops.dfa_mask_verify)."""
+        g_spec: gen_len and the states of the T <= 8 verify rows of a guided verify step (ops.dfa_mask_verify), one row
+        of 1 + 8 words per sequence of the step: one row, or 8 with ``spec_batch_guided`` (the one-sequence step uses
+        row 0)."""
         off = torch.as_tensor(tok_off).to(torch.int64).reshape(-1)
         blob = torch.as_tensor(tok_blob).to(torch.uint8).reshape(-1)
         V = self.V
@@ -1095,7 +1113,7 @@ class ModelRunner:
         self.g_on = torch.zeros(S, **i32)
         self.g_state = torch.zeros(S, 2, **i32)
         self.g_base = torch.zeros(S, **i32)
-        self.g_spec = torch.zeros(1 + 8, **i32)
+        self.g_spec = torch.zeros(8 if self.spec_batch_guided else 1, 1 + 8, **i32)
         self.guided = True
         self.graphs.clear()
 

@@ -1706,7 +1706,27 @@ def dfa_mask_verify(logits, tok_off, tok_blob, cls, trans, accept, g_dim, g_on, 
     verify rows of the sequence in state row 0 (table row ``r``), ``draft`` [k] int32 what ``spec_draft`` wrote.  Row t
     is masked as ``dfa_mask`` masks a row whose state is the one after the input token and drafts 1..t (DEAD from the
     first draft that is -1, unknown, of 0 or > 32 bytes, or kills the walk).  ``g_spec`` int32 [1 + 8] receives gen_len
-    and the T states for ``dfa_spec_advance``.  The exact rule: ``ops.reference.dfa_mask_verify``."""
+    and the T states for ``dfa_spec_advance``.  The exact rule: ``ops.reference.dfa_mask_verify``.
+
+    A 2-D ``g_spec`` [S, 1 + 8] selects the form over S sequences (``spec_batch_guided``; as the 2-D ``stats`` of
+    ``spec_commit``): ``logits`` [S * T, V], ``draft`` [>= S * k]; sequence s is the sequence of state row s and table
+    row s (``r`` must be 0: table row = state row = slot, as in ``dfa_mask``), masks its rows s T .. s T + T - 1 from
+    its own drafts and fills g_spec[s].  A sequence whose g_on is 0 or that has finished is left untouched, g_spec row
+    included.  1 <= S <= 8, 2 <= T <= 8, S * T <= 32.  The exact rule: ``ops.reference.dfa_mask_verify_batch``."""
+    if g_spec.dim() == 2:
+        S, R = g_spec.shape[0], logits.shape[0]
+        if not (1 <= S <= 8 and g_spec.shape[1] == 9 and R % S == 0 and 2 <= R // S <= 8 and R <= 32):
+            raise ValueError("dfa_mask_verify: g_spec [1 <= S <= 8, 9], logits [S * T, V] with 2 <= T <= 8 verify rows "
+                             "per sequence and S * T <= 32")
+        if draft.numel() < S * (R // S - 1) or min(gen_len.numel(), input_ids.numel(), finished.numel()) < S:
+            raise ValueError("dfa_mask_verify: draft [S * (T - 1)] and one state row per sequence")
+        if int(r) != 0 or S > cls.shape[0]:
+            raise ValueError("dfa_mask_verify over S sequences: table row = state row (r = 0), S <= table rows")
+        if not _gpu(logits):
+            return ref.dfa_mask_verify_batch(logits, tok_off, tok_blob, cls, trans, accept, g_dim, g_on, g_state, g_base,
+                                             gen_len, input_ids, finished, eos, draft, g_spec, 0)
+        return ext().dfa_mask_verify(logits, tok_off, tok_blob, cls, trans, accept, g_dim, g_on, g_state, g_base, 0,
+                                     gen_len, input_ids, finished, eos, draft, g_spec)
     if not 2 <= logits.shape[0] <= 8:
         raise ValueError("dfa_mask_verify: 2 <= T <= 8 verify rows")
     if not _gpu(logits):
@@ -1719,7 +1739,17 @@ def dfa_mask_verify(logits, tok_off, tok_blob, cls, trans, accept, g_dim, g_on, 
 def dfa_spec_advance(g_on, g_state, g_spec, gen_len, k: int, r: int = 0):
     """After ``spec_commit`` (one wave): with a = gen_len[0] - g_spec[0] - 1 accepted drafts, 0 <= a <= k, the state
     g_spec[1 + a] goes to g_state[r, (gen_len[0] - 1) & 1] -- where the next mask launch, verify or plain, advances
-    from."""
+    from.  A 2-D ``g_spec`` [S, 1 + 8] selects the form over S sequences (one launch): sequence s reads gen_len[s] and
+    g_spec[s] and stores to g_state[s]; ``r`` must be 0."""
+    if g_spec.dim() == 2:
+        S = g_spec.shape[0]
+        if not (1 <= S <= 8 and g_spec.shape[1] == 9 and 1 <= int(k) <= 7 and S * (int(k) + 1) <= 32):
+            raise ValueError("dfa_spec_advance: g_spec [1 <= S <= 8, 9], 1 <= k <= 7, S * (k + 1) <= 32")
+        if gen_len.numel() < S or int(r) != 0 or S > g_on.numel():
+            raise ValueError("dfa_spec_advance over S sequences: gen_len [S], r = 0, S <= table rows")
+        if not _gpu(g_state):
+            return ref.dfa_spec_advance_batch(g_on, g_state, g_spec, gen_len, k, 0)
+        return ext().dfa_spec_advance(g_on, g_state, g_spec, gen_len, 0, int(k))
     if not _gpu(g_state):
         return ref.dfa_spec_advance(g_on, g_state, g_spec, gen_len, k, r)
     ext().dfa_spec_advance(g_on, g_state, g_spec, gen_len, int(r), int(k))

@@ -327,6 +327,27 @@ def dfa_spec_advance(g_on, g_state, g_spec, gen_len, k, r=0):
         g_state[r, (n1 - 1) & 1] = int(g_spec[1 + a]) & 0xFFFF
 
 
+def dfa_mask_verify_batch(logits, tok_off, tok_blob, cls, trans, accept, g_dim, g_on, g_state, g_base, gen_len,
+                          input_ids, finished, eos, draft, g_spec, r=0):
+    """Host twin of dfa_mask_verify_kernel over S = g_spec.shape[0] sequences: ``logits`` [S * T, V], ``draft`` [S * k],
+    ``g_spec`` [S, 1 + 8].  Sequence s is one application of ``dfa_mask_verify`` -- the single statement of the rule --
+    to its own slices: state row s, table row r + s, logits rows s T .. s T + T - 1, drafts s k .. s k + k - 1 and
+    g_spec[s].  An unconstrained (g_on[r + s] == 0) or finished sequence is left as it is, with its g_spec row."""
+    S = g_spec.shape[0]
+    T = logits.shape[0] // S
+    for s in range(S):
+        dfa_mask_verify(logits[s * T:(s + 1) * T], tok_off, tok_blob, cls, trans, accept, g_dim, g_on, g_state, g_base,
+                        gen_len[s:s + 1], input_ids[s:s + 1], finished[s:s + 1], eos, draft[s * (T - 1):(s + 1) * (T - 1)],
+                        g_spec[s], r + s)
+
+
+def dfa_spec_advance_batch(g_on, g_state, g_spec, gen_len, k, r=0):
+    """Host twin of dfa_spec_advance_kernel over S = g_spec.shape[0] sequences: ``dfa_spec_advance`` of sequence s on
+    gen_len[s], g_spec[s] and table row r + s."""
+    for s in range(g_spec.shape[0]):
+        dfa_spec_advance(g_on, g_state, g_spec[s], gen_len[s:s + 1], k, r + s)
+
+
 # ----------------------------------------------------------------------------------- prefix cache
 def kv_copy_blocks(kv, kv_scale, pairs):
     """Copy the whole KV block src to dst, with its scales, in every layer for K and V (csrc/kernels/kv_copy.hip);

@@ -25,9 +25,22 @@ profiles/spec/spec_guided_mi355x.jsonl:
            and against the plain guided step (what a constrained request pays today): the break-even accepted drafts
            per step of a constrained request = guided verify / plain guided - 1.  16-step runs in a mirrored order.
 
+With --spec-batch: speculative decoding of several requests of which some are constrained (``spec_batch_guided``),
+appended to profiles/spec/spec_batch_guided_mi355x.jsonl:
+
+  kernel   the S-sequence form of ops.dfa_mask_verify beside the unchanged ops.dfa_mask at B = S * T on the same logits,
+           every baseline row in the state its verify row is in: (S, T) = (2, 4), (4, 4), (4, 8) at V = 32,000 and (4, 5)
+           at V = 128,256, both patterns, every sequence constrained; and one record per shape with half the sequences
+           unconstrained (g_on = 0 in both arms), which shows the early return.
+  step     S constrained requests per model (duckdb-nsql-7B 128-token prompts, Llama-3.2-3B 2k-token prompts; S = 2 and
+           4, k = 3), planted drafts that the pattern allows: the guided batched verify step against the unguided
+           batched verify step (what the mask of S * T rows and the hand-over cost) and against the plain guided step
+           of bucket S (what S constrained requests pay without the flag): the break-even accepted drafts per step and
+           request of a constrained batch = guided batched verify / plain guided - 1.  16-step runs, mirrored order.
+
 Appends JSON lines to profiles/guided/guided_mask_mi355x.jsonl (--out overrides).  Needs a GPU.
 
-  python scripts/bench_guided.py [--spec] [--layers N] [--skip kernel,step] [--reps 5] [--out FILE]
+  python scripts/bench_guided.py [--spec | --spec-batch] [--layers N] [--skip kernel,step] [--reps 5] [--out FILE]
 """
 from __future__ import annotations
 
@@ -52,6 +65,7 @@ from llm_based_apache_spark_optimization_amd.models.llama import init_random  # 
 
 OUT = os.path.join(ROOT, "profiles", "guided", "guided_mask_mi355x.jsonl")
 OUT_SPEC = os.path.join(ROOT, "profiles", "spec", "spec_guided_mi355x.jsonl")
+OUT_SPEC_BATCH = os.path.join(ROOT, "profiles", "spec", "spec_batch_guided_mi355x.jsonl")
 LIMIT_PATTERN = r"(abcdefghijklmnopqrstuvwxyz01234){33}"  # 1024 states x 32 classes
 
 
@@ -318,21 +332,151 @@ def bench_spec_step(dev, layers: int, reps: int) -> None:
         torch.cuda.empty_cache()
 
 
+def bench_spec_batch_kernel(dev, reps: int) -> None:
+    sql = compile_regex(prompts.SQL_STATEMENT_REGEX)
+    lim = compile_regex(LIMIT_PATTERN)
+    pats = (("sql", sql, sql.walk(sql.start, b"SELECT ")), ("limit", lim, lim.walk(lim.start, b"abc")))
+    for V, shapes in ((32000, ((2, 4), (4, 4), (4, 8))), (128256, ((4, 5),))):
+        off_h, blob_h = synthetic_vocab(V)
+        off, blob = off_h.to(dev), blob_h.to(dev)
+        i32 = dict(dtype=torch.int32, device=dev)
+        eos = torch.tensor([2], **i32)
+        for name, dfa, state in pats:
+            for S, T in shapes:
+                drafts = legal_drafts(dfa, state, off_h, blob_h, T - 1)
+                states = [state]
+                for t in drafts:
+                    states.append(dfa.walk(states[-1], bytes(blob_h[off_h[t]:off_h[t + 1]].tolist())))
+                assert DEAD not in states
+                B = S * T
+                cls, trans, accept, dim, on, gst, base = tables(dfa, B, dev, state)
+                gst.copy_(torch.tensor([[s, s] for s in states] * S, **i32))  # baseline row s T + t sits in state s_t
+                z = torch.zeros(B, **i32)
+                logits = torch.randn(B, V, device=dev)
+                dr = torch.tensor(drafts * S, **i32)
+                gst0 = torch.full((B, 2), state, **i32)
+                for half in (False, True):  # half: the odd sequences carry no constraint, in both arms
+                    wv, wm = logits.clone(), logits.clone()
+                    g_spec = torch.zeros(S, 9, **i32)
+                    on_v, on_m = on.clone(), on.clone()
+                    if half:
+                        on_v[1:S:2] = 0
+                        on_m.view(S, T)[1::2] = 0
+                    arms = {
+                        "dfa_mask_verify_S": lambda: ops.dfa_mask_verify(wv, off, blob, cls, trans, accept, dim, on_v,
+                                                                         gst0, base, z, z, z, eos, dr, g_spec),
+                        "dfa_mask_B_ST": lambda: ops.dfa_mask(wm, off, blob, cls, trans, accept, dim, on_m, gst, base, z,
+                                                              z, z, eos),
+                    }
+                    us = {k: [] for k in arms}
+                    for _ in range(reps):  # alternate the arms
+                        for k, fn in arms.items():
+                            us[k].append(time_graph(fn))
+                    live = [s for s in range(S) if not (half and s & 1)]
+                    assert torch.equal(wv, wm) and all(g_spec[s, 1:1 + T].tolist() == states for s in live)
+                    assert all(torch.equal(wv[s * T:(s + 1) * T], logits[s * T:(s + 1) * T]) for s in range(S) if s not in live)
+                    med = {k: round(statistics.median(v), 2) for k, v in us.items()}
+                    emit(dict(bench="spec_batch_kernel", V=V, S=S, T=T, rows=B, pattern=name, states=dfa.n_states,
+                              classes=dfa.n_classes, constrained_sequences=len(live),
+                              draft_bytes=[int(off_h[t + 1] - off_h[t]) for t in drafts],
+                              tokens_alive_per_masked_row=int(torch.isfinite(wv[:T]).sum()) // T, us=med,
+                              draft_walk_us=round(med["dfa_mask_verify_S"] - med["dfa_mask_B_ST"], 2),
+                              ratio=round(med["dfa_mask_verify_S"] / med["dfa_mask_B_ST"], 3)))
+
+
+def bench_spec_batch_step(dev, layers: int, reps: int, Ss=(2, 4), k: int = 3, models=None) -> None:
+    dfa = compile_regex(prompts.SQL_STATEMENT_REGEX)
+    inside = dfa.walk(dfa.start, b"SELECT ")
+    for base, plen in (("duckdb-nsql", 128), ("llama3.2", 2048)):
+        if models and base not in models:
+            continue
+        spec = get_spec(base)
+        if layers:
+            spec = dataclasses.replace(spec, n_layers=layers, name=f"{base}-{layers}l")
+        w = init_random(spec, dev, seed=5, kind="bf16")
+        new, run, SM = 1024, 16, max(Ss)
+        r = ModelRunner(w, max_slots=SM, max_model_len=plen + new + 64, num_kv_blocks=SM * ((plen + new) // 64 + 3) + 1,
+                        spec_tokens=k, spec_guided=True, spec_batch=SM, spec_batch_guided=True)
+        off_h, blob_h = synthetic_vocab(spec.vocab_size)
+        r.enable_guided(off_h, blob_h)
+        eng = LLMEngine(r, name=spec.name, kv_reserve_tokens=-1, guided=True, max_prefill_tokens=SM * plen + 64)
+        assert r.spec_k() == k and r.spec_s() == SM, (r.spec_k(), r.spec_s())
+        g = torch.Generator().manual_seed(7)
+        ids = [[1] + torch.randint(3, spec.vocab_size, (plen - 1,), generator=g).tolist() for _ in range(SM)]
+        ctx = plen + new
+        r.set_spec_forced(torch.tensor([legal_drafts(dfa, inside, off_h, blob_h, k)], dtype=torch.int32))
+        for S in Ss:
+            for p in ids[:S]:
+                eng.add_request(p, SamplingParams(max_tokens=new, regex=prompts.SQL_STATEMENT_REGEX))
+            s0 = eng.stats["spec_steps"]
+            eng.step()  # prefill + one run of guided verify steps over the S sequences
+            assert eng.stats["spec_steps"] > s0
+
+            def rebase() -> None:
+                """The unguided arms commit tokens the DFA never saw: restart the lazy advance inside the statement."""
+                r.g_base[:S].copy_(r.gen_len[:S])
+                r.g_state[:S].fill_(inside)
+
+            def timed(arm: str) -> float:
+                if arm in ("guided_verify", "guided"):
+                    rebase()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                if arm.endswith("verify"):
+                    r.decode_spec(run, max_ctx=ctx, guided=arm == "guided_verify", S=S)
+                else:
+                    r.decode(S, run, False, max_ctx=ctx, guided=arm == "guided")
+                e1.record()
+                torch.cuda.synchronize()
+                return e0.elapsed_time(e1) / run
+
+            order = ("guided_verify", "verify", "guided", "plain")
+            for arm in order:
+                timed(arm)  # warms the four graphs
+            ms = {arm: [] for arm in order}
+            n0 = r.gen_len[:S].tolist()
+            for _ in range(reps):  # mirrored: the context grows with every run, the order cancels it
+                for arm in order + order[::-1]:
+                    ms[arm].append(timed(arm))
+            m = {arm: statistics.mean(v) for arm, v in ms.items()}
+            emit(dict(bench="spec_batch_step", model=spec.name, layers=spec.n_layers, prompt=plen, vocab=spec.vocab_size,
+                      k=k, T=k + 1, S=S, rows=S * (k + 1), rows_live_after=S - int(r.finished[:S].sum()),
+                      steps=reps * 8 * run, tokens=[a - b for a, b in zip(r.gen_len[:S].tolist(), n0)],
+                      plain_step_ms=round(m["plain"], 4), guided_step_ms=round(m["guided"], 4),
+                      verify_step_ms=round(m["verify"], 4), guided_verify_step_ms=round(m["guided_verify"], 4),
+                      mask_verify_cost_us=round((m["guided_verify"] - m["verify"]) * 1e3, 1),
+                      mask_plain_cost_us=round((m["guided"] - m["plain"]) * 1e3, 1),
+                      break_even_unconstrained=round(m["verify"] / m["plain"] - 1, 3),
+                      break_even_constrained=round(m["guided_verify"] / m["guided"] - 1, 3)))
+            eng.abort_all("bench over")
+        del eng, r, w
+        torch.cuda.empty_cache()
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--layers", type=int, default=0, help="truncate the models to this many layers (0 = full depth)")
     ap.add_argument("--skip", default="", help="comma list of kernel,step")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--spec", action="store_true", help="measure spec_guided (verify-row mask, guided verify step)")
+    ap.add_argument("--spec-batch", action="store_true",
+                    help="measure spec_batch_guided (the mask over S sequences, the guided batched verify step)")
+    ap.add_argument("--models", default="", help="comma list of duckdb-nsql,llama3.2 (--spec-batch step; default both)")
     ap.add_argument("--out", default="", help="JSON-lines file to append to")
     a = ap.parse_args()
     global OUT
-    OUT = a.out or (OUT_SPEC if a.spec else OUT)
+    OUT = a.out or (OUT_SPEC_BATCH if a.spec_batch else OUT_SPEC if a.spec else OUT)
     if not torch.cuda.is_available():
         raise SystemExit("bench_guided.py needs a GPU")
     ops.ext()
     dev = torch.device("cuda:0")
     skip = set(a.skip.split(",")) if a.skip else set()
+    if a.spec_batch:
+        if "kernel" not in skip:
+            bench_spec_batch_kernel(dev, a.reps)
+        if "step" not in skip:
+            bench_spec_batch_step(dev, a.layers, a.reps, models=set(a.models.split(",")) if a.models else None)
+        return
     if a.spec:
         if "kernel" not in skip:
             bench_spec_kernel(dev, a.reps)
