@@ -88,13 +88,14 @@ int lsa_sample_commit(float* logits, int B, int V, unsigned long long* part, uns
                       int window, const float* penalty, const int* last_n, const float* temperature, const int* top_k,
                       const float* top_p, const unsigned long long* seeds, int* out_tokens, int max_new, int* gen_len,
                       int* input_ids, int* positions, int* finished, const int* eos, int neos, const int* limit,
-                      const int* eos_on, hipStream_t s);
+                      const int* eos_on, const float* presence, const float* frequency, const float* min_p,
+                      hipStream_t s);
 int lsa_spec_sample_commit(float* logits, int S, int T, int V, const int* draft, long long* stats, int* hist, int window,
                            const float* penalty, const int* last_n, const float* temperature, const int* top_k,
                            const float* top_p, const unsigned long long* seeds, int* out_tokens, int max_new,
                            int* gen_len, int* input_ids, int* positions, int* finished, const int* eos, int neos,
                            const int* limit, const int* eos_on, unsigned long long* part, unsigned long long* cand,
-                           int* picks, hipStream_t s);
+                           int* picks, const float* presence, const float* frequency, const float* min_p, hipStream_t s);
 int lsa_fp8_gemm(const void* X, int ldx, int M, int K, const void* Wq, const float* wscale, int N, void* out, int epi,
                  int nb, int splitk, hipStream_t stream);
 int lsa_fp8_dequant(const void* Wq, const float* wscale, int N, int K, void* Wf, hipStream_t s);
@@ -1201,16 +1202,30 @@ void dfa_spec_advance(const at::Tensor& g_on, at::Tensor& g_state, const at::Ten
         "dfa_spec_advance");
 }
 
+// presence / frequency / min_p of the sampled commits: optional f32, one entry per row (sequence); checked before any
+// launch
+static void sampler_option(const c10::optional<at::Tensor>& t, int rows, const char* name) {
+  if (!t.has_value()) return;
+  need(*t, at::kFloat, name);
+  TORCH_CHECK(t->numel() >= rows && t->is_contiguous(), name, ": one f32 per row");
+}
+
 void sample_commit(at::Tensor& logits, at::Tensor& part, at::Tensor& cand, const c10::optional<at::Tensor>& hist,
                    const c10::optional<at::Tensor>& penalty, const c10::optional<at::Tensor>& last_n,
                    const at::Tensor& temperature, const at::Tensor& top_k,
                    const at::Tensor& top_p, const at::Tensor& seeds, at::Tensor& out_tokens, at::Tensor& gen_len,
                    at::Tensor& input_ids, at::Tensor& positions, at::Tensor& finished, const at::Tensor& eos,
-                   const at::Tensor& limit, const at::Tensor& eos_on) {
+                   const at::Tensor& limit, const at::Tensor& eos_on,
+                   const c10::optional<at::Tensor>& presence = c10::nullopt,
+                   const c10::optional<at::Tensor>& frequency = c10::nullopt,
+                   const c10::optional<at::Tensor>& min_p = c10::nullopt) {
   need(logits, at::kFloat, "logits");
   TORCH_CHECK(logits.dim() == 2 && logits.is_contiguous(), "logits: contiguous [B, V]");
   const int B = logits.size(0), V = logits.size(1);
   check_state(B, out_tokens, gen_len, input_ids, positions, finished, eos, limit, eos_on);
+  sampler_option(presence, B, "presence");
+  sampler_option(frequency, B, "frequency");
+  sampler_option(min_p, B, "min_p");
   need(part, at::kLong, "part");
   need(cand, at::kLong, "cand");
   TORCH_CHECK(part.numel() >= (int64_t)B * ((V + 4095) / 4096) && cand.numel() >= (int64_t)B * ((V + 2047) / 2048) * 64,
@@ -1233,7 +1248,8 @@ void sample_commit(at::Tensor& logits, at::Tensor& part, at::Tensor& cand, const
                           top_p.data_ptr<float>(), reinterpret_cast<const unsigned long long*>(seeds.data_ptr()),
                           out_tokens.data_ptr<int>(), out_tokens.size(1), gen_len.data_ptr<int>(),
                           input_ids.data_ptr<int>(), positions.data_ptr<int>(), finished.data_ptr<int>(),
-                          eos.data_ptr<int>(), eos.numel(), limit.data_ptr<int>(), eos_on.data_ptr<int>(), cur_stream()),
+                          eos.data_ptr<int>(), eos.numel(), limit.data_ptr<int>(), eos_on.data_ptr<int>(),
+                          ptr<const float>(presence), ptr<const float>(frequency), ptr<const float>(min_p), cur_stream()),
         "sample_commit");
 }
 
@@ -1248,7 +1264,9 @@ void spec_sample_commit(at::Tensor& logits, const at::Tensor& draft, at::Tensor&
                         const at::Tensor& top_p, const at::Tensor& seeds, at::Tensor& out_tokens, at::Tensor& gen_len,
                         at::Tensor& input_ids, at::Tensor& positions, at::Tensor& finished, const at::Tensor& eos,
                         const at::Tensor& limit, const at::Tensor& eos_on, at::Tensor& part, at::Tensor& cand,
-                        at::Tensor& picks) {
+                        at::Tensor& picks, const c10::optional<at::Tensor>& presence = c10::nullopt,
+                        const c10::optional<at::Tensor>& frequency = c10::nullopt,
+                        const c10::optional<at::Tensor>& min_p = c10::nullopt) {
   need(logits, at::kFloat, "logits");
   need(stats, at::kLong, "stats");
   const bool rows = stats.dim() == 2 && stats.size(0) > 1;  // the S-sequence form
@@ -1287,6 +1305,9 @@ void spec_sample_commit(at::Tensor& logits, const at::Tensor& draft, at::Tensor&
     need(*last_n, at::kInt, "last_n");
     TORCH_CHECK(last_n->numel() >= S, "last_n: one per sequence");
   }
+  sampler_option(presence, S, "presence");
+  sampler_option(frequency, S, "frequency");
+  sampler_option(min_p, S, "min_p");
   const int window = hist.has_value() ? hist->size(1) : 0;
   check(lsa_spec_sample_commit(logits.data_ptr<float>(), S, T, V, draft.data_ptr<int>(),
                                reinterpret_cast<long long*>(stats.data_ptr<int64_t>()), ptr<int>(hist), window,
@@ -1297,7 +1318,9 @@ void spec_sample_commit(at::Tensor& logits, const at::Tensor& draft, at::Tensor&
                                positions.data_ptr<int>(), finished.data_ptr<int>(), eos.data_ptr<int>(), eos.numel(),
                                limit.data_ptr<int>(), eos_on.data_ptr<int>(),
                                reinterpret_cast<unsigned long long*>(part.data_ptr()),
-                               reinterpret_cast<unsigned long long*>(cand.data_ptr()), picks.data_ptr<int>(), cur_stream()),
+                               reinterpret_cast<unsigned long long*>(cand.data_ptr()), picks.data_ptr<int>(),
+                               ptr<const float>(presence), ptr<const float>(frequency), ptr<const float>(min_p),
+                               cur_stream()),
         "spec_sample_commit");
 }
 
@@ -1492,7 +1515,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("cu_q"), py::arg("ctx_lens"), py::arg("work"), py::arg("H"), py::arg("Hkv"), py::arg("scale"),
         py::arg("out"), py::arg("rows32") = 0, py::arg("xf_mt") = 0);
   m.def("argmax_commit", &argmax_commit);
-  m.def("sample_commit", &sample_commit);
+  m.def("sample_commit", &sample_commit, py::arg("logits"), py::arg("part"), py::arg("cand"), py::arg("hist"),
+        py::arg("penalty"), py::arg("last_n"), py::arg("temperature"), py::arg("top_k"), py::arg("top_p"),
+        py::arg("seeds"), py::arg("out_tokens"), py::arg("gen_len"), py::arg("input_ids"), py::arg("positions"),
+        py::arg("finished"), py::arg("eos"), py::arg("limit"), py::arg("eos_on"), py::arg("presence") = py::none(),
+        py::arg("frequency") = py::none(), py::arg("min_p") = py::none());
   m.def("attn_verify", &attn_verify, py::arg("q"), py::arg("kc"), py::arg("vc"), py::arg("block_table"),
         py::arg("pos0"), py::arg("H"), py::arg("Hkv"), py::arg("scale"), py::arg("chunk_blocks"), py::arg("nsplit"),
         py::arg("unsplit_max"), py::arg("out"), py::arg("opart"), py::arg("mlpart"), py::arg("counters"),
@@ -1501,7 +1528,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("gen_len"), py::arg("input_ids"), py::arg("positions"), py::arg("k"), py::arg("n_max"), py::arg("n_min"),
         py::arg("forced"), py::arg("spec_ids"), py::arg("spec_pos"), py::arg("spec_draft"));
   m.def("spec_commit", &spec_commit);
-  m.def("spec_sample_commit", &spec_sample_commit);
+  m.def("spec_sample_commit", &spec_sample_commit, py::arg("logits"), py::arg("draft"), py::arg("stats"),
+        py::arg("hist"), py::arg("penalty"), py::arg("last_n"), py::arg("temperature"), py::arg("top_k"),
+        py::arg("top_p"), py::arg("seeds"), py::arg("out_tokens"), py::arg("gen_len"), py::arg("input_ids"),
+        py::arg("positions"), py::arg("finished"), py::arg("eos"), py::arg("limit"), py::arg("eos_on"), py::arg("part"),
+        py::arg("cand"), py::arg("picks"), py::arg("presence") = py::none(), py::arg("frequency") = py::none(),
+        py::arg("min_p") = py::none());
   m.def("dfa_mask", &dfa_mask, py::arg("logits"), py::arg("tok_off"), py::arg("tok_blob"), py::arg("cls"),
         py::arg("trans"), py::arg("accept"), py::arg("g_dim"), py::arg("g_on"), py::arg("g_state"), py::arg("g_base"),
         py::arg("rows"), py::arg("gen_len"), py::arg("input_ids"), py::arg("finished"), py::arg("eos"));

@@ -2,9 +2,10 @@
 //
 //   lsa_argmax_partial   [B, V] f32 logits -> per-chunk packed (orderable key << 32 | ~index) maxima
 //   lsa_sample_commit    per row: greedy (temperature <= 0) = reduce the argmax partials; otherwise
-//                        repetition penalty (last `window` tokens, llama.cpp semantics), top-k (<= 64)
-//                        by a per-chunk bitonic sort in LDS, temperature softmax, top-p nucleus and a
-//                        counter-based RNG draw.  Then the decode state is advanced in place:
+//                        repetition / presence / frequency penalties (last `window` tokens, llama.cpp semantics),
+//                        top-k (<= 64) by a per-chunk bitonic sort in LDS, temperature softmax, top-p nucleus and
+//                        min-p on the same probabilities, and a counter-based RNG draw.  Then the decode state is
+//                        advanced in place:
 //                        out_tokens[b, gen_len[b]] = tok, gen_len++, input_ids = tok, positions++,
 //                        finished on EOS / length.  A finished row keeps its position (its KV slot is
 //                        re-written, never a new block), so a replayed graph can never walk past the
@@ -90,6 +91,9 @@ __global__ __launch_bounds__(64) void argmax_commit_kernel(const unsigned long l
 __device__ void bitonic_desc(unsigned long long* a, int n) {
   for (int k = 2; k <= n; k <<= 1) {
     for (int j = k >> 1; j > 0; j >>= 1) {
+      // the compare-exchange loop starts on an instruction-cache line, wherever the code before the sort puts it (a
+      // few bytes more ahead of it moved the sort of 4096 candidates by 5%: README, "Sampling options")
+      asm volatile(".p2align 6");
       for (int i = threadIdx.x; i < n; i += blockDim.x) {
         const int ix = i ^ j;
         if (ix > i) {
@@ -108,27 +112,43 @@ __device__ void bitonic_desc(unsigned long long* a, int n) {
 
 // repetition penalty applied in place (llama.cpp / Ollama semantics: logit / pen if > 0, else * pen) to
 // each distinct token among the row's last `last_n` context tokens (prompt + generated), read from the
-// position-indexed ring `hist` ending at the current input position
+// position-indexed ring `hist` ending at the current input position.  Then llama.cpp's presence / frequency penalties
+// over the same window: a token that occurs c times in it loses fma(c, frequency, presence) (one rounding of the
+// subtrahend, one of the subtraction; ops/reference.py repeat_penalty is the exact host twin).  penalty / presence /
+// frequency: per row, null = off (1 / 0 / 0); a row with all three off is left alone.
+__device__ __forceinline__ float penalised(float v, float pen, float pres, float freq, int c) {
+#pragma clang fp contract(off)  // v * pen and the subtraction round separately: no second fused multiply-add
+  v = v > 0.f ? v / pen : v * pen;
+  return v - __fmaf_rn((float)c, freq, pres);
+}
+
 __global__ __launch_bounds__(64) void repeat_penalty_kernel(float* __restrict__ logits, int V,
                                                             const int* __restrict__ hist, int window,
                                                             const float* __restrict__ penalty,
                                                             const int* __restrict__ last_n,
-                                                            const int* __restrict__ positions) {
+                                                            const int* __restrict__ positions,
+                                                            const float* __restrict__ presence,
+                                                            const float* __restrict__ frequency) {
   const int b = blockIdx.x;
-  const float pen = penalty[b];
-  if (pen == 1.0f) return;
+  const float pen = penalty ? penalty[b] : 1.0f;
+  const float pres = presence ? presence[b] : 0.f;
+  const float freq = frequency ? frequency[b] : 0.f;
+  if (pen == 1.0f && pres == 0.f && freq == 0.f) return;
+  const bool counted = freq != 0.f;  // (the count multiplies nothing else)
   const int* hrow = hist + (size_t)b * window;
   const int p = positions[b];
   const int n = min(min(last_n ? last_n[b] : window, window), p + 1);
   for (int i = threadIdx.x; i < n; i += 64) {
     const int t = hrow[(p - i) % window];
     if (t < 0 || t >= V) continue;
-    bool first = true;  // the most recent occurrence applies the penalty, once per distinct token
+    bool first = true;  // the most recent occurrence applies the penalties, once per distinct token
     for (int k = 0; k < i; ++k) first &= (hrow[(p - k) % window] != t);
     if (!first) continue;
+    int c = 1;  // its occurrences in the window: itself and the older ones
+    if (counted)
+      for (int k = i + 1; k < n; ++k) c += (hrow[(p - k) % window] == t);
     float* q = logits + (size_t)b * V + t;
-    const float v = *q;
-    *q = v > 0.f ? v / pen : v * pen;
+    *q = penalised(*q, pen, pres, freq, c);
   }
 }
 
@@ -177,8 +197,11 @@ __device__ __forceinline__ int argmax_pick(const unsigned long long* __restrict_
 // THE sampler: the sampled pick of one row by its whole block (a: ncand_pow2 keys of dynamic LDS) -- merge the row's
 // candidates, softmax(T), top-k / top-p, inverse-CDF pick at draw counter `ctr` of the seed word `sv`.  The token is
 // returned on the first wave (-1 on the others).  sample_commit_kernel and spec_sample_pick_kernel both call it.
+// min_p: next to the nucleus rule, candidate i > 0 stays only if e_i >= min_p; e_0 is exactly 1, so that is p_i >= min_p
+// * p_max on the temperature-scaled probabilities, with no division.  min_p = 0 keeps every lane's `keep` as it is.
 __device__ int sample_pick(unsigned long long* a, const unsigned long long* __restrict__ cand_row, int ncand_pow2,
-                           int ncand, float T, int k, float tp, unsigned long long sv, unsigned long long ctr) {
+                           int ncand, float T, int k, float tp, float min_p, unsigned long long sv,
+                           unsigned long long ctr) {
   for (int i = threadIdx.x; i < ncand_pow2; i += blockDim.x) a[i] = i < ncand ? cand_row[i] : 0ull;
   __syncthreads();
   bitonic_desc(a, ncand_pow2);
@@ -198,8 +221,8 @@ __device__ int sample_pick(unsigned long long* a, const unsigned long long* __re
     const float x = __shfl_up(cum, o, 64);
     if (i >= o) cum += x;
   }
-  // keep token i if the mass before it is < top_p (always keeps the first)
-  const bool keep = (i < k) && (i == 0 || (cum - p) < tp) && e > 0.f;
+  // keep token i if the mass before it is < top_p and it reaches min_p of the best one (always keeps the first)
+  const bool keep = (i < k) && (i == 0 || ((cum - p) < tp && e >= min_p)) && e > 0.f;
   const float pk = keep ? p : 0.f;
   const float ktot = wave_sum(pk);
   const float pn = pk / ktot;
@@ -232,7 +255,7 @@ __global__ __launch_bounds__(1024) void sample_commit_kernel(const unsigned long
                                                              int nch_amax, const float* __restrict__ temperature,
                                                              const int* __restrict__ top_k, const float* __restrict__ top_p,
                                                              const unsigned long long* __restrict__ seeds,
-                                                             DecodeState st) {
+                                                             const float* __restrict__ min_p, DecodeState st) {
   extern __shared__ unsigned long long a[];
   const int b = blockIdx.x;
   const float T = temperature[b];
@@ -245,8 +268,8 @@ __global__ __launch_bounds__(1024) void sample_commit_kernel(const unsigned long
   }
   // the draw counter, read by every thread before the pick's first barrier: thread 0 commits (and advances it) after
   const int g = st.gen_len[b];
-  const int tok = sample_pick(a, cand + (size_t)b * ncand, ncand_pow2, ncand, T, top_k[b], top_p[b], seeds[b],
-                              (unsigned long long)g);
+  const int tok = sample_pick(a, cand + (size_t)b * ncand, ncand_pow2, ncand, T, top_k[b], top_p[b],
+                              min_p ? min_p[b] : 0.f, seeds[b], (unsigned long long)g);
   if (threadIdx.x == 0) commit_token(st, b, tok);
 }
 
@@ -328,7 +351,7 @@ extern "C" int lsa_spec_commit(const float* logits, int S, int T, int V, unsigne
 // penalty (grid T x S) -> argmax / top-k partials (B = S T) -> pick (grid T x S, picks[s T + i]) -> in-order commit
 // (one wave per sequence).  No workgroup reads a word another workgroup of its launch writes.
 
-// Repetition penalty of verify row i, in place, with repeat_penalty_kernel's rule over the tokens at context positions
+// Penalties of verify row i, in place, with repeat_penalty_kernel's rule (counts included) over the tokens at positions
 // (p + i - m, p + i], m = min(last_n, window, p + i + 1): the token at position p + j, 1 <= j <= i, is draft[j - 1];
 // the token at a position <= p is hist[pos % window].  (A ring slot whose position is > p still holds the token
 // `window` positions older; m <= window, so no such slot is ever read for it.)  A draft < 0 or >= V penalises nothing.
@@ -337,10 +360,15 @@ __global__ __launch_bounds__(64) void spec_repeat_penalty_kernel(float* __restri
                                                                  const float* __restrict__ penalty,
                                                                  const int* __restrict__ last_n,
                                                                  const int* __restrict__ positions,
-                                                                 const int* __restrict__ draft) {
+                                                                 const int* __restrict__ draft,
+                                                                 const float* __restrict__ presence,
+                                                                 const float* __restrict__ frequency) {
   const int row = blockIdx.x, s = blockIdx.y, T = gridDim.x;
-  const float pen = penalty[s];
-  if (pen == 1.0f) return;
+  const float pen = penalty ? penalty[s] : 1.0f;
+  const float pres = presence ? presence[s] : 0.f;
+  const float freq = frequency ? frequency[s] : 0.f;
+  if (pen == 1.0f && pres == 0.f && freq == 0.f) return;
+  const bool counted = freq != 0.f;
   hist += (size_t)s * window;
   draft += (size_t)s * (T - 1);
   const int p = positions[s];
@@ -350,12 +378,14 @@ __global__ __launch_bounds__(64) void spec_repeat_penalty_kernel(float* __restri
   for (int i = threadIdx.x; i < n; i += 64) {
     const int t = tok_at(P - i);
     if (t < 0 || t >= V) continue;
-    bool first = true;  // the most recent occurrence applies the penalty, once per distinct token
+    bool first = true;  // the most recent occurrence applies the penalties, once per distinct token
     for (int k = 0; k < i; ++k) first &= (tok_at(P - k) != t);
     if (!first) continue;
+    int c = 1;  // its occurrences in the row's window, the drafts before the row included
+    if (counted)
+      for (int k = i + 1; k < n; ++k) c += (tok_at(P - k) == t);
     float* q = logits + ((size_t)s * T + row) * V + t;
-    const float v = *q;
-    *q = v > 0.f ? v / pen : v * pen;
+    *q = penalised(*q, pen, pres, freq, c);
   }
 }
 
@@ -368,6 +398,7 @@ __global__ __launch_bounds__(1024) void spec_sample_pick_kernel(const unsigned l
                                                                 const int* __restrict__ top_k,
                                                                 const float* __restrict__ top_p,
                                                                 const unsigned long long* __restrict__ seeds,
+                                                                const float* __restrict__ min_p,
                                                                 const int* __restrict__ gen_len, int* __restrict__ picks) {
   extern __shared__ unsigned long long a[];
   const int s = blockIdx.y;
@@ -380,8 +411,8 @@ __global__ __launch_bounds__(1024) void spec_sample_pick_kernel(const unsigned l
     }
     return;
   }
-  const int tok = sample_pick(a, cand + (size_t)row * ncand, ncand_pow2, ncand, T, top_k[s], top_p[s], seeds[s],
-                              (unsigned long long)(gen_len[s] + blockIdx.x));
+  const int tok = sample_pick(a, cand + (size_t)row * ncand, ncand_pow2, ncand, T, top_k[s], top_p[s],
+                              min_p ? min_p[s] : 0.f, seeds[s], (unsigned long long)(gen_len[s] + blockIdx.x));
   if (threadIdx.x == 0) picks[row] = tok;
 }
 
@@ -424,7 +455,8 @@ extern "C" int lsa_spec_sample_commit(float* logits, int S, int T, int V, const 
                                       const int* top_k, const float* top_p, const unsigned long long* seeds,
                                       int* out_tokens, int max_new, int* gen_len, int* input_ids, int* positions,
                                       int* finished, const int* eos, int neos, const int* limit, const int* eos_on,
-                                      unsigned long long* part, unsigned long long* cand, int* picks, hipStream_t s) {
+                                      unsigned long long* part, unsigned long long* cand, int* picks,
+                                      const float* presence, const float* frequency, const float* min_p, hipStream_t s) {
   // sizes refused before anything is launched or written: 2 <= T <= 8 verify rows per sequence, S T <= 32 rows (the
   // verify buffers), V <= 262144 (lsa_sample_commit)
   if (T < 2 || T > 8 || V < 1) return -1;
@@ -434,15 +466,15 @@ extern "C" int lsa_spec_sample_commit(float* logits, int S, int T, int V, const 
   int p2 = 64;
   while (p2 < ncand) p2 <<= 1;
   if (p2 > 8192) return -1;
-  if (hist && window > 0 && penalty)
+  if (hist && window > 0 && (penalty || presence || frequency))
     hipLaunchKernelGGL(spec_repeat_penalty_kernel, dim3(T, S), dim3(64), 0, s, logits, V, hist, window, penalty,
-                       last_n, positions, draft);
+                       last_n, positions, draft, presence, frequency);
   const int chunk = 4096;
   const int nch = (V + chunk - 1) / chunk;
   hipLaunchKernelGGL(argmax_partial_kernel, dim3(nch, S * T), dim3(256), 0, s, logits, V, chunk, part, nch);
   hipLaunchKernelGGL(topk_partial_kernel, dim3(nch2, S * T), dim3(256), 0, s, logits, V, cand, nch2);
   hipLaunchKernelGGL(spec_sample_pick_kernel, dim3(T, S), dim3(1024), p2 * sizeof(unsigned long long), s, cand, p2,
-                     ncand, part, nch, temperature, top_k, top_p, seeds, gen_len, picks);
+                     ncand, part, nch, temperature, top_k, top_p, seeds, min_p, gen_len, picks);
   DecodeState st{out_tokens, max_new, gen_len, input_ids, positions, finished, eos, neos, limit, eos_on,
                  window > 0 ? hist : nullptr, window};
   hipLaunchKernelGGL(spec_sample_commit_kernel, dim3(S), dim3(64), 0, s, picks, T - 1, draft, stats, st);
@@ -456,7 +488,7 @@ extern "C" int lsa_sample_commit(float* logits, int B, int V, unsigned long long
                                  const int* top_k, const float* top_p, const unsigned long long* seeds,
                                  int* out_tokens, int max_new, int* gen_len, int* input_ids, int* positions,
                                  int* finished, const int* eos, int neos, const int* limit, const int* eos_on,
-                                 hipStream_t s) {
+                                 const float* presence, const float* frequency, const float* min_p, hipStream_t s) {
   const int nch2 = (V + LSA_CHUNK - 1) / LSA_CHUNK;
   const int ncand = nch2 * LSA_TOPK;
   int p2 = 64;
@@ -464,9 +496,9 @@ extern "C" int lsa_sample_commit(float* logits, int B, int V, unsigned long long
   // V > 262144 unsupported (8192 candidates = 64 KiB of dynamic LDS); refused before anything is launched, so
   // neither the logits (penalty) nor the workspace is touched
   if (p2 > 8192) return -1;
-  if (hist && window > 0 && penalty)
+  if (hist && window > 0 && (penalty || presence || frequency))
     hipLaunchKernelGGL(repeat_penalty_kernel, dim3(B), dim3(64), 0, s, logits, V, hist, window, penalty, last_n,
-                       positions);
+                       positions, presence, frequency);
   const int chunk = 4096;
   const int nch = (V + chunk - 1) / chunk;
   hipLaunchKernelGGL(argmax_partial_kernel, dim3(nch, B), dim3(256), 0, s, logits, V, chunk, part, nch);
@@ -474,6 +506,6 @@ extern "C" int lsa_sample_commit(float* logits, int B, int V, unsigned long long
   DecodeState st{out_tokens, max_new, gen_len, input_ids, positions, finished, eos, neos, limit, eos_on,
                  window > 0 ? hist : nullptr, window};
   hipLaunchKernelGGL(sample_commit_kernel, dim3(B), dim3(1024), p2 * sizeof(unsigned long long), s, cand, p2, ncand,
-                     part, nch, temperature, top_k, top_p, seeds, st);
+                     part, nch, temperature, top_k, top_p, seeds, min_p, st);
   return (int)hipGetLastError();
 }

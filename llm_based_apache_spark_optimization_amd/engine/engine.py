@@ -18,6 +18,7 @@ from __future__ import annotations
 
 import dataclasses
 import itertools
+import math
 import queue
 import threading
 import time
@@ -38,6 +39,11 @@ from .runner import BLOCK, ModelRunner
 UNLIMITED = 1 << 30  # max_tokens of a request without num_predict: EOS / context window end it
 
 
+class SamplingOptionError(ValueError):
+    """A request's sampler option cannot be served (a non-finite penalty or min_p, min_p outside [0, 1]).  The HTTP
+    layer answers it with 400, as it answers a ``GuidedRequestError``."""
+
+
 @dataclasses.dataclass
 class SamplingParams:
     """Ollama-compatible options (temperature 0 = greedy, as the benchmark configs require)."""
@@ -53,7 +59,14 @@ class SamplingParams:
     # unless a request sets it (Ollama's own default is 1.1; the benchmark configs are plain greedy)
     repeat_penalty: float = 1.0
     repeat_last_n: int = 64
-    num_ctx: Optional[int] = None     # Ollama context window (prompt + generated tokens); None = model's
+    # llama.cpp's presence / frequency penalties over the same window (after the repetition penalty, a token that
+    # occurs c times there loses c * frequency_penalty + presence_penalty; negative values reward repeats) and min_p
+    # (a candidate stays only with probability >= min_p times the best one's, on the temperature-scaled probabilities,
+    # next to top_p -- Ollama's order; inert on a greedy request).  0.0 = off
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
+    min_p: float = 0.0
+    num_ctx: Optional[int] = None    # Ollama context window (prompt + generated tokens); None = model's
     num_keep: int = 4
     # prompt-lookup speculative decoding, where the engine runs it (LLMEngine(spec_tokens > 0), batch 1: a greedy
     # request, and -- on an engine built with spec_sampled (LSA_SPEC_SAMPLED=1) -- one with temperature > 0 and / or a
@@ -72,8 +85,9 @@ class SamplingParams:
 
     @property
     def needs_sampler(self) -> bool:
-        """Rows that need the sampling path (draw and/or penalty) rather than the argmax-only graph."""
-        return self.temperature > 0 or self.repeat_penalty != 1.0
+        """Rows that need the sampling path (draw and/or a penalty) rather than the argmax-only graph."""
+        return (self.temperature > 0 or self.repeat_penalty != 1.0 or self.presence_penalty != 0.0
+                or self.frequency_penalty != 0.0)
 
     @staticmethod
     def from_ollama_options(opts: Optional[dict], default_max: int = UNLIMITED) -> "SamplingParams":
@@ -90,6 +104,9 @@ class SamplingParams:
                               seed=opts.get("seed"), stop=tuple(stop), ignore_eos=bool(opts.get("ignore_eos", False)),
                               repeat_penalty=float(opts.get("repeat_penalty", 1.0)),
                               repeat_last_n=int(opts.get("repeat_last_n", 64)),
+                              presence_penalty=float(opts.get("presence_penalty", 0.0)),
+                              frequency_penalty=float(opts.get("frequency_penalty", 0.0)),
+                              min_p=float(opts.get("min_p", 0.0)),
                               num_ctx=int(opts["num_ctx"]) if opts.get("num_ctx") else None,
                               num_keep=int(opts.get("num_keep", 4)), speculate=bool(opts.get("speculate", True)),
                               cache_prompt=bool(opts.get("cache_prompt", True)),
@@ -248,6 +265,11 @@ class LLMEngine:
         if room < 1:
             raise ValueError("prompt longer than the model context")
         p = dataclasses.replace(params, max_tokens=max(1, min(params.max_tokens, room, self.runner.max_new_cap)))
+        for name in ("presence_penalty", "frequency_penalty", "min_p"):  # refused here, like a bad pattern below
+            if not math.isfinite(float(getattr(p, name))):
+                raise SamplingOptionError(f"{name} must be a finite number")
+        if not 0.0 <= float(p.min_p) <= 1.0:
+            raise SamplingOptionError("min_p must lie in [0, 1]")
         dfa = None
         if p.regex is not None:  # compiled here, so that a bad pattern fails the request, not the engine loop
             if not self.guided:
@@ -313,7 +335,8 @@ class LLMEngine:
                 entries.append(dict(slot=slot, blocks=self.sched.block_table(rid), limit=sp.max_tokens,
                                     temperature=sp.temperature, top_k=sp.top_k, top_p=sp.top_p, seed=seed,
                                     eos_on=not sp.ignore_eos, repeat_penalty=sp.repeat_penalty,
-                                    repeat_last_n=sp.repeat_last_n, prompt_ids=req.ctx_ids,
+                                    repeat_last_n=sp.repeat_last_n, presence_penalty=sp.presence_penalty,
+                                    frequency_penalty=sp.frequency_penalty, min_p=sp.min_p, prompt_ids=req.ctx_ids,
                                     defer_table=self.prefill_chunk is not None))
                 if req.dfa is not None:  # a re-admitted request resumes in the state its generated tokens reached
                     entries[-1].update(dfa=req.dfa, dfa_state=req.dfa.walk(req.dfa.start, self._bytes_of(req.resumed)))

@@ -181,6 +181,11 @@ class ModelRunner:
         self.penalty = torch.ones(S, dtype=torch.float32, device=dev)
         self.last_n = torch.full((S,), REPEAT_WINDOW, **i32)
         self.hist = torch.full((S, REPEAT_WINDOW), -1, **i32)
+        # presence / frequency penalties over the same ring and the sampler's min_p (0 = off, the default: every
+        # captured sampling graph reads them, and a zero changes no logit and no draw)
+        self.presence = torch.zeros(S, dtype=torch.float32, device=dev)
+        self.frequency = torch.zeros(S, dtype=torch.float32, device=dev)
+        self.min_p = torch.zeros(S, dtype=torch.float32, device=dev)
         self.eos_list = list(spec.eos_ids) or [-1]
         self.eos = torch.tensor(self.eos_list, **i32)
 
@@ -639,7 +644,8 @@ class ModelRunner:
             ops.sample_commit(logits, self.hist[:B], self.penalty[:B], self.temperature[:B], self.top_k[:B],
                               self.top_p[:B], self.seeds[:B], *st, self.eos, self.limit[:B], self.eos_on[:B],
                               workspace=(self.amax_part, self.cand) if self.on_gpu else None,
-                              last_n=self.last_n[:B])
+                              last_n=self.last_n[:B], presence=self.presence[:B], frequency=self.frequency[:B],
+                              min_p=self.min_p[:B])
         else:
             ops.argmax_commit(logits, *st, self.eos, self.limit[:B], self.eos_on[:B],
                               part=self.amax_part if self.on_gpu else None)
@@ -979,7 +985,8 @@ class ModelRunner:
                                    self.penalty[:S], self.temperature[:S], self.top_k[:S], self.top_p[:S],
                                    self.seeds[:S], *st, self.eos, self.limit[:S], self.eos_on[:S],
                                    workspace=(sb["amax_part"], sb["cand"], sb["picks"]) if self.on_gpu else None,
-                                   last_n=self.last_n[:S])
+                                   last_n=self.last_n[:S], presence=self.presence[:S], frequency=self.frequency[:S],
+                                   min_p=self.min_p[:S])
         else:
             ops.spec_commit(logits, draft, sb["stats"][0] if S == 1 else sb["stats"][:S], *st, self.eos, self.limit[:S],
                             self.eos_on[:S], part=sb["amax_part"] if self.on_gpu else None)
@@ -1150,13 +1157,15 @@ class ModelRunner:
     # ------------------------------------------------------------------------------------ slots
     def set_slot(self, slot: int, blocks: Sequence[int], limit: int, temperature: float = 0.0, top_k: int = 40,
                  top_p: float = 0.9, seed: int = 0, eos_on: bool = True, repeat_penalty: float = 1.0,
-                 repeat_last_n: int = REPEAT_WINDOW, prompt_ids: Sequence[int] = (), defer_table: bool = False) -> None:
+                 repeat_last_n: int = REPEAT_WINDOW, prompt_ids: Sequence[int] = (), defer_table: bool = False,
+                 presence_penalty: float = 0.0, frequency_penalty: float = 0.0, min_p: float = 0.0) -> None:
         """``defer_table``: the slot's block table stays out of the decode-visible table until its prompt's
         final prefill chunk commits (chunked-prefill interleave: decode runs in between must not append
         the idle row's k/v into the blocks the prompt is being written to)."""
         self.set_slots([dict(slot=slot, blocks=blocks, limit=limit, temperature=temperature, top_k=top_k, top_p=top_p,
                              seed=seed, eos_on=eos_on, repeat_penalty=repeat_penalty, repeat_last_n=repeat_last_n,
-                             prompt_ids=prompt_ids, defer_table=defer_table)])
+                             prompt_ids=prompt_ids, defer_table=defer_table, presence_penalty=presence_penalty,
+                             frequency_penalty=frequency_penalty, min_p=min_p)])
 
     def set_slots(self, entries: Sequence[dict]) -> None:
         """``set_slot`` for every admitted request at once (keyword dicts of set_slot's arguments): the per-slot
@@ -1171,9 +1180,12 @@ class ModelRunner:
         SB = self.spec_s() if (self.spec_tokens > 0 and self.spec_supported()) else 0
         sx = (1 + self.max_model_len) if any(int(e["slot"]) < SB for e in entries) else 0
         ints = torch.zeros(n, mb + 5 + sx, dtype=torch.int32)  # block-table row | limit top_k eos_on last_n visible
-        flts = torch.zeros(n, 3, dtype=torch.float32)     # temperature top_p penalty
+        flts = torch.zeros(n, 6, dtype=torch.float32)     # temperature top_p penalty presence frequency min_p
         seeds = torch.zeros(n, dtype=torch.int64)
         hist = None
+        # a request with any of the three penalties reads the ring from its first token on
+        ringed = [float(e.get("repeat_penalty", 1.0)) != 1.0 or float(e.get("presence_penalty", 0.0)) != 0.0 or
+                  float(e.get("frequency_penalty", 0.0)) != 0.0 for e in entries]
         for i, e in enumerate(entries):
             blocks = list(e["blocks"])
             ints[i, : len(blocks)] = torch.tensor(blocks, dtype=torch.int32)
@@ -1186,9 +1198,10 @@ class ModelRunner:
                 ints[i, mb + 5] = len(pids)
                 ints[i, mb + 6: mb + 6 + len(pids)] = torch.tensor(pids, dtype=torch.int32)
             flts[i] = torch.tensor([float(e.get("temperature", 0.0)), float(e.get("top_p", 0.9)),
-                                    float(e.get("repeat_penalty", 1.0))])
+                                    float(e.get("repeat_penalty", 1.0)), float(e.get("presence_penalty", 0.0)),
+                                    float(e.get("frequency_penalty", 0.0)), float(e.get("min_p", 0.0))])
             seeds[i] = int(e.get("seed", 0))
-            if float(e.get("repeat_penalty", 1.0)) != 1.0:  # seed the ring with the prompt's last tokens (p -> p % W)
+            if ringed[i]:  # seed the ring with the prompt's last tokens (p -> p % W)
                 if hist is None:
                     hist = torch.full((n, W), -1, dtype=torch.int32)
                 ids = list(e.get("prompt_ids", ()))
@@ -1221,6 +1234,9 @@ class ModelRunner:
         self.temperature.index_copy_(0, idx, fv[:, 0])
         self.top_p.index_copy_(0, idx, fv[:, 1])
         self.penalty.index_copy_(0, idx, fv[:, 2])
+        self.presence.index_copy_(0, idx, fv[:, 3])
+        self.frequency.index_copy_(0, idx, fv[:, 4])
+        self.min_p.index_copy_(0, idx, fv[:, 5])
         self.seeds.index_copy_(0, idx, sv)
         if self.guided:
             self._set_guided(entries, idx)
@@ -1228,8 +1244,7 @@ class ModelRunner:
             raise RuntimeError("a request carries a regex but the runner was built without guided decoding")
         if hist is not None:
             hv = hist.pin_memory() if self.on_gpu else hist
-            hsel = torch.tensor([i for i, e in enumerate(entries) if float(e.get("repeat_penalty", 1.0)) != 1.0],
-                                dtype=torch.long)
+            hsel = torch.tensor([i for i in range(n) if ringed[i]], dtype=torch.long)
             self.hist.index_copy_(0, idx[hsel.to(self.device)], hv[hsel].to(self.device, non_blocking=True))
 
     def extend_tables(self, entries: Sequence[tuple]) -> None:
@@ -1357,7 +1372,10 @@ class ModelRunner:
                               self.temperature.index_select(0, slot_t),
                               self.top_k.index_select(0, slot_t), self.top_p.index_select(0, slot_t),
                               self.seeds.index_select(0, slot_t), out_t, gl, iid, pp, fin, self.eos, lim, eon,
-                              last_n=self.last_n.index_select(0, slot_t))
+                              last_n=self.last_n.index_select(0, slot_t),
+                              presence=self.presence.index_select(0, slot_t),
+                              frequency=self.frequency.index_select(0, slot_t),
+                              min_p=self.min_p.index_select(0, slot_t))
             self.hist.index_copy_(0, slot_t, hist)
         else:
             ops.argmax_commit(logits, out_t, gl, iid, pp, fin, self.eos, lim, eon)

@@ -1527,25 +1527,33 @@ def argmax_commit(logits, out_tokens, gen_len, input_ids, positions, finished, e
 
 
 def sample_commit(logits, hist, penalty, temperature, top_k, top_p, seeds, out_tokens, gen_len, input_ids,
-                  positions, finished, eos, limit=None, eos_on=None, workspace=None, last_n=None):
-    """Temperature / top-k / top-p draw (+ optional repetition penalty) + decode-state update.
+                  positions, finished, eos, limit=None, eos_on=None, workspace=None, last_n=None, presence=None,
+                  frequency=None, min_p=None):
+    """Temperature / top-k / top-p / min-p draw (+ optional penalties) + decode-state update.
 
     ``hist`` [B, W] int32 is the ring of each row's last W context tokens (token at position p in column
     p % W, -1 = empty); with it, rows whose ``penalty`` != 1 have the logits of the distinct tokens among
     their last ``last_n`` (<= W, default W) positions penalised (Ollama ``repeat_penalty`` /
-    ``repeat_last_n``), and the committed token is written into the ring.  ``logits`` is modified."""
+    ``repeat_last_n``), and the committed token is written into the ring.  ``logits`` is modified.
+
+    ``presence`` / ``frequency`` / ``min_p``: optional f32 [B], None = off.  A token that occurs c times among those
+    positions also loses c * frequency + presence (llama.cpp's ``penalties`` sampler, after the repetition penalty);
+    a sampled row keeps, next to its best candidate, only the candidates of probability >= min_p times the best
+    one's, on the temperature-scaled probabilities the nucleus rule reads.  Zeros are bit for bit the call without
+    them (``ops.reference.repeat_penalty`` / ``sample_pick`` state the exact rules)."""
     B, V = logits.shape
     limit, eos_on = _row_defaults(B, out_tokens, limit, eos_on)
     if not _gpu(logits):
         return ref.sample_commit(logits, hist, penalty, temperature, top_k, top_p, seeds, out_tokens, gen_len,
-                                 input_ids, positions, finished, eos, limit, eos_on, last_n=last_n)
+                                 input_ids, positions, finished, eos, limit, eos_on, last_n=last_n, presence=presence,
+                                 frequency=frequency, min_p=min_p)
     if workspace is None:
         part = torch.empty(B * ((V + 4095) // 4096), device=logits.device, dtype=torch.int64)
         cand = torch.empty(B * ((V + 2047) // 2048) * 64, device=logits.device, dtype=torch.int64)
     else:
         part, cand = workspace
     ext().sample_commit(logits, part, cand, hist, penalty, last_n, temperature, top_k, top_p, seeds, out_tokens,
-                        gen_len, input_ids, positions, finished, eos, limit, eos_on)
+                        gen_len, input_ids, positions, finished, eos, limit, eos_on, presence, frequency, min_p)
 
 
 # ----------------------------------------------------------------------------------- speculative decoding
@@ -1644,7 +1652,8 @@ def spec_commit(logits, draft, stats, out_tokens, gen_len, input_ids, positions,
 
 
 def spec_sample_commit(logits, draft, stats, hist, penalty, temperature, top_k, top_p, seeds, out_tokens, gen_len,
-                       input_ids, positions, finished, eos, limit=None, eos_on=None, workspace=None, last_n=None):
+                       input_ids, positions, finished, eos, limit=None, eos_on=None, workspace=None, last_n=None,
+                       presence=None, frequency=None, min_p=None):
     """Sampled verification of the T = k + 1 verify rows ``logits`` (2 <= T <= 8, V <= 262144) of the sequence in
     state row 0 (kernels/sampling.hip lsa_spec_sample_commit).  Row i is penalised over the ring ``hist`` [1, W] as it
     would stand had drafts 0 .. i-1 been committed (``logits`` is modified) and makes the draw of the plain
@@ -1657,7 +1666,10 @@ def spec_sample_commit(logits, draft, stats, hist, penalty, temperature, top_k, 
     stats [S, 3]: ``logits`` [S * T, V] and ``draft`` [S, T - 1] are the rows of S sequences (S * T <= 32, as
     ``spec_commit``); sequence s reads ring row s and entry s of every parameter, commits into state row s and counts
     in stats[s]; the workspace is sized for S * T rows.  A sequence with temperature 0 and penalty 1 commits what
-    ``spec_commit`` commits for its rows."""
+    ``spec_commit`` commits for its rows.
+
+    ``presence`` / ``frequency`` / ``min_p``: the optional per-sequence f32 options of ``sample_commit`` (>= S entries,
+    None = off); row i counts a token's occurrences in the window it is penalised over, drafts 0 .. i-1 included."""
     R, V = logits.shape  # (all S * T rows)
     S = stats.shape[0] if stats.dim() == 2 else 1
     if S > 1 and (stats.shape[1] != 3 or R % S or R > 32):
@@ -1669,20 +1681,21 @@ def spec_sample_commit(logits, draft, stats, hist, penalty, temperature, top_k, 
             raise RuntimeError("spec_sample_commit: 2 <= T <= 8 verify rows, V <= 262144")
         if S > 1:  # as the binding: one ring row, one parameter and one state row per sequence
             per_seq = [temperature, top_k, top_p, seeds, gen_len, input_ids, positions, finished] + \
-                [t for t in (penalty, last_n) if t is not None]
+                [t for t in (penalty, last_n, presence, frequency, min_p) if t is not None]
             if any(t.numel() < S for t in per_seq) or draft.numel() < S * (T - 1) or out_tokens.shape[0] < S or \
                     (hist is not None and hist.shape[0] < S):
                 raise RuntimeError("spec_sample_commit: one row of every per-sequence operand per sequence")
         return ref.spec_sample_commit(logits, draft, stats, hist, penalty, temperature, top_k, top_p, seeds,
                                       out_tokens, gen_len, input_ids, positions, finished, eos, limit, eos_on,
-                                      last_n=last_n)
+                                      last_n=last_n, presence=presence, frequency=frequency, min_p=min_p)
     if workspace is None:
         workspace = (torch.empty(R * ((V + 4095) // 4096), device=logits.device, dtype=torch.int64),
                      torch.empty(R * ((V + 2047) // 2048) * 64, device=logits.device, dtype=torch.int64),
                      torch.empty(R, device=logits.device, dtype=torch.int32))
     part, cand, picks = workspace
     ext().spec_sample_commit(logits, draft, stats, hist, penalty, last_n, temperature, top_k, top_p, seeds, out_tokens,
-                             gen_len, input_ids, positions, finished, eos, limit, eos_on, part, cand, picks)
+                             gen_len, input_ids, positions, finished, eos, limit, eos_on, part, cand, picks, presence,
+                             frequency, min_p)
 
 
 # ----------------------------------------------------------------------------------- regex-constrained decoding

@@ -8,6 +8,7 @@ production: ``ops`` refuses to fall back when the extension is missing on a GPU 
 from __future__ import annotations
 
 import math
+import struct
 
 import torch
 
@@ -442,28 +443,64 @@ def spec_commit(logits, draft, stats, out_tokens, gen_len, input_ids, positions,
         st[2] += max(committed - 1, 0)
 
 
-def sample_probs(logits_row: torch.Tensor, temperature: float, top_k: int, top_p: float, topk_cap: int = 64):
-    """Distribution the sampler draws from (top-k capped at 64, nucleus within it)."""
+def sample_probs(logits_row: torch.Tensor, temperature: float, top_k: int, top_p: float, topk_cap: int = 64, *,
+                 min_p: float = 0.0):
+    """Distribution the sampler draws from (top-k capped at 64, nucleus within it; ``min_p`` > 0: and only the
+    candidates with ``exp((l_i - l_0) / T) >= min_p``, i.e. p_i >= min_p * p_max, next to the best one)."""
     k = top_k if 0 < top_k <= topk_cap else topk_cap
     vals, idx = logits_row.float().topk(min(topk_cap, logits_row.numel()))
     vals, idx = vals[:k], idx[:k]
     p = torch.softmax(vals / temperature, -1)
     before = torch.cumsum(p, 0) - p
     keep = before < top_p
+    if min_p > 0:
+        keep &= torch.exp((vals - vals[0]) / temperature) >= min_p
     keep[0] = True
     p = torch.where(keep, p, torch.zeros_like(p))
     return idx, p / p.sum()
 
 
-def repeat_penalty(row, hist_row, pen, pos, last_n):
-    """llama.cpp/Ollama repetition penalty on one row of logits over the distinct tokens at context
-    positions (pos - last_n, pos] of the position-indexed ring ``hist_row``."""
-    W = hist_row.numel()
-    n = min(W if last_n is None else int(last_n), W, pos + 1)
-    for t in {int(hist_row[(pos - i) % W]) for i in range(n)}:
+def fma_f32(a: float, b: float, c: float) -> float:
+    """The correctly rounded f32 of a * b + c for f32 operands whose product is exact in f64 (here: a count <= 64
+    times an f32), as the device's one fused multiply-add gives it.  The f64 sum is made round-to-odd (the exact error
+    of the addition picks the odd neighbour when the sum is inexact), so the second rounding, to f32, is the correct
+    one of the exact value."""
+    x = float(a) * float(b)
+    y = float(c)
+    s = x + y
+    if not math.isfinite(s):
+        return s
+    yy = s - x
+    err = (x - (s - yy)) + (y - yy)
+    if err != 0.0 and not (struct.unpack("<Q", struct.pack("<d", s))[0] & 1):
+        s = math.nextafter(s, math.inf if err > 0 else -math.inf)
+    return float(torch.tensor(s, dtype=torch.float64).to(torch.float32))
+
+
+def _penalise(row, counts: dict, pen: float, presence: float, frequency: float):
+    """The two-step rule of the penalty kernels on ``row`` (f32, in place) for the in-range tokens of ``counts``
+    (token -> occurrences c in the window): l = l / pen if l > 0 else l * pen, then l -= fma(c, frequency, presence)."""
+    for t, c in counts.items():
         if 0 <= t < row.numel():
             row[t] = row[t] / pen if row[t] > 0 else row[t] * pen
+            row[t] = row[t] - fma_f32(float(c), frequency, presence)
     return row
+
+
+def repeat_penalty(row, hist_row, pen, pos, last_n, presence: float = 0.0, frequency: float = 0.0):
+    """llama.cpp/Ollama penalties on one row of logits over the distinct tokens at context positions
+    (pos - last_n, pos] of the position-indexed ring ``hist_row``: the repetition penalty ``pen`` (l / pen if l > 0
+    else l * pen), then l -= c * frequency + presence for a token that occurs c times in that window (the subtrahend
+    is one fused multiply-add, rounded once to f32).  pen == 1 with presence == frequency == 0 changes nothing."""
+    if float(pen) == 1.0 and float(presence) == 0.0 and float(frequency) == 0.0:
+        return row
+    W = hist_row.numel()
+    n = min(W if last_n is None else int(last_n), W, pos + 1)
+    counts: dict = {}
+    for i in range(n):
+        t = int(hist_row[(pos - i) % W])
+        counts[t] = counts.get(t, 0) + 1
+    return _penalise(row, counts, pen, float(presence), float(frequency))
 
 
 _M64 = (1 << 64) - 1
@@ -532,24 +569,27 @@ def sample_candidates(row_f32: torch.Tensor, top_k: int):
     return vals[:k], idx[:k]
 
 
-def sample_pick(row: torch.Tensor, T: float, top_k: int, top_p: float, u: float) -> int:
+def sample_pick(row: torch.Tensor, T: float, top_k: int, top_p: float, u: float, *, min_p: float = 0.0) -> int:
     """The token sample_commit_kernel commits for uniform ``u``, computed in float64:
 
     * ``e_i = exp((l_i - l_0) / T)`` over the candidates of ``sample_candidates``, ``p = e / sum(e)``;
-    * candidate i is kept iff ``(i == 0 or mass before i < top_p) and e_i > 0`` -- the best token is always kept,
-      ``top_p <= 0`` keeps nothing else, a -inf logit is never kept;
+    * candidate i is kept iff ``(i == 0 or (mass before i < top_p and e_i >= min_p)) and e_i > 0`` -- the best token
+      is always kept, ``top_p <= 0`` keeps nothing else, a -inf logit is never kept; e_0 is exactly 1, so the ``min_p``
+      rule is p_i >= min_p * p_max on the temperature-scaled probabilities, and ``min_p`` = 0 keeps what it finds;
     * the kept mass is renormalised and the pick is the first kept i whose inclusive cumulative mass exceeds u
       (``u < cum_i``); when no cumulative value exceeds u (rounding left the last one below u) it is the LAST
       kept candidate -- a deliberate device convention, never a token outside the nucleus."""
-    return _pick(*sample_candidates(row, top_k), T, top_p, u)
+    return _pick(*sample_candidates(row, top_k), T, top_p, u, min_p=min_p)
 
 
-def _pick(vals, idx, T, top_p, u) -> int:
+def _pick(vals, idx, T, top_p, u, *, min_p: float = 0.0) -> int:
     l = vals.double()
     e = torch.exp((l - l[0]) / float(T))
     p = e / e.sum()
     before = torch.cumsum(p, 0) - p
     keep = (before < float(top_p)) & (e > 0)
+    if min_p > 0:
+        keep &= e >= float(min_p)
     keep[0] = bool(e[0] > 0)
     pk = torch.where(keep, p, torch.zeros_like(p))
     cum = torch.cumsum(pk / pk.sum(), 0)
@@ -560,31 +600,44 @@ def _pick(vals, idx, T, top_p, u) -> int:
     return int(idx[int(kept[-1])]) if kept.numel() else int(idx[0])
 
 
-def sample_pick_set(row: torch.Tensor, T: float, top_k: int, top_p: float, u: float, m: float = SAMPLE_MARGIN) -> set:
+def sample_pick_set(row: torch.Tensor, T: float, top_k: int, top_p: float, u: float, m: float = SAMPLE_MARGIN, *,
+                    min_p: float = 0.0) -> set:
     """Tokens the device may commit: ``sample_pick`` over u in {u - m, u, u + m} x top_p in {top_p - m, top_p,
-    top_p + m}.  The device evaluates the same quantities in f32 (``__expf``, shuffle prefix sums); over <= 64
+    top_p + m} and, with ``min_p`` > 0, x min_p in {min_p (1 - m), min_p, min_p (1 + m)}: the device compares its
+    f32 ``__expf`` value e_i with min_p, and the relative error of that value (about (|x| + 4) * 2^-23, below 1e-5 for
+    every e_i that is not far under any min_p worth setting) is a tenth of the relative margin m.  The device evaluates the same quantities in f32 (``__expf``, shuffle prefix sums); over <= 64
     candidates the absolute error of any cumulative boundary stays below about 1e-5 (per-term relative error about
     (|x| + 4) * 2^-23 weighted by p, six levels of prefix rounding, two normalisations), so m = 1e-4 is more than
     ten times the bound.  A draw is DECIDED when the set has one element: the device must then commit it."""
     vals, idx = sample_candidates(row, top_k)
-    return {_pick(vals, idx, T, tp, uu) for uu in (u - m, u, u + m) for tp in (top_p - m, top_p, top_p + m)}
+    mps = (min_p * (1 - m), min_p, min_p * (1 + m)) if min_p > 0 else (0.0,)
+    return {_pick(vals, idx, T, tp, uu, min_p=mp) for uu in (u - m, u, u + m) for tp in (top_p - m, top_p, top_p + m)
+            for mp in mps}
+
+
+def _row_opt(t, b: int, default: float = 0.0) -> float:
+    """Entry b of an optional per-row f32 operand (None = ``default``)."""
+    return default if t is None else float(t[b])
 
 
 def sample_commit(logits, hist, penalty, temperature, top_k, top_p, seeds, out_tokens, gen_len, input_ids,
                   positions, finished, eos, limit=None, eos_on=None, generator: torch.Generator | None = None,
-                  last_n=None):
+                  last_n=None, presence=None, frequency=None, min_p=None):
+    """``presence`` / ``frequency`` / ``min_p``: per-row f32 options, None = off (0); with all three off the call is
+    what it is without them."""
     B = logits.shape[0]
     toks = torch.empty(B, dtype=torch.long)
     for b in range(B):
         row = logits[b].float().clone()
-        if hist is not None and penalty is not None and float(penalty[b]) != 1.0:
-            row = repeat_penalty(row, hist[b].cpu(), float(penalty[b]), int(positions[b]),
-                                 None if last_n is None else int(last_n[b]))
+        pen, pres, freq = _row_opt(penalty, b, 1.0), _row_opt(presence, b), _row_opt(frequency, b)
+        if hist is not None and (pen != 1.0 or pres != 0.0 or freq != 0.0):
+            row = repeat_penalty(row, hist[b].cpu(), pen, int(positions[b]),
+                                 None if last_n is None else int(last_n[b]), pres, freq)
         T = float(temperature[b])
         if T <= 0:
             toks[b] = int(row.argmax())
             continue
-        idx, p = sample_probs(row, T, int(top_k[b]), float(top_p[b]))
+        idx, p = sample_probs(row, T, int(top_k[b]), float(top_p[b]), min_p=_row_opt(min_p, b))
         # draw g of a row comes from (seed key, g + offset) alone (one generator per row: a generator shared across
         # rows made a row's draws depend on the rows sampled before it in the batch)
         g = generator if generator is not None else torch.Generator().manual_seed(draw_seed(int(seeds[b]), int(gen_len[b])))
@@ -593,37 +646,38 @@ def sample_commit(logits, hist, penalty, temperature, top_k, top_p, seeds, out_t
 
 
 # --------------------------------------------------------------- speculative decoding of a sampled request
-def spec_penalised_row(row, hist_row, draft, i, pen, pos, last_n):
-    """Verify row ``i`` of a sampled verify step with its repetition penalty (spec_repeat_penalty_kernel): ``row``
-    (modified and returned) is penalised with ``repeat_penalty``'s rule over the distinct tokens at context positions
+def spec_penalised_row(row, hist_row, draft, i, pen, pos, last_n, presence: float = 0.0, frequency: float = 0.0):
+    """Verify row ``i`` of a sampled verify step with its penalties (spec_repeat_penalty_kernel): ``row``
+    (modified and returned) is penalised with ``repeat_penalty``'s rule (repetition penalty, then the frequency /
+    presence subtrahend of the token's count in the window) over the distinct tokens at context positions
     (pos + i - m, pos + i], m = min(last_n, W, pos + i + 1), where ``pos`` is the row's position at the launch: the
     token at position pos + j, 1 <= j <= i, is ``draft[j - 1]``, the token at a position <= pos is
     ``hist_row[position % W]`` -- the ring the plain step at position pos + i would see had drafts 0 .. i-1 been
     committed.  (A ring slot whose position is > pos holds a token W positions older; m <= W, so it is never read for
-    it.)  A draft < 0 or >= V penalises nothing; pen == 1 changes nothing."""
-    if float(pen) == 1.0:
+    it.)  A draft < 0 or >= V penalises nothing and counts for nothing; pen == 1 with presence == frequency == 0
+    changes nothing."""
+    if float(pen) == 1.0 and float(presence) == 0.0 and float(frequency) == 0.0:
         return row
     W = hist_row.numel()
     P = pos + i
     m = min(W if last_n is None else int(last_n), W, P + 1)
-    toks = set()
+    counts: dict = {}
     for j in range(m):
         q = P - j
-        toks.add(int(draft[q - pos - 1]) if q > pos else int(hist_row[q % W]))
-    for t in toks:
-        if 0 <= t < row.numel():
-            row[t] = row[t] / pen if row[t] > 0 else row[t] * pen
-    return row
+        t = int(draft[q - pos - 1]) if q > pos else int(hist_row[q % W])
+        counts[t] = counts.get(t, 0) + 1
+    return _penalise(row, counts, pen, float(presence), float(frequency))
 
 
-def _spec_rows(logits, draft, hist, penalty, last_n, positions):
-    """The T verify rows (f32 clones) with the penalty of ``spec_penalised_row``."""
+def _spec_rows(logits, draft, hist, penalty, last_n, positions, presence=None, frequency=None):
+    """The T verify rows (f32 clones) with the penalties of ``spec_penalised_row``."""
     rows = []
+    pen, pres, freq = _row_opt(penalty, 0, 1.0), _row_opt(presence, 0), _row_opt(frequency, 0)
     for i in range(logits.shape[0]):
         row = logits[i].float().clone()
-        if hist is not None and penalty is not None and float(penalty[0]) != 1.0:
-            row = spec_penalised_row(row, hist[0].cpu(), draft.cpu(), i, float(penalty[0]), int(positions[0]),
-                                     None if last_n is None else int(last_n[0]))
+        if hist is not None and (pen != 1.0 or pres != 0.0 or freq != 0.0):
+            row = spec_penalised_row(row, hist[0].cpu(), draft.cpu(), i, pen, int(positions[0]),
+                                     None if last_n is None else int(last_n[0]), pres, freq)
         rows.append(row)
     return rows
 
@@ -638,7 +692,8 @@ def _seq_views(s, T, logits, draft, stats, per_seq):
 
 
 def spec_sample_commit(logits, draft, stats, hist, penalty, temperature, top_k, top_p, seeds, out_tokens, gen_len,
-                       input_ids, positions, finished, eos, limit=None, eos_on=None, last_n=None):
+                       input_ids, positions, finished, eos, limit=None, eos_on=None, last_n=None, presence=None,
+                       frequency=None, min_p=None):
     """The CPU engine's twin of lsa_spec_sample_commit.  stats [S, 3], S > 1: logits [S * T, V] are the rows of S
     sequences, and the call is a loop of the one-sequence call below over the row views of sequence s (rows s T .. s T
     + T - 1, draft[s (T - 1) ..], ring / parameter / state row s, stats[s]).  Otherwise logits [T, V]: the verify rows
@@ -648,20 +703,22 @@ def spec_sample_commit(logits, draft, stats, hist, penalty, temperature, top_k, 
     ``draw_seed(seed, n + i)``; temperature <= 0: the argmax), so a verify step is bit-equal to the plain sampled
     steps.  Commits picks[0 .. a] in order, ring included (a = leading drafts >= 0 equal to their row's pick),
     stopping after a finishing token; stats += (1, drafts >= 0, tokens committed beyond the first).  A finished row
-    changes no state."""
+    changes no state.  ``presence`` / ``frequency`` / ``min_p``: the per-sequence options of ``sample_commit``."""
     S = stats.shape[0] if stats.dim() == 2 else 1
     if S > 1:
         T = logits.shape[0] // S
         for s in range(S):
-            lg, dr, st, (h, pen, tmp, tk, tp, sd, ot, gl, ii, ps, fin, lim, eon, ln) = _seq_views(
+            lg, dr, st, (h, pen, tmp, tk, tp, sd, ot, gl, ii, ps, fin, lim, eon, ln, pr, fr, mp) = _seq_views(
                 s, T, logits, draft, stats, (hist, penalty, temperature, top_k, top_p, seeds, out_tokens, gen_len,
-                                             input_ids, positions, finished, limit, eos_on, last_n))
-            spec_sample_commit(lg, dr, st, h, pen, tmp, tk, tp, sd, ot, gl, ii, ps, fin, eos, lim, eon, last_n=ln)
+                                             input_ids, positions, finished, limit, eos_on, last_n, presence, frequency,
+                                             min_p))
+            spec_sample_commit(lg, dr, st, h, pen, tmp, tk, tp, sd, ot, gl, ii, ps, fin, eos, lim, eon, last_n=ln,
+                               presence=pr, frequency=fr, min_p=mp)
         return
     stats = stats.view(-1)
     T = logits.shape[0]
     n = int(gen_len[0])
-    rows = _spec_rows(logits, draft, hist, penalty, last_n, positions)
+    rows = _spec_rows(logits, draft, hist, penalty, last_n, positions, presence, frequency)
     Tmp = float(temperature[0])
     picks = []
     for i, row in enumerate(rows):
@@ -669,7 +726,7 @@ def spec_sample_commit(logits, draft, stats, hist, penalty, temperature, top_k, 
         if Tmp <= 0:
             picks.append(int(row.argmax()))
             continue
-        idx, p = sample_probs(row, Tmp, int(top_k[0]), float(top_p[0]))
+        idx, p = sample_probs(row, Tmp, int(top_k[0]), float(top_p[0]), min_p=_row_opt(min_p, 0))
         g = torch.Generator().manual_seed(draw_seed(int(seeds[0]), n + i))
         picks.append(int(idx[torch.multinomial(p.cpu(), 1, generator=g)]))
     if int(finished[0]):
@@ -689,7 +746,8 @@ def spec_sample_commit(logits, draft, stats, hist, penalty, temperature, top_k, 
 
 
 def spec_sample_pick_sets(logits, draft, hist, penalty, temperature, top_k, top_p, seeds, gen_len, positions,
-                          last_n=None, m: float = SAMPLE_MARGIN, S: int = 1) -> list:
+                          last_n=None, m: float = SAMPLE_MARGIN, S: int = 1, presence=None, frequency=None,
+                          min_p=None) -> list:
     """The exact device twin of the picks of lsa_spec_sample_commit: per verify row i the set of tokens the device
     may write to picks[i] -- ``sample_pick_set`` of the penalised row at ``device_uniform(seed, gen_len[0] + i)``, or
     the plain argmax for temperature <= 0.  A one-element set is a decided draw.  ``S`` > 1: logits [S * T, V], draft
@@ -698,17 +756,19 @@ def spec_sample_pick_sets(logits, draft, hist, penalty, temperature, top_k, top_
         T = logits.shape[0] // S
         out = []
         for s in range(S):
-            lg, dr, _, (h, pen, tmp, tk, tp, sd, gl, ps, ln) = _seq_views(
+            lg, dr, _, (h, pen, tmp, tk, tp, sd, gl, ps, ln, pr, fr, mp) = _seq_views(
                 s, T, logits, draft, torch.zeros(S, 3), (hist, penalty, temperature, top_k, top_p, seeds, gen_len,
-                                                         positions, last_n))
-            out += spec_sample_pick_sets(lg, dr, h, pen, tmp, tk, tp, sd, gl, ps, last_n=ln, m=m)
+                                                         positions, last_n, presence, frequency, min_p))
+            out += spec_sample_pick_sets(lg, dr, h, pen, tmp, tk, tp, sd, gl, ps, last_n=ln, m=m, presence=pr,
+                                         frequency=fr, min_p=mp)
         return out
     n = int(gen_len[0])
     Tmp = float(temperature[0])
     out = []
-    for i, row in enumerate(_spec_rows(logits, draft, hist, penalty, last_n, positions)):
+    for i, row in enumerate(_spec_rows(logits, draft, hist, penalty, last_n, positions, presence, frequency)):
         if Tmp <= 0:
             out.append({int(row.argmax())})
         else:
-            out.append(sample_pick_set(row, Tmp, int(top_k[0]), float(top_p[0]), device_uniform(int(seeds[0]), n + i), m))
+            out.append(sample_pick_set(row, Tmp, int(top_k[0]), float(top_p[0]), device_uniform(int(seeds[0]), n + i), m,
+                                       min_p=_row_opt(min_p, 0)))
     return out

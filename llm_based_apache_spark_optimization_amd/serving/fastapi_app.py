@@ -31,6 +31,7 @@ from pydantic import BaseModel
 
 from .. import prompts
 from ..client import EngineUnavailable
+from ..engine.engine import SamplingOptionError
 from ..engine.guided import GuidedRequestError
 from ..utils.metrics import REGISTRY, record_generation
 from ..utils.tracing import new_request_id
@@ -83,6 +84,12 @@ def create_app(ctx: Optional[AppContext] = None) -> FastAPI:
         # a pattern the engine cannot serve (unsupported syntax, too large, guided decoding off) is the caller's error
         REGISTRY.inc("lsa_requests_total", 1, "requests", route=request.url.path.strip("/"), outcome="bad_regex")
         return JSONResponse(status_code=400, content={"error": "invalid regex constraint", "detail": str(exc)})
+
+    @app.exception_handler(SamplingOptionError)
+    def bad_option(request: Request, exc: SamplingOptionError):
+        # a sampler option the engine refuses (a NaN penalty, min_p outside [0, 1]) is the caller's error too
+        REGISTRY.inc("lsa_requests_total", 1, "requests", route=request.url.path.strip("/"), outcome="bad_option")
+        return JSONResponse(status_code=400, content={"error": "invalid sampling option", "detail": str(exc)})
 
     @app.post("/process-data/")
     def modify_string(data: InputString):

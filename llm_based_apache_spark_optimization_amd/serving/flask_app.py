@@ -29,6 +29,7 @@ from werkzeug.utils import secure_filename
 
 from .. import prompts
 from ..client import EngineUnavailable
+from ..engine.engine import SamplingOptionError
 from ..engine.guided import GuidedRequestError
 from ..utils.metrics import REGISTRY
 from ..utils.tracing import new_request_id
@@ -52,6 +53,10 @@ def create_app(ctx: Optional[AppContext] = None) -> Flask:
     @app.errorhandler(GuidedRequestError)
     def bad_regex(exc):  # a regex constraint the engine cannot serve is the caller's error
         return jsonify({"error": "invalid regex constraint", "detail": str(exc)}), 400
+
+    @app.errorhandler(SamplingOptionError)
+    def bad_option(exc):  # so is a sampler option the engine refuses (a NaN penalty, min_p outside [0, 1])
+        return jsonify({"error": "invalid sampling option", "detail": str(exc)}), 400
 
     @app.after_request
     def cors(resp):  # the reference enabled CORS for every origin (Flask/app.py:13)
