@@ -178,6 +178,80 @@ def attn_prefill(q, kc, vc, block_tables, cu_q, ctx_lens, H, Hkv, scale, out, kv
     return out
 
 
+# fp64 attention with its componentwise error scale, for the elementwise tests (tests/attn_exact.py): next to the output
+# o = sum_j p_j v_j every function returns a = sum_j p_j |v_j| per (row, head, column).  A kernel that rounds P, the row
+# sum or the output to bf16 is off by a small multiple of 2^-9 a in EVERY element, whatever cancels in o; a wrong or
+# missing key is off by about p_j |v_j|, which the whole-tensor norm ratio does not see.  fp8 caches: over the
+# dequantised cache (e4m3 value times the f32 row scale, exact in fp64).
+def _attn_rows_f64(q, k, v, scale, limits):
+    """q [H, R, D], k / v [H, n, D] (fp64); row r sees keys j < limits[r] -> (o, a) [R, H, D]."""
+    s = torch.einsum("hrd,hnd->hrn", q, k) * scale
+    hidden = torch.arange(k.shape[1], device=q.device).view(1, -1) >= limits.view(-1, 1)
+    p = s.masked_fill(hidden, float("-inf")).softmax(-1)
+    return (torch.einsum("hrn,hnd->rhd", p, v), torch.einsum("hrn,hnd->rhd", p, v.abs()))
+
+
+def _gather_kv_f64(cache, table_row, n, scales, G):
+    if scales is None:
+        return _gather_kv(cache, table_row, n).double().repeat_interleave(G, 0)
+    nb = (n + BLOCK - 1) // BLOCK
+    idx = table_row[:nb].long()
+    blocks = kv8_logical(cache[idx]).view(torch.float8_e4m3fn).double() * scales[idx].double().unsqueeze(-1)
+    return blocks.permute(1, 0, 2, 3).reshape(cache.shape[1], nb * BLOCK, cache.shape[3])[:, :n].repeat_interleave(G, 0)
+
+
+def attn_decode_f64(q, kc, vc, block_tables, pos, H, Hkv, scale, kv_scales=None):
+    """``attn_decode`` in fp64 -> (o, a), both [B, H, D] float64."""
+    B, G = pos.shape[0], H // Hkv
+    ks, vs = kv_scales if kv_scales is not None else (None, None)
+    o = torch.zeros(B, H, q.shape[-1], dtype=torch.float64, device=q.device)
+    a = torch.zeros_like(o)
+    for b in range(B):
+        n = int(pos[b]) + 1
+        k = _gather_kv_f64(kc, block_tables[b], n, ks, G)
+        v = _gather_kv_f64(vc, block_tables[b], n, vs, G)
+        ob, ab = _attn_rows_f64(q[b].double().view(H, 1, -1), k, v, scale, torch.tensor([n], device=q.device))
+        o[b], a[b] = ob[0], ab[0]
+    return o, a
+
+
+def attn_prefill_f64(q, kc, vc, block_tables, cu_q, ctx_lens, H, Hkv, scale, kv_scales=None):
+    """``attn_prefill`` in fp64 -> (o, a), both [T, H, D] float64 (rows of a zero-length sequence: none)."""
+    G = H // Hkv
+    ks, vs = kv_scales if kv_scales is not None else (None, None)
+    o = torch.zeros(q.shape[0], H, q.shape[-1], dtype=torch.float64, device=q.device)
+    a = torch.zeros_like(o)
+    cu = cu_q.tolist()
+    for sq in range(len(cu) - 1):
+        q0, q1 = cu[sq], cu[sq + 1]
+        if q1 == q0:
+            continue
+        n = int(ctx_lens[sq])
+        k = _gather_kv_f64(kc, block_tables[sq], n, ks, G)
+        v = _gather_kv_f64(vc, block_tables[sq], n, vs, G)
+        limits = torch.arange(n - (q1 - q0), n, device=q.device) + 1
+        o[q0:q1], a[q0:q1] = _attn_rows_f64(q[q0:q1].double().transpose(0, 1), k, v, scale, limits)
+    return o, a
+
+
+def attn_verify_f64(q, kc, vc, block_table, pos0, H, Hkv, scale, kv_scales=None):
+    """``attn_verify`` in fp64 -> (o, a), both [S * T, H, D] float64."""
+    S, T = (q.shape[0], q.shape[1]) if q.dim() == 4 else (1, q.shape[0])
+    G = H // Hkv
+    ks, vs = kv_scales if kv_scales is not None else (None, None)
+    qs = q.reshape(S, T, H, -1)
+    o = torch.zeros(S * T, H, q.shape[-1], dtype=torch.float64, device=q.device)
+    a = torch.zeros_like(o)
+    for s in range(S):
+        p0 = int(pos0.reshape(-1)[s])
+        row = block_table.reshape(S, -1)[s]
+        k = _gather_kv_f64(kc, row, p0 + T, ks, G)
+        v = _gather_kv_f64(vc, row, p0 + T, vs, G)
+        limits = torch.arange(p0, p0 + T, device=q.device) + 1
+        o[s * T:(s + 1) * T], a[s * T:(s + 1) * T] = _attn_rows_f64(qs[s].double().transpose(0, 1), k, v, scale, limits)
+    return o, a
+
+
 def commit(tok, out_tokens, gen_len, input_ids, positions, finished, eos, limit=None, eos_on=None, hist=None):
     eos_set = set(eos.tolist()) if eos is not None else set()
     max_new = out_tokens.shape[1]
