@@ -64,6 +64,11 @@ int lsa_spec_draft(const int* prompt_tok, int prompt_ld, const int* prompt_len, 
                    const int* gen_len, const int* input_ids, const int* positions, int rows, int k, int n_max, int n_min,
                    const int* forced, int nf, int forced_ld, int* spec_ids, int* spec_pos, int* spec_draft,
                    hipStream_t s);
+int lsa_logprob_scan(const float* logits, int B, int V, const int* lp_k, const int* finished, const int* gen_len,
+                     float* lp_raw, float* lp_ms, unsigned long long* lp_cand, int* lp_n0, hipStream_t s);
+int lsa_logprob_commit(const float* lp_raw, int B, int V, const float* lp_ms, const unsigned long long* lp_cand,
+                       const int* lp_k, int* lp_n0, const int* gen_len, const int* out_tokens, int max_new, float* lp_tok,
+                       int* lp_ids, float* lp_top, int kcap, hipStream_t s);
 int lsa_dfa_mask(float* logits, int B, int V, const int* tok_off, const uint8_t* tok_blob, const uint8_t* cls,
                  const uint16_t* trans, const uint8_t* accept, const int* g_dim, const int* g_on, int* g_state,
                  const int* g_base, const int* rows, const int* gen_len, const int* input_ids, const int* finished,
@@ -1062,6 +1067,70 @@ void spec_commit(const at::Tensor& logits, at::Tensor& part, const at::Tensor& d
         "spec_commit");
 }
 
+// per-token logprobs (kernels/logprobs.hip).  Workspace of both launches: lp_ms f32 [>= B * ceil(V / 2048) * 2], lp_cand
+// int64 [>= B * ceil(V / 2048) * 32]; lp_raw f32 [>= B, V] holds the raw rows between them.
+void check_logprob_ws(const char* op, int64_t B, int64_t V, const at::Tensor& lp_k, const at::Tensor& lp_n0,
+                      const at::Tensor& gen_len, const at::Tensor& lp_raw, const at::Tensor& lp_ms,
+                      const at::Tensor& lp_cand) {
+  TORCH_CHECK(B >= 1 && V >= 1 && V <= 262144, op, ": 1 <= V <= 262144 (the sampler's bound), B >= 1");
+  for (const at::Tensor* t : {&lp_k, &lp_n0, &gen_len}) {
+    need(*t, at::kInt, "logprob state operand");
+    TORCH_CHECK(t->is_contiguous() && t->numel() >= B, op, ": lp_k / lp_n0 / gen_len contiguous int32 [>= B]");
+  }
+  need(lp_raw, at::kFloat, "lp_raw");
+  need(lp_ms, at::kFloat, "lp_ms");
+  need(lp_cand, at::kLong, "lp_cand");
+  TORCH_CHECK(lp_raw.dim() == 2 && lp_raw.size(0) >= B && lp_raw.size(1) == V && lp_raw.is_contiguous(), op,
+              ": lp_raw contiguous f32 [>= B, V]");
+  const int64_t nch = (V + 2047) / 2048;
+  TORCH_CHECK(lp_ms.is_contiguous() && lp_cand.is_contiguous() && lp_ms.numel() >= B * nch * 2 &&
+                  lp_cand.numel() >= B * nch * 32,
+              op, ": chunk workspaces too small");
+}
+
+void logprob_scan(const at::Tensor& logits, const at::Tensor& lp_k, const at::Tensor& finished,
+                  const at::Tensor& gen_len, at::Tensor& lp_raw, at::Tensor& lp_ms, at::Tensor& lp_cand,
+                  at::Tensor& lp_n0) {
+  need(logits, at::kFloat, "logits");
+  TORCH_CHECK(logits.dim() == 2 && logits.is_contiguous(), "logprob_scan: logits contiguous [B, V]");
+  const int64_t B = logits.size(0), V = logits.size(1);
+  check_logprob_ws("logprob_scan", B, V, lp_k, lp_n0, gen_len, lp_raw, lp_ms, lp_cand);
+  need(finished, at::kInt, "finished");
+  TORCH_CHECK(finished.is_contiguous() && finished.numel() >= B, "logprob_scan: finished contiguous int32 [>= B]");
+  check(lsa_logprob_scan(logits.data_ptr<float>(), (int)B, (int)V, lp_k.data_ptr<int>(), finished.data_ptr<int>(),
+                         gen_len.data_ptr<int>(), lp_raw.data_ptr<float>(), lp_ms.data_ptr<float>(),
+                         reinterpret_cast<unsigned long long*>(lp_cand.data_ptr()), lp_n0.data_ptr<int>(), cur_stream()),
+        "logprob_scan");
+}
+
+// records: lp_tok f32 of out_tokens' shape, lp_ids int32 / lp_top f32 [rows, max_new, K] with 0 <= K <= 20
+void logprob_commit(const at::Tensor& lp_raw, const at::Tensor& lp_ms, const at::Tensor& lp_cand,
+                    const at::Tensor& lp_k, at::Tensor& lp_n0, const at::Tensor& gen_len, const at::Tensor& out_tokens,
+                    at::Tensor& lp_tok, at::Tensor& lp_ids, at::Tensor& lp_top, int64_t B) {
+  need(lp_raw, at::kFloat, "lp_raw");
+  TORCH_CHECK(lp_raw.dim() == 2, "logprob_commit: lp_raw [>= B, V]");
+  const int64_t V = lp_raw.size(1);
+  check_logprob_ws("logprob_commit", B, V, lp_k, lp_n0, gen_len, lp_raw, lp_ms, lp_cand);
+  need(out_tokens, at::kInt, "out_tokens");
+  need(lp_tok, at::kFloat, "lp_tok");
+  need(lp_ids, at::kInt, "lp_ids");
+  need(lp_top, at::kFloat, "lp_top");
+  TORCH_CHECK(out_tokens.dim() == 2 && out_tokens.size(0) >= B && out_tokens.size(1) >= 1 && out_tokens.is_contiguous(),
+              "logprob_commit: out_tokens contiguous [>= B, max_new]");
+  TORCH_CHECK(lp_tok.sizes() == out_tokens.sizes() && lp_tok.is_contiguous(),
+              "logprob_commit: lp_tok must have out_tokens' shape");
+  TORCH_CHECK(lp_ids.dim() == 3 && lp_ids.sizes() == lp_top.sizes() && lp_ids.size(0) == out_tokens.size(0) &&
+                  lp_ids.size(1) == out_tokens.size(1) && lp_ids.is_contiguous() && lp_top.is_contiguous(),
+              "logprob_commit: lp_ids / lp_top contiguous [rows, max_new, K] over out_tokens' rows");
+  TORCH_CHECK(lp_ids.size(2) >= 0 && lp_ids.size(2) <= 20, "logprob_commit: top_logprobs K must be in 0 .. 20");
+  check(lsa_logprob_commit(lp_raw.data_ptr<float>(), (int)B, (int)V, lp_ms.data_ptr<float>(),
+                           reinterpret_cast<const unsigned long long*>(lp_cand.data_ptr()), lp_k.data_ptr<int>(),
+                           lp_n0.data_ptr<int>(), gen_len.data_ptr<int>(), out_tokens.data_ptr<int>(),
+                           (int)out_tokens.size(1), lp_tok.data_ptr<float>(), lp_ids.data_ptr<int>(),
+                           lp_top.data_ptr<float>(), (int)lp_ids.size(2), cur_stream()),
+        "logprob_commit");
+}
+
 // regex-constrained decoding: -inf into every logit whose token would kill the row's DFA (kernels/guided.hip).
 // Table rows are indexed by rows[b] when given (prefill tail: the sequence's slot), else by b.
 void dfa_mask(at::Tensor& logits, const at::Tensor& tok_off, const at::Tensor& tok_blob, const at::Tensor& cls,
@@ -1534,6 +1603,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("positions"), py::arg("finished"), py::arg("eos"), py::arg("limit"), py::arg("eos_on"), py::arg("part"),
         py::arg("cand"), py::arg("picks"), py::arg("presence") = py::none(), py::arg("frequency") = py::none(),
         py::arg("min_p") = py::none());
+  m.def("logprob_scan", &logprob_scan, py::arg("logits"), py::arg("lp_k"), py::arg("finished"), py::arg("gen_len"),
+        py::arg("lp_raw"), py::arg("lp_ms"), py::arg("lp_cand"), py::arg("lp_n0"));
+  m.def("logprob_commit", &logprob_commit, py::arg("lp_raw"), py::arg("lp_ms"), py::arg("lp_cand"), py::arg("lp_k"),
+        py::arg("lp_n0"), py::arg("gen_len"), py::arg("out_tokens"), py::arg("lp_tok"), py::arg("lp_ids"),
+        py::arg("lp_top"), py::arg("B"));
   m.def("dfa_mask", &dfa_mask, py::arg("logits"), py::arg("tok_off"), py::arg("tok_blob"), py::arg("cls"),
         py::arg("trans"), py::arg("accept"), py::arg("g_dim"), py::arg("g_on"), py::arg("g_state"), py::arg("g_base"),
         py::arg("rows"), py::arg("gen_len"), py::arg("input_ids"), py::arg("finished"), py::arg("eos"));

@@ -30,7 +30,7 @@ from typing import Callable, Dict, Iterator, Optional
 
 import torch
 
-from .engine.engine import SamplingParams
+from .engine.engine import SamplingOptionError, SamplingParams
 
 
 @dataclasses.dataclass
@@ -48,6 +48,9 @@ class GenerateResponse:
     eval_duration: int = 0
     # of prompt_eval_count (the full prompt length), the tokens served from the engine's prefix cache
     prompt_cached_count: int = 0
+    # per-token logprobs, when the request asked ("logprobs": true): one {"token", "logprob", "bytes", "top_logprobs":
+    # [{"token", "logprob", "bytes"}]} per generated token (a streamed chunk: those of the tokens read at its sync)
+    logprobs: Optional[list] = None
 
     def __getitem__(self, k):
         return getattr(self, k)
@@ -56,7 +59,10 @@ class GenerateResponse:
         return getattr(self, k, default)
 
     def to_dict(self) -> dict:
-        return dataclasses.asdict(self)
+        d = dataclasses.asdict(self)
+        if d["logprobs"] is None:  # nothing asked: the response is key for key what it is without the feature
+            del d["logprobs"]
+        return d
 
     @property
     def tokens_per_second(self) -> float:
@@ -252,7 +258,7 @@ class EngineService(Backend):
                                 total_duration=r.total_duration_ns, load_duration=r.load_duration_ns,
                                 prompt_eval_count=r.prompt_tokens, prompt_eval_duration=r.prompt_eval_duration_ns,
                                 eval_count=r.eval_count, eval_duration=r.eval_duration_ns,
-                                prompt_cached_count=r.cached_prompt_tokens)
+                                prompt_cached_count=r.cached_prompt_tokens, logprobs=r.logprobs)
 
     def generate(self, model, prompt, system="", options=None, raw=False) -> GenerateResponse:
         eng, req = self._submit(model, prompt, system, options, raw)
@@ -267,13 +273,23 @@ class EngineService(Backend):
         ``run_ahead`` steps for requests that ignore EOS), then the final chunk with the timings."""
         eng, req = self._submit(model, prompt, system, options, raw, stream=True)
         try:
+            sent = 0  # generated tokens whose logprob entries went out
             for piece in eng.stream_text(req, timeout_s=self.timeout_s):
-                yield GenerateResponse(model=model, response=piece, done=False, done_reason="", created_at=_now())
+                ents = None
+                if req.params.logprobs:  # the entries of the tokens this sync revealed
+                    toks = req.stream_toks
+                    ents = eng.logprob_entries(req, toks[sent:], start=sent)
+                    sent = len(toks)
+                yield GenerateResponse(model=model, response=piece, done=False, done_reason="", created_at=_now(),
+                                       logprobs=ents)
         except queue.Empty:
             raise TimeoutError(f"generation on {model} timed out after {self.timeout_s}s") from None
         except RuntimeError as e:
             raise RuntimeError(f"engine {model} failed: {e}") from None
-        yield dataclasses.replace(self._final(model, eng, req), response="")
+        last = self._final(model, eng, req)
+        if last.logprobs is not None:  # what no earlier chunk carried; over the chunks: the non-streamed list
+            last = dataclasses.replace(last, logprobs=last.logprobs[sent:])
+        yield dataclasses.replace(last, response="")
 
     def models(self) -> list:
         return sorted(self._loops)
@@ -289,6 +305,7 @@ class EngineService(Backend):
                                                                    "spec_batch_sampled", False)),
                                 "spec_batch_guided": bool(getattr(getattr(lp.engine, "runner", None),
                                                                   "spec_batch_guided", False)),
+                                "logprobs": bool(getattr(lp.engine, "logprobs", False)),
                                 **lp.engine.stats} for m, lp in self._loops.items()}}
 
 
@@ -311,6 +328,8 @@ class FakeBackend(Backend):
             if self.fail_next is not None:
                 e, self.fail_next = self.fail_next, None
                 raise e
+        if options and (options.get("logprobs") or options.get("top_logprobs")):
+            raise SamplingOptionError("the fake backend has no model distribution: logprobs cannot be served")
         t0 = time.perf_counter()
         if options and options.get("fake_delay"):
             time.sleep(float(options["fake_delay"]))
@@ -364,6 +383,9 @@ def get_backend() -> Backend:
 
 
 def generate(model: str, prompt: str = "", system: str = "", options: Optional[dict] = None, raw: bool = False,
-             **_ignored) -> GenerateResponse:
-    """Drop-in for ``ollama.generate(model=, system=, prompt=)``."""
+             logprobs: bool = False, top_logprobs: int = 0, **_ignored) -> GenerateResponse:
+    """Drop-in for ``ollama.generate(model=, system=, prompt=)``.  ``logprobs`` / ``top_logprobs`` (Ollama's top-level
+    request fields) travel to the backend inside ``options``."""
+    if logprobs or top_logprobs:
+        options = dict(options or {}, logprobs=bool(logprobs), top_logprobs=top_logprobs)
     return get_backend().generate(model, prompt, system, options, raw)

@@ -86,6 +86,12 @@ class Settings:
     # plain).  Needs guided, spec_guided, spec_tokens and spec_batch > 1 (and spec_batch_sampled for a constrained
     # request that needs the sampler); every request's tokens are those of its plain guided steps
     spec_batch_guided: bool = dataclasses.field(default_factory=lambda: _env("SPEC_BATCH_GUIDED", False, bool))
+    # per-token logprobs (off by default): requests may carry "logprobs" / "top_logprobs" (0 .. 20) and get every
+    # generated token's log-probability under the model's own distribution (raw logits: before the regex mask, the
+    # penalties and temperature / top-k / top-p / min-p).  sql_logprobs (needs logprobs): /nl2sql and the pipeline's
+    # job result add sql_mean_logprob / sql_min_logprob of the generated statement
+    logprobs: bool = dataclasses.field(default_factory=lambda: _env("LOGPROBS", False, bool))
+    sql_logprobs: bool = dataclasses.field(default_factory=lambda: _env("SQL_LOGPROBS", False, bool))
     tp: int = dataclasses.field(default_factory=lambda: _env("TP", 1, int))
     dp: int = dataclasses.field(default_factory=lambda: _env("DP", 1, int))
     max_batch: int = dataclasses.field(default_factory=lambda: _env("MAX_BATCH", 32, int))

@@ -44,6 +44,13 @@ class SamplingOptionError(ValueError):
     layer answers it with 400, as it answers a ``GuidedRequestError``."""
 
 
+def _top_logprobs_option(v) -> int:
+    try:
+        return int(v or 0)
+    except (TypeError, ValueError):
+        raise SamplingOptionError("top_logprobs must be an integer in 0 .. 20") from None
+
+
 @dataclasses.dataclass
 class SamplingParams:
     """Ollama-compatible options (temperature 0 = greedy, as the benchmark configs require)."""
@@ -82,6 +89,13 @@ class SamplingParams:
     # returned as it stands, possibly short of a match.  Not with ignore_eos.  A constrained request speculates only
     # on an engine built with spec_guided (LSA_SPEC_GUIDED=1); its tokens are those of its plain guided steps.
     regex: Optional[str] = None
+    # per-token log-probabilities, where the engine runs them (LLMEngine(logprobs=True)): Ollama's / OpenAI's
+    # "logprobs" (bool) and "top_logprobs" (K, 0 .. 20).  Every generated token comes back with its log-probability
+    # and, K > 0, the K most likely tokens of its step with theirs -- under the model's own distribution: log-softmax
+    # over the whole vocabulary of the logits as the lm_head wrote them, before the regex mask, the penalties and
+    # temperature / top-k / top-p / min-p.  A request that asks never speculates; its tokens are what they are without.
+    logprobs: bool = False
+    top_logprobs: int = 0
 
     @property
     def needs_sampler(self) -> bool:
@@ -110,7 +124,9 @@ class SamplingParams:
                               num_ctx=int(opts["num_ctx"]) if opts.get("num_ctx") else None,
                               num_keep=int(opts.get("num_keep", 4)), speculate=bool(opts.get("speculate", True)),
                               cache_prompt=bool(opts.get("cache_prompt", True)),
-                              regex=(str(opts["regex"]) if opts.get("regex") else None))
+                              regex=(str(opts["regex"]) if opts.get("regex") else None),
+                              logprobs=bool(opts.get("logprobs", False)),
+                              top_logprobs=_top_logprobs_option(opts.get("top_logprobs", 0)))
 
 
 @dataclasses.dataclass
@@ -131,6 +147,7 @@ class Request:
     # streaming: ("tokens", ids-so-far) after every host sync that saw new tokens, then ("done", None)
     stream: Optional[queue.Queue] = None
     streamed: int = 0
+    stream_toks: list = dataclasses.field(default_factory=list)  # the snapshot ``stream_text`` last took from it
     # tokens generated before a preemption (lazy KV growth ran the arena dry): the current incarnation's prompt is
     # prompt_ids + resumed and its params.max_tokens the remaining budget
     resumed: list = dataclasses.field(default_factory=list)
@@ -143,6 +160,10 @@ class Request:
     cached_tokens: int = 0
     # regex-constrained decoding: the compiled pattern (engine/guided.py Dfa) of params.regex
     dfa: Optional[object] = None
+    # per-token logprobs (params.logprobs): one (logprob, [(token id, logprob)] * K) per generated token, in order,
+    # kept on the host across preemptions; lp_read = device records of the current incarnation already read
+    logprobs: list = dataclasses.field(default_factory=list)
+    lp_read: int = 0
 
     @property
     def ctx_ids(self) -> list:
@@ -162,13 +183,16 @@ class GenerationResult:
     eval_duration_ns: int
     done_reason: str
     cached_prompt_tokens: int = 0  # prompt tokens served from the prefix cache instead of being prefilled
+    # params.logprobs: one {"token", "logprob", "bytes", "top_logprobs": [{"token", "logprob", "bytes"}]} per generated
+    # token (len == eval_count); None when the request did not ask
+    logprobs: Optional[list] = None
 
 
 class LLMEngine:
     def __init__(self, runner: ModelRunner, tokenizer=None, max_prefill_tokens: int = 16384, sync_every: int = 8,
                  name: Optional[str] = None, prefill_chunk: Optional[int] = None, kv_reserve_tokens: int = BLOCK,
                  spec_tokens: int = 0, prefix_cache: bool = False, prefix_cow_min_tokens: Optional[int] = None,
-                 guided: bool = False, spec_batch: int = 0):
+                 guided: bool = False, spec_batch: int = 0, logprobs: bool = False):
         self.runner = runner
         if spec_tokens:  # speculative decoding for batch-1 greedy requests (the runner clamps it to what it supports)
             runner.spec_tokens = int(spec_tokens)
@@ -231,6 +255,14 @@ class LLMEngine:
             if not getattr(runner, "guided", False):
                 runner.enable_guided(off, blob)
             self.stats.update(guided_requests=0, guided_steps=0)
+        # per-token logprobs (SamplingParams.logprobs): the runner allocates its per-slot records and captures a variant
+        # of each decode graph; off (the default) nothing is allocated, launched or counted
+        self.logprobs = bool(logprobs) or bool(getattr(runner, "logprobs", False))
+        self._lp_pieces: dict = {}  # token id -> (decoded piece, its bytes)
+        if self.logprobs:
+            if not getattr(runner, "logprobs", False):
+                runner.enable_logprobs()
+            self.stats.update(logprob_requests=0, logprob_steps=0)
         # per-decode-run device timing (hipEvents around the graph replays, read after the host sync the
         # run ends with anyway): lsa_decode_step_device_seconds{model} = GPU time per token step
         self.device_timing = runner.on_gpu
@@ -270,6 +302,13 @@ class LLMEngine:
                 raise SamplingOptionError(f"{name} must be a finite number")
         if not 0.0 <= float(p.min_p) <= 1.0:
             raise SamplingOptionError("min_p must lie in [0, 1]")
+        if not isinstance(p.top_logprobs, int) or isinstance(p.top_logprobs, bool) or not 0 <= p.top_logprobs <= 20:
+            raise SamplingOptionError("top_logprobs must be an integer in 0 .. 20")
+        if p.top_logprobs and not p.logprobs:
+            raise SamplingOptionError("top_logprobs needs logprobs: true")
+        if p.logprobs and not self.logprobs:
+            raise SamplingOptionError("this engine was built without per-token logprobs (logprobs=True / "
+                                      "LSA_LOGPROBS=1 enables it)")
         dfa = None
         if p.regex is not None:  # compiled here, so that a bad pattern fails the request, not the engine loop
             if not self.guided:
@@ -280,6 +319,8 @@ class LLMEngine:
             dfa = compile_regex(p.regex)
         req = Request(next(self._ids), list(map(int, prompt_ids)), p, time.perf_counter(),
                       stream=queue.Queue() if stream else None, dfa=dfa)
+        if p.logprobs:
+            self.stats["logprob_requests"] += 1
         if dfa is not None:
             self.stats["guided_requests"] += 1
             REGISTRY.inc("lsa_guided_requests_total", 1, "requests with a regex constraint", model=self.name)
@@ -338,6 +379,9 @@ class LLMEngine:
                                     repeat_last_n=sp.repeat_last_n, presence_penalty=sp.presence_penalty,
                                     frequency_penalty=sp.frequency_penalty, min_p=sp.min_p, prompt_ids=req.ctx_ids,
                                     defer_table=self.prefill_chunk is not None))
+                if sp.logprobs:  # the row records (runner.enable_logprobs): lp_k = its top_logprobs K
+                    entries[-1].update(lp_k=int(sp.top_logprobs))
+                    req.lp_read = 0  # the device record indices restart with the incarnation
                 if req.dfa is not None:  # a re-admitted request resumes in the state its generated tokens reached
                     entries[-1].update(dfa=req.dfa, dfa_state=req.dfa.walk(req.dfa.start, self._bytes_of(req.resumed)))
                 self._prefilling.append(req)
@@ -357,6 +401,8 @@ class LLMEngine:
                     q.gen_host = 1
                     if q.stream is not None:  # the prefill's token goes out now (one sync, streaming only)
                         q.streamed = len(q.resumed) + 1
+                        if q.params.logprobs:  # its record too, ahead of the chunk that carries the token
+                            self._read_logprobs([q], [1])
                         q.stream.put(("tokens", q.resumed + r.tokens_of(q.slot, 1)))
                 self.stats["prefill_s"] += t1 - t0
             pending = {q.rid for q in self._prefilling}
@@ -365,6 +411,8 @@ class LLMEngine:
                 return []
             sample = any(self._reqs[rid].params.needs_sampler for rid in running)
             guided = self.guided and any(self._reqs[rid].dfa is not None for rid in running)
+            # the logprob graph variant exactly while a running request asked; such a request never speculates
+            lp = self.logprobs and any(self._reqs[rid].params.logprobs for rid in running)
             # steps until the earliest request can hit its length limit; with EOS possible, at most
             # sync_every steps between host checks
             reqs = [self._reqs[rid] for rid in running]
@@ -375,7 +423,7 @@ class LLMEngine:
                 n_steps = remaining if self.run_ahead is None else min(self.run_ahead, remaining)
             else:
                 n_steps = min(self.sync_every, remaining)
-            spec_T = self._spec_run(reqs, n_steps, remaining) if n_steps else 0
+            spec_T = self._spec_run(reqs, n_steps, remaining) if (n_steps and not lp) else 0
             if spec_T:  # verify steps: each commits 1 .. spec_T tokens, so fewer cover the same budget
                 n_steps = min(n_steps, -(-remaining // spec_T))
             elif n_steps:
@@ -411,6 +459,8 @@ class LLMEngine:
                     r.decode_spec(n_steps, max_ctx=max_ctx, guided=True)
                 else:
                     r.decode_spec(n_steps, max_ctx=max_ctx)
+            elif lp:  # the variant with the two logprob launches (masked too, if a row is constrained)
+                r.decode(B, n_steps, sample, max_ctx=max_ctx, guided=guided, logprobs=True)
             else:
                 if guided:  # the graph variant with the mask launch, only while a running row is constrained
                     r.decode(B, n_steps, sample, max_ctx=max_ctx, guided=True)
@@ -427,6 +477,10 @@ class LLMEngine:
                 REGISTRY.inc("lsa_guided_steps_total", n_steps, "decode steps run with the regex mask", model=self.name)
             if spec_T and n_steps:
                 self._spec_account(reqs)
+            if lp:  # the records of this sync's new tokens, for the rows that asked, in one transfer
+                self.stats["logprob_steps"] += n_steps
+                asked = [(q, min(int(gl[i]), q.params.max_tokens)) for i, q in enumerate(reqs) if q.params.logprobs]
+                self._read_logprobs([q for q, _ in asked], [n for _, n in asked])
             if ev is not None:
                 dev_s = ev[0].elapsed_time(ev[1]) / 1e3  # both recorded before read_rows' sync
                 self.stats["decode_device_s"] += dev_s
@@ -502,7 +556,8 @@ class LLMEngine:
         has not opted out or been dropped by the acceptance guard; room for every position the run may write inside the model window; and the KV blocks of those
         positions without preempting anyone: the worst case is T committed tokens per step plus T - 1 rows of
         lookahead (also reserved so that a finished row, which rewrites its last T positions while the graph replays,
-        stays in its own blocks)."""
+        stays in its own blocks).  A run in which a request asked for per-token logprobs is never one (``step`` does not
+        ask: the verify graphs record none), which for ``spec_batch`` is one more reason of the all-or-nothing rule."""
         r = self.runner
         if not (getattr(r, "spec_tokens", 0) > 0 and r.spec_supported()):
             return 0
@@ -575,6 +630,41 @@ class LLMEngine:
             r.extend_tables(grown)
         return T if ok else 0
 
+    def _read_logprobs(self, reqs: list, ns: list) -> None:
+        """Append device records [q.lp_read, n) of each request's slot row to ``q.logprobs`` (one transfer)."""
+        sel = [(q, n) for q, n in zip(reqs, ns) if n > q.lp_read]
+        if not sel:
+            return
+        recs = self.runner.logprobs_of_many([q.slot for q, _ in sel], [q.lp_read for q, _ in sel], [n for _, n in sel])
+        for (q, n), rec in zip(sel, recs):
+            q.logprobs.extend(rec)
+            q.lp_read = n
+
+    def _lp_piece(self, tid: int) -> tuple:
+        """(decoded piece, byte values) of a token id: the bytes come from the tokenizer's ``token_bytes`` table."""
+        got = self._lp_pieces.get(tid)
+        if got is None:
+            if self._tok_bytes is None:
+                off, blob = token_bytes(self.tok, self.spec.vocab_size)
+                self._tok_bytes = (off.tolist(), blob.tobytes())
+            off, blob = self._tok_bytes
+            raw = blob[off[tid]:off[tid + 1]] if 0 <= tid < len(off) - 1 else b""
+            got = self._lp_pieces[tid] = (self.tok.decode([tid]), list(raw))
+        return got
+
+    def logprob_entries(self, req: Request, token_ids: Sequence[int], start: int = 0) -> list:
+        """The response entries of generated tokens ``token_ids`` = output tokens [start, start + len) of ``req``."""
+        out = []
+        for j, tid in enumerate(token_ids):
+            lpv, top = req.logprobs[start + j]
+            piece, raw = self._lp_piece(int(tid))
+            ent = {"token": piece, "logprob": float(lpv), "bytes": raw}
+            if req.params.top_logprobs:
+                ent["top_logprobs"] = [dict(zip(("token", "bytes"), self._lp_piece(int(i))), logprob=float(v))
+                                       for i, v in top]
+            out.append(ent)
+        return out
+
     def _bytes_of(self, ids: Sequence[int]) -> bytes:
         """The bytes the token ids decode to (the table regex-constrained decoding walks on the device)."""
         off, blob = self._tok_bytes
@@ -607,6 +697,9 @@ class LLMEngine:
         of the prompt it re-prefills (recompute), its budget shrinks by as many."""
         n = min(q.gen_host, q.params.max_tokens)
         toks = self.runner.tokens_of(q.slot, n) if n else []
+        if q.params.logprobs:  # its unread records, before the slot goes: they stay with the request on the host
+            self._read_logprobs([q], [n])
+            q.lp_read = 0
         q.resumed = q.resumed + toks
         q.params = dataclasses.replace(q.params, max_tokens=q.params.max_tokens - n)
         self.runner.release_slot(q.slot)
@@ -735,7 +828,8 @@ class LLMEngine:
             total_duration_ns=ns(req.finished_at - req.arrival), load_duration_ns=ns(self.load_time_s),
             prompt_eval_duration_ns=ns(req.first_token - req.admitted),
             eval_duration_ns=ns(req.finished_at - req.first_token), done_reason="stop" if ended_eos else "length",
-            cached_prompt_tokens=req.cached_tokens)
+            cached_prompt_tokens=req.cached_tokens,
+            logprobs=self.logprob_entries(req, req.output_ids) if req.params.logprobs else None)
 
     def text_of(self, token_ids: Sequence[int], req: Request) -> str:
         """The response text of ``token_ids`` exactly as ``result`` builds it (stop strings applied)."""
@@ -753,6 +847,7 @@ class LLMEngine:
             kind, toks = req.stream.get(timeout=timeout_s)
             if kind == "done":
                 break
+            req.stream_toks = toks
             raw = self.tok.decode(list(toks))
             text = self.text_of(toks, req)
             if len(text) < len(raw):  # a stop string appeared: only its prefix is ever sent

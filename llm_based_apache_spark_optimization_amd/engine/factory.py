@@ -22,7 +22,7 @@ def build_engine(model: str, device: Optional[str] = None, checkpoint: Optional[
                  prefix_cow_min_tokens: Optional[int] = None, spec_quantized: bool = False,
                  guided: bool = False, spec_guided: bool = False, spec_sampled: bool = False,
                  spec_batch: int = 1, spec_batch_sampled: bool = False,
-                 spec_batch_guided: bool = False) -> LLMEngine:
+                 spec_batch_guided: bool = False, logprobs: bool = False) -> LLMEngine:
     """kv_dtype: paged KV cache dtype, "bf16" | "fp8" (None: LSA_KV_FP8, default bf16).
     max_new_cap: generated-token cap per request (None: the context window).
     kv_reserve_tokens: generated tokens whose KV is reserved at admission (the rest grows lazily; < 0 reserves
@@ -54,7 +54,10 @@ def build_engine(model: str, device: Optional[str] = None, checkpoint: Optional[
     and leaves an unconstrained sequence untouched; every request's tokens are those of its plain (guided) steps.  An
     all-unconstrained run keeps the unguided batched graph.  Needs guided, spec_guided, spec_tokens and spec_batch > 1
     (a constrained request that needs the sampler: spec_sampled and spec_batch_sampled too), and is inert without any
-    of them."""
+    of them.
+    logprobs: per-token log-probabilities for requests that carry ``SamplingParams.logprobs`` (off by default: such a
+    request is then rejected); allocates the per-slot record buffers and captures a logprob variant of each decode
+    graph, replayed only while a running request asked."""
     if device is None:
         device = f"cuda:{torch.cuda.current_device()}" if torch.cuda.is_available() else "cpu"
     t0 = time.perf_counter()
@@ -73,7 +76,8 @@ def build_engine(model: str, device: Optional[str] = None, checkpoint: Optional[
                          spec_batch_sampled=spec_batch_sampled, spec_batch_guided=spec_batch_guided)
     eng = LLMEngine(runner, tok, sync_every=sync_every, max_prefill_tokens=max_prefill_tokens, name=model,
                     prefill_chunk=prefill_chunk or None, kv_reserve_tokens=kv_reserve_tokens, spec_tokens=spec_tokens,
-                    prefix_cache=prefix_cache, prefix_cow_min_tokens=prefix_cow_min_tokens, guided=guided)
+                    prefix_cache=prefix_cache, prefix_cow_min_tokens=prefix_cow_min_tokens, guided=guided,
+                    logprobs=logprobs)
     if torch.device(device).type == "cuda":
         if warm_graphs:
             runner.capture_all()

@@ -294,6 +294,8 @@ class ModelRunner:
         # regex-constrained decoding (``enable_guided``): off = no buffer, launch or graph differs
         self.guided = False
         self._g_host_on: set = set()  # slots whose current request carries a constraint (host mirror of g_on)
+        # per-token logprobs (``enable_logprobs``): off = no buffer, launch or graph differs
+        self.logprobs = False
         if self.tp is not None and self.tp.size > 1 and self.on_gpu:
             self.tp.warmup()  # communicators (RCCL + the one-shot IPC all-reduce) before any launch
             if not self.tp.capturable():  # gloo without the IPC kernel (test boxes): eager decode steps
@@ -413,12 +415,13 @@ class ModelRunner:
         tier = min(tier, self.max_model_len)
         return tuple(ops.decode_split_plan(B, self.Hkv, tier))
 
-    def _decode_step(self, B: int, sample: bool, plan: Optional[tuple] = None, guided: bool = False) -> None:
+    def _decode_step(self, B: int, sample: bool, plan: Optional[tuple] = None, guided: bool = False,
+                     logprobs: bool = False) -> None:
         a8, a8m, a8o, a8d = self.a8_plan(B)  # qkv / gate_up / o / down W8A8 (W4A8)
         if B == 1 and self.rr_decode and (self.rr_a8 or not (a8 or a8m or a8o)):
-            return self._decode_step_rr(sample, plan, guided)
+            return self._decode_step_rr(sample, plan, guided, logprobs)
         if self.fused_norm and B <= self.fused_norm_max_batch and not (a8 or a8m or a8o):
-            return self._decode_step_fused(B, sample, plan, guided)
+            return self._decode_step_fused(B, sample, plan, guided, logprobs)
         w, d = self.w, self.d
         ids, pos, bt = self.input_ids[:B], self.positions[:B], self.block_tables[:B]
         h = self.h[:B]
@@ -505,9 +508,10 @@ class ModelRunner:
             else:
                 lin(act, lw.w_down, "f32", out=d_parts, splitk=sk_d)
         ops.add_rmsnorm(h, w.final_norm, self.eps, xn, parts=self._reduce_parts(d_parts), rows=B, xf=xf)
-        self._decode_tail(B, sample, xn, xf, guided, z12=z12)
+        self._decode_tail(B, sample, xn, xf, guided, z12=z12, logprobs=logprobs)
 
-    def _decode_step_fused(self, B: int, sample: bool, plan: Optional[tuple] = None, guided: bool = False) -> None:
+    def _decode_step_fused(self, B: int, sample: bool, plan: Optional[tuple] = None, guided: bool = False,
+                           logprobs: bool = False) -> None:
         """Norm-free decode step (TP = 1): 5 launches per layer instead of 7.
 
           embed (+ row sum of squares)  ->  per layer:
@@ -557,9 +561,10 @@ class ModelRunner:
             lin(xn, lw.w_gate_up, "silu", out=act, rownorm=(ssq[2 * l + 1], self.eps))
             lin(act, lw.w_down, "res", out=d_parts, splitk=sk_d, res=(h, xn, ssq[2 * l + 2], tk), **rc)
         ops.add_rmsnorm(h, w.final_norm, self.eps, xn, rows=B, xf=xf, write_h=False)
-        self._decode_tail(B, sample, xn, xf, guided)
+        self._decode_tail(B, sample, xn, xf, guided, logprobs=logprobs)
 
-    def _decode_step_rr(self, sample: bool, plan: Optional[tuple] = None, guided: bool = False) -> None:
+    def _decode_step_rr(self, sample: bool, plan: Optional[tuple] = None, guided: bool = False,
+                        logprobs: bool = False) -> None:
         """Batch-1 decode step with the residual adds folded into the GEMM prologues (TP = 1, bf16, gammas folded):
         5 launches per layer.
 
@@ -633,10 +638,13 @@ class ModelRunner:
             cur = 1 - cur
             ops.linear(act, lw.w_down, "f32", out=d_parts, splitk=sk_d)
         ops.add_rmsnorm(hs[cur], w.final_norm, self.eps, xn, parts=d_parts, rows=1, write_h=False)
-        self._decode_tail(B, sample, xn, False, guided)
+        self._decode_tail(B, sample, xn, False, guided, logprobs=logprobs)
 
-    def _decode_tail(self, B: int, sample: bool, xn, xf: bool, guided: bool = False, z12: bool = False) -> None:
+    def _decode_tail(self, B: int, sample: bool, xn, xf: bool, guided: bool = False, z12: bool = False,
+                     logprobs: bool = False) -> None:
         logits = self._lm_head(xn, B, xf, z12)
+        if logprobs:  # the raw rows: ahead of the mask and the penalties, which rewrite ``logits`` in place
+            self._logprob_scan(logits, self.lp_k[:B], self.finished[:B], self.gen_len[:B], self.lp_n0[:B])
         if guided:  # -inf into every token that would kill a constrained row's DFA; the commits below run unchanged
             self._dfa_mask(logits, self.gen_len[:B], self.input_ids[:B], self.finished[:B])
         st = (self.out_tokens[:B], self.gen_len[:B], self.input_ids[:B], self.positions[:B], self.finished[:B])
@@ -649,6 +657,9 @@ class ModelRunner:
         else:
             ops.argmax_commit(logits, *st, self.eos, self.limit[:B], self.eos_on[:B],
                               part=self.amax_part if self.on_gpu else None)
+        if logprobs:
+            ops.logprob_commit(self.lp_raw, self.lp_k, self.lp_n0, self.gen_len, self.out_tokens, self.lp_tok,
+                               self.lp_ids, self.lp_top, B, workspace=self.lp_ws)
 
     def final_hidden(self, B: int) -> torch.Tensor:
         """[B, d] bf16: the final-norm output rows of the last decode step (what the lm_head read), in row order
@@ -670,17 +681,23 @@ class ModelRunner:
         return min(b, self.max_slots) if n <= self.max_slots else self.max_slots
 
     @staticmethod
-    def graph_key(B: int, sample: bool, plan: tuple, guided: bool = False) -> tuple:
+    def graph_key(B: int, sample: bool, plan: tuple, guided: bool = False, logprobs: bool = False) -> tuple:
         """Key of a decode graph: (B, sample, plan), and (B, sample, plan, True) for its guided variant (the same step
-        with the ``dfa_mask`` launch between the lm_head and the commit)."""
+        with the ``dfa_mask`` launch between the lm_head and the commit).  The logprob variant of either (two launches
+        more: ``logprob_scan`` after the lm_head, ``logprob_commit`` after the token commit) is (B, sample, plan,
+        guided, "lp"); without the flag every key is what it was."""
+        if logprobs:
+            return (B, sample, plan, bool(guided), "lp")
         return (B, sample, plan, True) if guided else (B, sample, plan)
 
-    def capture(self, B: int, sample: bool, plan: Optional[tuple] = None, guided: bool = False) -> None:
+    def capture(self, B: int, sample: bool, plan: Optional[tuple] = None, guided: bool = False,
+                logprobs: bool = False) -> None:
         """Capture the decode-step graph of (bucket, sampling mode, split plan).  (Several steps per graph were
         measured no faster -- no idle time at graph boundaries, profiles/decode_b32_normfree_spg_ab_mi355x.txt.)"""
         plan = tuple(plan or self.ctx_plan(B))
         assert self.guided or not guided, "guided decode graphs need enable_guided()"
-        key = self.graph_key(B, sample, plan, guided)
+        assert self.logprobs or not logprobs, "logprob decode graphs need enable_logprobs()"
+        key = self.graph_key(B, sample, plan, guided, logprobs)
         if key in self.graphs:
             return
         if self.tp is not None and self.tp.size > 1:
@@ -691,11 +708,11 @@ class ModelRunner:
         with torch.cuda.stream(s):
             # state must not change during capture: kernels are recorded, not executed
             with torch.cuda.graph(g, stream=s):
-                self._decode_step(B, sample, plan, guided)
+                self._decode_step(B, sample, plan, guided, logprobs)
         torch.cuda.current_stream(self.device).wait_stream(s)
         self.graphs[key] = g
 
-    def count_step_kernels(self, B: int, sample: bool = False) -> int:
+    def count_step_kernels(self, B: int, sample: bool = False, logprobs: bool = False) -> int:
         """Kernel launches of one captured decode step of bucket B (a throw-away capture whose graph is kept and
         walked with hipGraphGetNodes): the launch-count check of the fused TP step (tests/test_tp_launches_gpu.py)."""
         import ctypes
@@ -709,7 +726,7 @@ class ModelRunner:
         g = torch.cuda.CUDAGraph(keep_graph=True)
         with torch.cuda.stream(s):
             with torch.cuda.graph(g, stream=s):
-                self._decode_step(B, sample, plan)
+                self._decode_step(B, sample, plan, False, logprobs)
         torch.cuda.current_stream(self.device).wait_stream(s)
         lib = ctypes.CDLL("libamdhip64.so")
         graph = ctypes.c_void_p(g.raw_cuda_graph())
@@ -754,20 +771,25 @@ class ModelRunner:
                     self.capture(b, sm, p)
                     if self.guided:
                         self.capture(b, sm, p, guided=True)
+                    if self.logprobs:
+                        self.capture(b, sm, p, logprobs=True)
+                        if self.guided:
+                            self.capture(b, sm, p, guided=True, logprobs=True)
         torch.cuda.synchronize(self.device)
 
     def decode(self, B: int, steps: int, sample: bool = False, max_ctx: Optional[int] = None,
-               guided: bool = False) -> None:
+               guided: bool = False, logprobs: bool = False) -> None:
         """Run ``steps`` decode steps over slot rows [0, B) (B a bucket size); ``max_ctx`` bounds every
         row's context length during the run (picks the graph planned for that tier).  ``guided``: the variant with
-        the regex mask, for runs in which a row is constrained."""
+        the regex mask, for runs in which a row is constrained; ``logprobs``: the variant that records per-token
+        log-probabilities, for runs in which a row asked (``enable_logprobs``)."""
         plan = tuple(self.ctx_plan(B, max_ctx))
         if not self.use_graphs:
             for _ in range(steps):
-                self._decode_step(B, sample, plan, guided)
+                self._decode_step(B, sample, plan, guided, logprobs)
             return
-        self.capture(B, sample, plan, guided)
-        g = self.graphs[self.graph_key(B, sample, plan, guided)]
+        self.capture(B, sample, plan, guided, logprobs)
+        g = self.graphs[self.graph_key(B, sample, plan, guided, logprobs)]
         for _ in range(steps):
             g.replay()
 
@@ -1154,6 +1176,63 @@ class ModelRunner:
         self.g_base.index_copy_(0, idx, mv[:, 3])
         self.g_dim.index_copy_(0, idx, mv[:, 4:6])
 
+    # ------------------------------------------------------------------------------------ per-token logprobs
+    def enable_logprobs(self) -> None:
+        """Allocate the device side of per-token logprobs (kernels/logprobs.hip), per slot: lp_k (-1 = the row did not
+        ask, else its top_logprobs K), lp_n0 (the record index the step's scan announces, -1 = none), the records
+        lp_tok [S, max_new_cap], lp_ids / lp_top [S, max_new_cap, 20], the raw-row copy lp_raw [S, V] and the chunk
+        workspaces.  ``logprobs_bytes()`` is what it costs."""
+        if self.logprobs:
+            return
+        dev, S, V, cap, K = self.device, self.max_slots, self.V, self.max_new_cap, ops.LOGPROB_KMAX
+        i32 = dict(dtype=torch.int32, device=dev)
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.lp_k = torch.full((S,), -1, **i32)
+        self.lp_n0 = torch.full((S,), -1, **i32)
+        self.lp_tok = torch.zeros(S, cap, **f32)
+        self.lp_ids = torch.full((S, cap, K), -1, **i32)
+        self.lp_top = torch.zeros(S, cap, K, **f32)
+        self.lp_raw = torch.zeros(S, V, **f32)
+        self.lp_ws = ops.logprob_workspace(S, V, dev)
+        self.logprobs = True
+
+    def logprobs_bytes(self) -> int:
+        """Device bytes ``enable_logprobs`` holds (records + raw rows + chunk workspaces)."""
+        if not self.logprobs:
+            return 0
+        ts = (self.lp_k, self.lp_n0, self.lp_tok, self.lp_ids, self.lp_top, self.lp_raw, *self.lp_ws)
+        return sum(t.numel() * t.element_size() for t in ts)
+
+    def _logprob_scan(self, logits, lp_k, finished, gen_len, lp_n0) -> None:
+        ops.logprob_scan(logits, lp_k, finished, gen_len, self.lp_raw, lp_n0, workspace=self.lp_ws)
+
+    def logprobs_of_many(self, slots: Sequence[int], lo: Sequence[int], hi: Sequence[int]) -> list[list[tuple]]:
+        """Records [lo[i], hi[i]) of slot row ``slots[i]`` in one device -> host transfer: per row a list of
+        (logprob, [(token id, logprob)] * K) with K the row's top_logprobs."""
+        if not slots:
+            return []
+        a, m = min(lo), max(hi)
+        if m <= a:
+            return [[] for _ in slots]
+        idx = torch.tensor(list(slots), dtype=torch.long, device=self.device)
+        K = ops.LOGPROB_KMAX
+        pack = torch.cat([self.lp_tok[:, a:m].index_select(0, idx).unsqueeze(-1),
+                          self.lp_top[:, a:m].index_select(0, idx),
+                          self.lp_ids[:, a:m].index_select(0, idx).view(torch.float32)], dim=-1)
+        ks = self.lp_k.index_select(0, idx).view(torch.float32)
+        host = torch.cat([pack.reshape(-1), ks]).cpu()
+        n = len(slots)
+        kh = host[-n:].view(torch.int32).tolist()
+        rec = host[:-n].view(n, m - a, 1 + 2 * K)
+        tok, top = rec[..., 0].tolist(), rec[..., 1:1 + K].tolist()
+        ids = rec[..., 1 + K:].contiguous().view(torch.int32).tolist()
+        out = []
+        for i in range(n):
+            k = max(0, kh[i])
+            out.append([(tok[i][j - a], list(zip(ids[i][j - a][:k], top[i][j - a][:k])))
+                        for j in range(lo[i], hi[i])])
+        return out
+
     # ------------------------------------------------------------------------------------ slots
     def set_slot(self, slot: int, blocks: Sequence[int], limit: int, temperature: float = 0.0, top_k: int = 40,
                  top_p: float = 0.9, seed: int = 0, eos_on: bool = True, repeat_penalty: float = 1.0,
@@ -1238,6 +1317,11 @@ class ModelRunner:
         self.frequency.index_copy_(0, idx, fv[:, 4])
         self.min_p.index_copy_(0, idx, fv[:, 5])
         self.seeds.index_copy_(0, idx, sv)
+        if self.logprobs:  # lp_k per entry: -1 = the request did not ask
+            lk = torch.tensor([int(e.get("lp_k", -1)) for e in entries], dtype=torch.int32)
+            self.lp_k.index_copy_(0, idx, (lk.pin_memory() if self.on_gpu else lk).to(self.device, non_blocking=True))
+        elif any(int(e.get("lp_k", -1)) >= 0 for e in entries):
+            raise RuntimeError("a request asks for logprobs but the runner was built without them")
         if self.guided:
             self._set_guided(entries, idx)
         elif any(e.get("dfa") is not None for e in entries):
@@ -1288,6 +1372,8 @@ class ModelRunner:
         self.finished[slot] = 1
         self.positions[slot] = 0
         self.gen_len[slot] = 0
+        if self.logprobs:
+            self.lp_k[slot] = -1
         self.block_tables[slot].zero_()
 
     # ------------------------------------------------------------------------------------ prefill
@@ -1362,6 +1448,12 @@ class ModelRunner:
         fin = torch.zeros(n, **i32)
         lim = self.limit.index_select(0, slot_t)
         eon = self.eos_on.index_select(0, slot_t)
+        lp = self.logprobs and commit
+        if lp:  # record 0 of every sequence that asked: the same two ops, eagerly, on the gathered rows
+            assert n <= self.max_slots, "one sequence per slot: lp_raw and the chunk workspaces hold max_slots rows"
+            lpk = self.lp_k.index_select(0, slot_t)
+            lpn = torch.full((n,), -1, **i32)
+            self._logprob_scan(logits, lpk, fin, gl, lpn)
         if self.guided and any(sl in self._g_host_on for sl in slots):
             # the first generated token obeys the constraint too: gl = 0 = g_base, so each row reads the start state
             # the admission wrote; the table rows are the sequences' slots
@@ -1379,6 +1471,15 @@ class ModelRunner:
             self.hist.index_copy_(0, slot_t, hist)
         else:
             ops.argmax_commit(logits, out_t, gl, iid, pp, fin, self.eos, lim, eon)
+        if lp:  # every row committed its token 0; the records are one entry wide
+            K = ops.LOGPROB_KMAX
+            t0 = torch.zeros(n, 1, dtype=torch.float32, device=dev)
+            i0 = torch.full((n, 1, K), -1, **i32)
+            p0 = torch.zeros(n, 1, K, dtype=torch.float32, device=dev)
+            ops.logprob_commit(self.lp_raw, lpk, lpn, gl, out_t[:, :1].contiguous(), t0, i0, p0, n, workspace=self.lp_ws)
+            self.lp_tok[:, 0].index_copy_(0, slot_t, t0[:, 0])
+            self.lp_ids[:, 0].index_copy_(0, slot_t, i0[:, 0])
+            self.lp_top[:, 0].index_copy_(0, slot_t, p0[:, 0])
         self.out_tokens.index_copy_(0, slot_t, out_t)
         self.gen_len.index_copy_(0, slot_t, gl)
         self.input_ids.index_copy_(0, slot_t, iid)

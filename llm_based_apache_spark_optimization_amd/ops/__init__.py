@@ -1556,6 +1556,73 @@ def sample_commit(logits, hist, penalty, temperature, top_k, top_p, seeds, out_t
                         gen_len, input_ids, positions, finished, eos, limit, eos_on, presence, frequency, min_p)
 
 
+# ----------------------------------------------------------------------------------- per-token logprobs
+LOGPROB_KMAX = ref.LOGPROB_KMAX
+LOGPROB_CHUNK = 2048
+LOGPROB_CAND = 32
+
+
+def logprob_workspace(B: int, V: int, device) -> tuple:
+    """(lp_ms f32 [B * nch * 2], lp_cand int64 [B * nch * 32]), nch = ceil(V / 2048): what ``logprob_scan`` hands
+    ``logprob_commit`` next to ``lp_raw``."""
+    nch = (V + LOGPROB_CHUNK - 1) // LOGPROB_CHUNK
+    return (torch.empty(B * nch * 2, device=device, dtype=torch.float32),
+            torch.empty(B * nch * LOGPROB_CAND, device=device, dtype=torch.int64))
+
+
+def _logprob_check(op: str, B: int, V: int, tensors: dict, lp_raw) -> None:
+    """The refusals both ops make before any launch (the binding repeats them on the device path)."""
+    if not (B >= 1 and 1 <= V <= ref.LOGPROB_VMAX):
+        raise ValueError(f"{op}: V = {V} outside 1 .. {ref.LOGPROB_VMAX} (the sampler's bound)")
+    for name, (t, dt) in tensors.items():
+        if t.dtype != dt or not t.is_contiguous():
+            raise ValueError(f"{op}: {name} must be a contiguous {dt} tensor")
+    if lp_raw.dim() != 2 or lp_raw.shape[0] < B or lp_raw.shape[1] != V:
+        raise ValueError(f"{op}: lp_raw must be [>= {B}, {V}]")
+
+
+def logprob_scan(logits, lp_k, finished, gen_len, lp_raw, lp_n0, workspace=None):
+    """First half of the per-token logprob record (kernels/logprobs.hip), right after the lm_head and ahead of the
+    regex mask and the penalties: for every row that asked (``lp_k[b] >= 0``) and is not finished, the chunk partials
+    of the raw row's log-sum-exp and its per-chunk best 32 go into ``workspace`` (``logprob_workspace``), the raw row
+    into ``lp_raw[b]`` and ``gen_len[b]`` into ``lp_n0[b]``.  ``logits`` is only read."""
+    if logits.dim() != 2:
+        raise ValueError("logprob_scan: logits must be [B, V]")
+    B, V = logits.shape
+    i32, f32 = torch.int32, torch.float32
+    _logprob_check("logprob_scan", B, V, {"logits": (logits, f32), "lp_k": (lp_k, i32), "finished": (finished, i32),
+                                          "gen_len": (gen_len, i32), "lp_raw": (lp_raw, f32), "lp_n0": (lp_n0, i32)},
+                   lp_raw)
+    if not _gpu(logits):
+        return ref.logprob_scan(logits, lp_k, finished, gen_len, lp_raw, lp_n0)
+    if workspace is None:
+        raise ValueError("logprob_scan: the device path needs the workspace logprob_commit will read")
+    ext().logprob_scan(logits, lp_k, finished, gen_len, lp_raw, workspace[0], workspace[1], lp_n0)
+
+
+def logprob_commit(lp_raw, lp_k, lp_n0, gen_len, out_tokens, lp_tok, lp_ids, lp_top, B: int, workspace=None):
+    """Second half, after the step's token commit: row b < B records ``lp_tok[b, n0]`` (the log-probability of
+    ``out_tokens[b, n0]`` under the raw row's softmax) and its ``lp_k[b]`` most likely tokens into ``lp_ids / lp_top
+    [b, n0, :K]`` exactly when it asked, this step's scan wrote ``lp_n0[b] = n0`` and the commit appended one token
+    (``ops.reference.logprob_commit`` states the rule; ``logprob_rows`` the values)."""
+    i32, f32 = torch.int32, torch.float32
+    V = lp_raw.shape[1] if lp_raw.dim() == 2 else 0
+    _logprob_check("logprob_commit", B, V, {"lp_raw": (lp_raw, f32), "lp_k": (lp_k, i32), "lp_n0": (lp_n0, i32),
+                                            "gen_len": (gen_len, i32), "out_tokens": (out_tokens, i32),
+                                            "lp_tok": (lp_tok, f32), "lp_ids": (lp_ids, i32), "lp_top": (lp_top, f32)},
+                   lp_raw)
+    if lp_ids.dim() != 3 or not 0 <= lp_ids.shape[2] <= LOGPROB_KMAX:
+        raise ValueError(f"logprob_commit: top_logprobs K must be in 0 .. {LOGPROB_KMAX}")
+    if (out_tokens.dim() != 2 or out_tokens.shape[0] < B or lp_tok.shape != out_tokens.shape
+            or lp_ids.shape != lp_top.shape or tuple(lp_ids.shape[:2]) != tuple(out_tokens.shape)):
+        raise ValueError("logprob_commit: record buffers must match out_tokens ([rows, max_new] / [rows, max_new, K])")
+    if not _gpu(lp_raw):
+        return ref.logprob_commit(lp_raw, lp_k, lp_n0, gen_len, out_tokens, lp_tok, lp_ids, lp_top, B)
+    if workspace is None:
+        raise ValueError("logprob_commit: the device path needs logprob_scan's workspace")
+    ext().logprob_commit(lp_raw, workspace[0], workspace[1], lp_k, lp_n0, gen_len, out_tokens, lp_tok, lp_ids, lp_top, B)
+
+
 # ----------------------------------------------------------------------------------- speculative decoding
 def verify_split_plan(Hkv: int, max_ctx: int, S: int = 1) -> tuple[int, int, int]:
     """(chunk_blocks, nsplit, unsplit_max) of ``attn_verify`` over S sequences for contexts (pos0 + T) up to max_ctx:

@@ -278,6 +278,67 @@ def argmax_commit(logits, out_tokens, gen_len, input_ids, positions, finished, e
     commit(logits.float().argmax(-1), out_tokens, gen_len, input_ids, positions, finished, eos, limit, eos_on)
 
 
+# ----------------------------------------------------------------------------------- per-token logprobs
+LOGPROB_KMAX = 20
+LOGPROB_VMAX = 262144
+
+
+def logprob_rows(logits, tok, k: int):
+    """The model's own log-probabilities of rows ``logits`` [R, V]: the float64 log-softmax over the whole row of the
+    logits as given (raw: no mask, penalty or temperature), rounded once to f32.
+
+    -> (lp f32 [R]: that of ``tok[r]``; ids int32 [R, k], top f32 [R, k]: the k most likely tokens by (value
+    descending, index ascending) with theirs; entries beyond V are id -1 and -inf)."""
+    R, V = logits.shape
+    lp = torch.log_softmax(logits.double(), dim=-1)
+    t = torch.as_tensor(tok, dtype=torch.int64, device=logits.device).reshape(R, 1)
+    chosen = lp.gather(1, t).reshape(R).float()
+    ids = torch.full((R, k), -1, dtype=torch.int32, device=logits.device)
+    top = torch.full((R, k), float("-inf"), dtype=torch.float32, device=logits.device)
+    kk = min(k, V)
+    if kk > 0:
+        order = torch.sort(logits.float(), dim=-1, descending=True, stable=True).indices[:, :kk]
+        ids[:, :kk] = order.int()
+        top[:, :kk] = lp.gather(1, order).float()
+    return chosen, ids, top
+
+
+def logprob_scan(logits, lp_k, finished, gen_len, lp_raw, lp_n0):
+    """Host twin of kernels/logprobs.hip logprob_scan_kernel (state level): a row b that asked (``lp_k[b] >= 0``) and
+    is not finished keeps its raw row in ``lp_raw[b]`` and n0 = gen_len[b] in ``lp_n0[b]``; a finished row that asked
+    gets ``lp_n0[b] = -1`` (no record this step); a row that did not ask is left alone.  ``logits`` is not modified."""
+    for b in range(logits.shape[0]):
+        if int(lp_k[b]) < 0:
+            continue
+        if int(finished[b]) != 0:
+            lp_n0[b] = -1
+            continue
+        lp_raw[b].copy_(logits[b])
+        lp_n0[b] = int(gen_len[b])
+
+
+def logprob_commit(lp_raw, lp_k, lp_n0, gen_len, out_tokens, lp_tok, lp_ids, lp_top, B: int):
+    """Host twin of logprob_commit_kernel, after the token commit of the step.  Row b records exactly when it asked,
+    ``lp_n0[b]`` was written by this step's scan (>= 0; it is consumed: set to -1) and ``gen_len[b] == n0 + 1``, at
+    index n0 < max_new: ``lp_tok[b, n0]`` and, for K = min(lp_k[b], lp_ids.shape[2]) > 0, ``lp_ids / lp_top[b, n0, :K]``
+    (``logprob_rows`` of the raw row and ``out_tokens[b, n0]``).  Nothing else is written."""
+    max_new = out_tokens.shape[1]
+    for b in range(B):
+        K = int(lp_k[b])
+        n0 = int(lp_n0[b])
+        if K < 0 or n0 < 0:
+            continue
+        lp_n0[b] = -1
+        if int(gen_len[b]) != n0 + 1 or n0 >= max_new:
+            continue
+        K = min(K, lp_ids.shape[2])
+        chosen, ids, top = logprob_rows(lp_raw[b:b + 1], out_tokens[b:b + 1, n0], K)
+        lp_tok[b, n0] = chosen[0]
+        if K > 0:
+            lp_ids[b, n0, :K] = ids[0]
+            lp_top[b, n0, :K] = top[0]
+
+
 # ----------------------------------------------------------------------------------- regex-constrained decoding
 DFA_DEAD = 0xFFFF
 DFA_MAX_TABLE = 32768

@@ -163,11 +163,14 @@ def _worker(conn, replica: int, devices: str, kind: str, settings_kw: dict, hear
             os._exit(3)
         try:
             if stream:
+                lps = None  # per-token logprob entries of the chunks: they travel whole with the final chunk
                 for c in backend.generate_stream(model, prompt, system, options, raw):
+                    if c.logprobs is not None:
+                        lps = (lps or []) + list(c.logprobs)
                     if not c.done:
                         send(("piece", rid, c.response))
                     else:
-                        send(("ok", rid, c.to_dict()))
+                        send(("ok", rid, c.to_dict() if lps is None else dict(c.to_dict(), logprobs=lps)))
             else:
                 r = backend.generate(model, prompt, system, options, raw)
                 send(("ok", rid, r.to_dict()))

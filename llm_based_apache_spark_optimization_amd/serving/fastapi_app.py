@@ -35,7 +35,7 @@ from ..engine.engine import SamplingOptionError
 from ..engine.guided import GuidedRequestError
 from ..utils.metrics import REGISTRY, record_generation
 from ..utils.tracing import new_request_id
-from .pipeline import resolve_input
+from .pipeline import resolve_input, sql_logprob_summary
 from .service import AppContext, make_context
 
 
@@ -65,6 +65,15 @@ class GenerateRequest(BaseModel):
     options: Optional[dict] = None
     stream: bool = False
     raw: bool = False
+    # per-token logprobs: Ollama's top-level request fields (also accepted inside ``options``)
+    logprobs: Optional[bool] = None
+    top_logprobs: Optional[int] = None
+
+    def merged_options(self) -> Optional[dict]:
+        if self.logprobs is None and self.top_logprobs is None:
+            return self.options
+        top = {k: v for k, v in (("logprobs", self.logprobs), ("top_logprobs", self.top_logprobs)) if v is not None}
+        return dict(self.options or {}, **top)
 
 
 def create_app(ctx: Optional[AppContext] = None) -> FastAPI:
@@ -108,13 +117,16 @@ def create_app(ctx: Optional[AppContext] = None) -> FastAPI:
             REGISTRY.inc("lsa_requests_total", 1, "requests", route="process-data", outcome="sql_error")
             return {"error": "SQL execution failed", "sql_query": res.sql_query, "error_details": res.explanation}
         REGISTRY.inc("lsa_requests_total", 1, "requests", route="process-data", outcome="ok")
-        return {
+        body = {
             "message": "Query executed successfully!",
             "input_file_name": data.file_name,
             "input_data": data.input_text,
             "sql_query": res.sql_query,
             "output_file": res.output_file,
         }
+        if res.sql_mean_logprob is not None:  # Settings.sql_logprobs only
+            body.update(sql_mean_logprob=res.sql_mean_logprob, sql_min_logprob=res.sql_min_logprob)
+        return body
 
     @app.post("/nl2sql")
     def nl2sql(req: NL2SQLRequest):
@@ -138,9 +150,12 @@ def create_app(ctx: Optional[AppContext] = None) -> FastAPI:
         dt = time.perf_counter() - t0
         REGISTRY.observe("lsa_request_seconds", dt, "e2e latency", route="nl2sql")
         REGISTRY.inc("lsa_requests_total", 1, "requests", route="nl2sql", outcome="ok")
-        return {"sql_query": r.response, "model": r.model, "request_id": rid, "table_schema": schema,
+        body = {"sql_query": r.response, "model": r.model, "request_id": rid, "table_schema": schema,
                 "eval_count": r.eval_count, "eval_duration": r.eval_duration,
                 "prompt_eval_count": r.prompt_eval_count, "total_duration": r.total_duration, "latency_s": dt}
+        if getattr(s, "sql_logprobs", False):  # (unset: the body is key for key what it was)
+            body.update(sql_logprob_summary(r) or {})
+        return body
 
     @app.post("/explain_error")
     def explain_error(req: ExplainRequest):
@@ -157,7 +172,7 @@ def create_app(ctx: Optional[AppContext] = None) -> FastAPI:
     @app.post("/api/generate")
     def api_generate(req: GenerateRequest):
         if req.stream:  # Ollama's NDJSON framing: response pieces as decoded, then the done chunk
-            chunks = ctx.backend.generate_stream(req.model, req.prompt, req.system, req.options, req.raw)
+            chunks = ctx.backend.generate_stream(req.model, req.prompt, req.system, req.merged_options(), req.raw)
 
             def ndjson():
                 for c in chunks:
@@ -165,7 +180,7 @@ def create_app(ctx: Optional[AppContext] = None) -> FastAPI:
                         record_generation(c, "api_generate")
                     yield json.dumps(c.to_dict()) + "\n"
             return StreamingResponse(ndjson(), media_type="application/x-ndjson")
-        r = ctx.backend.generate(req.model, req.prompt, req.system, req.options, req.raw)
+        r = ctx.backend.generate(req.model, req.prompt, req.system, req.merged_options(), req.raw)
         record_generation(r, "api_generate")
         return r.to_dict()
 

@@ -78,6 +78,17 @@ class JobResult:
     error_message: str = ""
     explanation: str = ""
     timings: dict = dataclasses.field(default_factory=dict)
+    # Settings.sql_logprobs: mean / smallest token log-probability of the generated statement (None: not asked)
+    sql_mean_logprob: Optional[float] = None
+    sql_min_logprob: Optional[float] = None
+
+
+def sql_logprob_summary(res) -> Optional[dict]:
+    """{"sql_mean_logprob", "sql_min_logprob"} of a generation that carries per-token logprobs, else None."""
+    lps = [float(e["logprob"]) for e in (res.get("logprobs") or [])]
+    if not lps:
+        return None
+    return {"sql_mean_logprob": sum(lps) / len(lps), "sql_min_logprob": min(lps)}
 
 
 def timestamp() -> str:
@@ -123,12 +134,18 @@ class Pipeline:
                 and not getattr(settings, "guided", False)):
             raise ValueError("sql_guided needs guided (LSA_GUIDED=1): the engines must be built with regex-constrained "
                              "decoding")
+        if (getattr(settings, "sql_logprobs", False) and getattr(settings, "engine", "") == "hip"
+                and not getattr(settings, "logprobs", False)):
+            raise ValueError("sql_logprobs needs logprobs (LSA_LOGPROBS=1): the engines must be built with per-token "
+                             "logprobs")
 
     # ------------------------------------------------------------------------------- LLM calls
     def nl2sql(self, table_schema: str, question: str, options: Optional[dict] = None, rid: str = ""):
         if getattr(self.settings, "sql_guided", False) and not (options or {}).get("regex"):
             # constrain the answer to one SELECT / WITH statement that stops at its ';' (the prompt is unchanged)
             options = dict(options or {}, regex=prompts.SQL_STATEMENT_REGEX)
+        if getattr(self.settings, "sql_logprobs", False) and not (options or {}).get("logprobs"):
+            options = dict(options or {}, logprobs=True)  # how sure the model was of its statement
         with span("nl2sql", rid):
             res = self.backend.generate(self.settings.nl2sql_model, question,
                                         system=prompts.nl2sql_system(table_schema), options=options)
@@ -158,7 +175,11 @@ class Pipeline:
                 table = self.executor.table_of(loaded)
             out.table_schema = prompts.table_schema_text(table.dtypes)
             st(ST_GEN)
-            out.sql_query = self.nl2sql(out.table_schema, input_text, options, rid).response
+            gen = self.nl2sql(out.table_schema, input_text, options, rid)
+            out.sql_query = gen.response
+            if getattr(self.settings, "sql_logprobs", False):
+                for k, v in (sql_logprob_summary(gen) or {}).items():
+                    setattr(out, k, v)
             st(ST_GEN_OK)
             st(ST_EXEC)
             with span("sql", rid):

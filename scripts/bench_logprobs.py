@@ -1,0 +1,202 @@
+#!/usr/bin/env python
+"""Device time of per-token logprobs: the two kernels standalone (``logprob_scan``, ``logprob_commit``) and the
+captured decode step with and without the logprob variant, at V = 32000 (duckdb-nsql) and 128256 (llama3.2), B = 1 and
+32, K = 0 and 20.
+
+  python scripts/bench_logprobs.py --out profiles/logprobs/logprobs_mi355x.jsonl [--no-steps] [--table]
+
+Each window is ITERS launches (or graph replays) between two device events; the arms of a shape are alternated window
+by window in one process; a row reports the median window and its spread (min, max) in microseconds per launch.
+Scan rows also report the bytes the scan moves (it reads V * 4 and writes V * 4 per row) over its median time, as a
+share of ``--hbm-gbs`` (the MI355X's 8 TB/s by default).  The cost is reported, not gated.  ``--table`` prints the README table
+from the rows of ``--out`` instead of measuring."""
+import argparse
+import json
+import statistics
+import sys
+
+import torch
+
+from llm_based_apache_spark_optimization_amd import ops
+
+
+def timed(run, iters):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(iters):
+        run()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) * 1000.0 / iters
+
+
+def alternate(arms, iters, windows, reset=None):
+    """arms: name -> callable; -> name -> list of us per launch, the arms taking turns window by window."""
+    for run in arms.values():
+        if reset:
+            reset()
+        timed(run, max(4, iters // 10))
+    times = {k: [] for k in arms}
+    for _ in range(windows):
+        for k, run in arms.items():
+            if reset:
+                reset()
+            times[k].append(timed(run, iters))
+    return times
+
+
+def row_of(ts, **kw):
+    return dict(kw, us_median=round(statistics.median(ts), 3), us_min=round(min(ts), 3), us_max=round(max(ts), 3),
+                windows=len(ts))
+
+
+def kernels(V, B, dev, iters, windows, hbm_gbs):
+    """The two launches standalone.  Arms: every row asks with K = 0 / K = 20, and no row asks (the early return)."""
+    g = torch.Generator().manual_seed(V + B)
+    logits = (torch.randn(B, V, generator=g) * 2).to(dev)
+    i32 = dict(dtype=torch.int32, device=dev)
+    max_new = 8
+    st = dict(gen_len=torch.zeros(B, **i32), finished=torch.zeros(B, **i32), out_tokens=torch.zeros(B, max_new, **i32),
+              lp_n0=torch.full((B,), -1, **i32), lp_tok=torch.zeros(B, max_new, device=dev),
+              lp_ids=torch.zeros(B, max_new, ops.LOGPROB_KMAX, **i32),
+              lp_top=torch.zeros(B, max_new, ops.LOGPROB_KMAX, device=dev), lp_raw=torch.zeros(B, V, device=dev))
+    ws = ops.logprob_workspace(B, V, dev)
+    ks = {"k0": torch.zeros(B, **i32), "k20": torch.full((B,), 20, **i32), "off": torch.full((B,), -1, **i32)}
+    ones = torch.ones(B, **i32)
+    rows = []
+
+    def scan(k):
+        return lambda: ops.logprob_scan(logits, ks[k], st["finished"], st["gen_len"], st["lp_raw"], st["lp_n0"],
+                                        workspace=ws)
+
+    t = alternate({k: scan(k) for k in ks}, iters, windows)
+    for k, ts in t.items():
+        r = row_of(ts, what="logprob_scan", V=V, B=B, case=k, iters=iters)
+        if k != "off":
+            r["bytes"] = 2 * 4 * V * B
+            r["hbm_share"] = round(r["bytes"] / (r["us_median"] * 1e-6) / (hbm_gbs * 1e9), 4)
+        rows.append(r)
+
+    # the commit records only after a scan of the same step: each timed launch is preceded, outside the timing of the
+    # other arm, by a state that makes it record -- lp_n0 = 0 and gen_len = 1 are restored by a tiny copy per launch,
+    # measured alone as the arm "restore" and subtracted by the reader
+    ops.logprob_scan(logits, ks["k20"], st["finished"], st["gen_len"], st["lp_raw"], st["lp_n0"], workspace=ws)
+    zeros = torch.zeros(B, **i32)
+
+    def commit(k):
+        def run():
+            st["lp_n0"].copy_(zeros)
+            ops.logprob_commit(st["lp_raw"], ks[k], st["lp_n0"], ones, st["out_tokens"], st["lp_tok"], st["lp_ids"],
+                               st["lp_top"], B, workspace=ws)
+        return run
+
+    arms = {k: commit(k) for k in ks}
+    arms["restore"] = lambda: st["lp_n0"].copy_(zeros)
+    t = alternate(arms, iters, windows)
+    base = statistics.median(t["restore"])
+    for k, ts in t.items():
+        r = row_of(ts, what="logprob_commit" if k != "restore" else "restore_copy", V=V, B=B, case=k, iters=iters)
+        if k != "restore":
+            r["us_median_less_restore"] = round(r["us_median"] - base, 3)
+        rows.append(r)
+    return rows
+
+
+def steps(model, B, dev, iters, windows):
+    """The captured decode step of ``model`` over B running rows: the plain graph, and the logprob variant with no row
+    asking, with every row asking K = 0, and K = 20."""
+    from llm_based_apache_spark_optimization_amd.engine import SamplingParams, build_engine
+
+    arms = ("plain", "lp_off", "lp_k0", "lp_k20")
+    budget = iters + 64
+    eng = build_engine(model, device=dev, max_slots=B, max_model_len=budget + 64, kv_reserve_tokens=-1, logprobs=True)
+    r = eng.runner
+    sp = SamplingParams(max_tokens=budget, ignore_eos=True, logprobs=True, top_logprobs=20)
+    for i in range(B):
+        eng.add_request([1] + list(range(10 + i, 26 + i)), sp)
+    eng.run_ahead = 1
+    eng.step()  # admission, prefill and one decode step; the rows keep running
+    assert eng.sched.num_running == B
+    i32 = dict(dtype=torch.int32, device=dev)
+    ks = {"lp_off": torch.full((B,), -1, **i32), "lp_k0": torch.zeros(B, **i32), "lp_k20": torch.full((B,), 20, **i32)}
+    max_ctx = budget + 32
+    # every window decodes the same ``iters`` steps from the same state (a later window would otherwise attend to a
+    # longer context than an earlier one): the decode state is put back before each
+    state = (r.gen_len, r.positions, r.input_ids, r.finished)
+    snap = [t.clone() for t in state]
+
+    def restore():
+        for t, s0 in zip(state, snap):
+            t.copy_(s0)
+
+    def arm(name):
+        def run():
+            r.decode(B, 1, False, max_ctx=max_ctx, logprobs=name != "plain")
+        return run
+
+    runs = {name: arm(name) for name in arms}
+    times = {k: [] for k in arms}
+    for w in range(windows + 1):  # window 0 warms every graph up
+        for name in arms:
+            restore()
+            if name != "plain":
+                r.lp_k[:B].copy_(ks[name])
+            t = timed(runs[name], iters)
+            if w:
+                times[name].append(t)
+    V = r.V
+    out = [row_of(ts, what="decode_step", model=model, V=V, B=B, case=k, iters=iters) for k, ts in times.items()]
+    eng.abort_all("measurement over")
+    del eng, r
+    torch.cuda.empty_cache()
+    return out
+
+
+def table(path):
+    rows = [json.loads(x) for x in open(path)]
+    print("| what | V | B | case | us median (min .. max) |")
+    print("|---|---|---|---|---|")
+    for r in rows:
+        extra = f", {100 * r['hbm_share']:.1f} % of HBM" if "hbm_share" in r else ""
+        print(f"| {r['what']} | {r['V']} | {r['B']} | {r['case']} | {r['us_median']} ({r['us_min']} .. {r['us_max']})"
+              f"{extra} |")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--iters", type=int, default=200)
+    ap.add_argument("--step-iters", type=int, default=100)
+    ap.add_argument("--windows", type=int, default=9)
+    ap.add_argument("--hbm-gbs", type=float, default=8000.0)
+    ap.add_argument("--no-steps", action="store_true")
+    ap.add_argument("--no-kernels", action="store_true")
+    ap.add_argument("--table", action="store_true")
+    args = ap.parse_args()
+    if args.table:
+        table(args.out)
+        return 0
+    if not torch.cuda.is_available():
+        print("needs a GPU", file=sys.stderr)
+        return 2
+    dev = "cuda:0"
+    with open(args.out, "a") as out:
+        def emit(rows):
+            for r in rows:
+                print(json.dumps(r), flush=True)
+                out.write(json.dumps(r) + "\n")
+            out.flush()
+
+        if not args.no_kernels:
+            for V in (32000, 128256):
+                for B in (1, 32):
+                    emit(kernels(V, B, dev, args.iters, args.windows, args.hbm_gbs))
+        if not args.no_steps:
+            for model in ("duckdb-nsql", "llama3.2"):
+                for B in (1, 32):
+                    emit(steps(model, B, dev, args.step_iters, args.windows))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
