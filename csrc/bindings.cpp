@@ -69,6 +69,13 @@ int lsa_logprob_scan(const float* logits, int B, int V, const int* lp_k, const i
 int lsa_logprob_commit(const float* lp_raw, int B, int V, const float* lp_ms, const unsigned long long* lp_cand,
                        const int* lp_k, int* lp_n0, const int* gen_len, const int* out_tokens, int max_new, float* lp_tok,
                        int* lp_ids, float* lp_top, int kcap, hipStream_t s);
+int lsa_spec_logprob_scan(const float* logits, int S, int T, int V, const int* lp_k, const int* finished,
+                          const int* gen_len, float* sp_raw, float* sp_ms, unsigned long long* sp_cand, int* lp_n0,
+                          hipStream_t st);
+int lsa_spec_logprob_commit(const float* sp_raw, int S, int T, int V, const float* sp_ms,
+                            const unsigned long long* sp_cand, const int* lp_k, const int* lp_n0, const int* gen_len,
+                            const int* out_tokens, int max_new, float* lp_tok, int* lp_ids, float* lp_top, int kcap,
+                            hipStream_t st);
 int lsa_dfa_mask(float* logits, int B, int V, const int* tok_off, const uint8_t* tok_blob, const uint8_t* cls,
                  const uint16_t* trans, const uint8_t* accept, const int* g_dim, const int* g_on, int* g_state,
                  const int* g_base, const int* rows, const int* gen_len, const int* input_ids, const int* finished,
@@ -1131,6 +1138,72 @@ void logprob_commit(const at::Tensor& lp_raw, const at::Tensor& lp_ms, const at:
         "logprob_commit");
 }
 
+// the verify-step pair (spec_logprobs): S = lp_k.numel() sequences of T rows; the spec-side workspace sp_raw f32 [32, V],
+// sp_ms, sp_cand holds 32 rows whatever S * T is.  S / T / S * T are refused here and in the launcher.
+void check_spec_logprob(const char* op, int64_t S, int64_t T, int64_t V, const at::Tensor& lp_k,
+                        const at::Tensor& lp_n0, const at::Tensor& gen_len, const at::Tensor& sp_raw,
+                        const at::Tensor& sp_ms, const at::Tensor& sp_cand) {
+  TORCH_CHECK(T >= 1 && T <= 8 && S >= 1 && S <= 8 && S * T <= 32, op, ": 1 <= T <= 8, 1 <= S <= 8, S * T <= 32");
+  TORCH_CHECK(V >= 1 && V <= 262144, op, ": 1 <= V <= 262144 (the sampler's bound)");
+  for (const at::Tensor* t : {&lp_k, &lp_n0, &gen_len}) {
+    need(*t, at::kInt, "logprob state operand");
+    TORCH_CHECK(t->is_contiguous() && t->numel() >= S, op, ": lp_k / lp_n0 / gen_len contiguous int32 [>= S]");
+  }
+  need(sp_raw, at::kFloat, "spec raw rows");
+  need(sp_ms, at::kFloat, "spec lp_ms");
+  need(sp_cand, at::kLong, "spec lp_cand");
+  TORCH_CHECK(sp_raw.dim() == 2 && sp_raw.size(0) >= 32 && sp_raw.size(1) == V && sp_raw.is_contiguous(), op,
+              ": raw rows contiguous f32 [>= 32, V]");
+  const int64_t nch = (V + 2047) / 2048;
+  TORCH_CHECK(sp_ms.is_contiguous() && sp_cand.is_contiguous() && sp_ms.numel() >= 32 * nch * 2 &&
+                  sp_cand.numel() >= 32 * nch * 32,
+              op, ": chunk workspaces too small (32 rows)");
+}
+
+void spec_logprob_scan(const at::Tensor& logits, int64_t T, const at::Tensor& lp_k, const at::Tensor& finished,
+                       const at::Tensor& gen_len, at::Tensor& sp_raw, at::Tensor& sp_ms, at::Tensor& sp_cand,
+                       at::Tensor& lp_n0) {
+  need(logits, at::kFloat, "logits");
+  TORCH_CHECK(logits.dim() == 2 && logits.is_contiguous(), "spec_logprob_scan: logits contiguous [S * T, V]");
+  const int64_t S = lp_k.numel(), V = logits.size(1);
+  check_spec_logprob("spec_logprob_scan", S, T, V, lp_k, lp_n0, gen_len, sp_raw, sp_ms, sp_cand);
+  TORCH_CHECK(logits.size(0) == S * T, "spec_logprob_scan: logits must have S * T rows");
+  need(finished, at::kInt, "finished");
+  TORCH_CHECK(finished.is_contiguous() && finished.numel() >= S, "spec_logprob_scan: finished contiguous int32 [>= S]");
+  check(lsa_spec_logprob_scan(logits.data_ptr<float>(), (int)S, (int)T, (int)V, lp_k.data_ptr<int>(),
+                              finished.data_ptr<int>(), gen_len.data_ptr<int>(), sp_raw.data_ptr<float>(),
+                              sp_ms.data_ptr<float>(), reinterpret_cast<unsigned long long*>(sp_cand.data_ptr()),
+                              lp_n0.data_ptr<int>(), cur_stream()),
+        "spec_logprob_scan");
+}
+
+// records as logprob_commit's, rows >= S (the per-slot record tensors: sequence s is slot s)
+void spec_logprob_commit(int64_t T, const at::Tensor& sp_raw, const at::Tensor& sp_ms, const at::Tensor& sp_cand,
+                         const at::Tensor& lp_k, const at::Tensor& lp_n0, const at::Tensor& gen_len,
+                         const at::Tensor& out_tokens, at::Tensor& lp_tok, at::Tensor& lp_ids, at::Tensor& lp_top) {
+  TORCH_CHECK(sp_raw.dim() == 2, "spec_logprob_commit: raw rows [32, V]");
+  const int64_t S = lp_k.numel(), V = sp_raw.size(1);
+  check_spec_logprob("spec_logprob_commit", S, T, V, lp_k, lp_n0, gen_len, sp_raw, sp_ms, sp_cand);
+  need(out_tokens, at::kInt, "out_tokens");
+  need(lp_tok, at::kFloat, "lp_tok");
+  need(lp_ids, at::kInt, "lp_ids");
+  need(lp_top, at::kFloat, "lp_top");
+  TORCH_CHECK(out_tokens.dim() == 2 && out_tokens.size(0) >= S && out_tokens.size(1) >= 1 && out_tokens.is_contiguous(),
+              "spec_logprob_commit: out_tokens contiguous [>= S, max_new]");
+  TORCH_CHECK(lp_tok.sizes() == out_tokens.sizes() && lp_tok.is_contiguous(),
+              "spec_logprob_commit: lp_tok must have out_tokens' shape");
+  TORCH_CHECK(lp_ids.dim() == 3 && lp_ids.sizes() == lp_top.sizes() && lp_ids.size(0) == out_tokens.size(0) &&
+                  lp_ids.size(1) == out_tokens.size(1) && lp_ids.is_contiguous() && lp_top.is_contiguous(),
+              "spec_logprob_commit: lp_ids / lp_top contiguous [rows, max_new, K] over out_tokens' rows");
+  TORCH_CHECK(lp_ids.size(2) >= 0 && lp_ids.size(2) <= 20, "spec_logprob_commit: top_logprobs K must be in 0 .. 20");
+  check(lsa_spec_logprob_commit(sp_raw.data_ptr<float>(), (int)S, (int)T, (int)V, sp_ms.data_ptr<float>(),
+                                reinterpret_cast<const unsigned long long*>(sp_cand.data_ptr()), lp_k.data_ptr<int>(),
+                                lp_n0.data_ptr<int>(), gen_len.data_ptr<int>(), out_tokens.data_ptr<int>(),
+                                (int)out_tokens.size(1), lp_tok.data_ptr<float>(), lp_ids.data_ptr<int>(),
+                                lp_top.data_ptr<float>(), (int)lp_ids.size(2), cur_stream()),
+        "spec_logprob_commit");
+}
+
 // regex-constrained decoding: -inf into every logit whose token would kill the row's DFA (kernels/guided.hip).
 // Table rows are indexed by rows[b] when given (prefill tail: the sequence's slot), else by b.
 void dfa_mask(at::Tensor& logits, const at::Tensor& tok_off, const at::Tensor& tok_blob, const at::Tensor& cls,
@@ -1608,6 +1681,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("logprob_commit", &logprob_commit, py::arg("lp_raw"), py::arg("lp_ms"), py::arg("lp_cand"), py::arg("lp_k"),
         py::arg("lp_n0"), py::arg("gen_len"), py::arg("out_tokens"), py::arg("lp_tok"), py::arg("lp_ids"),
         py::arg("lp_top"), py::arg("B"));
+  m.def("spec_logprob_scan", &spec_logprob_scan, py::arg("logits"), py::arg("T"), py::arg("lp_k"), py::arg("finished"),
+        py::arg("gen_len"), py::arg("sp_raw"), py::arg("sp_ms"), py::arg("sp_cand"), py::arg("lp_n0"));
+  m.def("spec_logprob_commit", &spec_logprob_commit, py::arg("T"), py::arg("sp_raw"), py::arg("sp_ms"),
+        py::arg("sp_cand"), py::arg("lp_k"), py::arg("lp_n0"), py::arg("gen_len"), py::arg("out_tokens"),
+        py::arg("lp_tok"), py::arg("lp_ids"), py::arg("lp_top"));
   m.def("dfa_mask", &dfa_mask, py::arg("logits"), py::arg("tok_off"), py::arg("tok_blob"), py::arg("cls"),
         py::arg("trans"), py::arg("accept"), py::arg("g_dim"), py::arg("g_on"), py::arg("g_state"), py::arg("g_base"),
         py::arg("rows"), py::arg("gen_len"), py::arg("input_ids"), py::arg("finished"), py::arg("eos"));

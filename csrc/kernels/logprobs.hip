@@ -19,7 +19,26 @@
 //                       all 4096), lp_ids[b, n0, j] and lp_top[b, n0, j] = l_j - lse -- the expression of the chosen
 //                       token, so the two are bitwise equal when it is among them.  j >= V: id -1, -inf.  Nothing is
 //                       written at n0 >= max_new.
-// Plain vector stores only.  ops/reference.py logprob_scan / logprob_commit are the host twins.
+//
+// The verify step of speculative decoding (S sequences of T rows, S * T <= 32; ``spec_logprobs``) runs the same two
+// bodies (lp_scan_chunk, lp_commit_row: one expression per value, so a verify row records bit for bit what the plain
+// pair records for the same row values and token) over its own 32-row raw buffer and chunk workspace:
+//
+//   lsa_spec_logprob_scan    grid (ceil(V / 2048), T, S), after the verify lm_head and ahead of dfa_mask_verify and the
+//                            verify commit.  Sequence s = blockIdx.z, row r = s T + blockIdx.y.  lp_k[s] < 0: return;
+//                            finished[s]: workgroup (0, 0, s) stores lp_n0[s] = -1, all return; else the plain scan of
+//                            row r into the spec-side buffers, and workgroup (0, 0, s) stores lp_n0[s] = gen_len[s].
+//   lsa_spec_logprob_commit  grid (T, S), after spec_commit / spec_sample_commit and dfa_spec_advance.  Workgroup
+//                            (t, s): K = lp_k[s], n0 = lp_n0[s], c = gen_len[s] - n0 (the tokens this step committed
+//                            into s, 0 .. T, already cut by EOS / limit).  It records exactly when K >= 0, n0 >= 0,
+//                            t < c and n0 + t < max_new: index n0 + t from row s T + t and out_tokens[s, n0 + t] (row
+//                            t is the distribution of generated token n0 + t), straight into the per-slot records.
+//
+// Invariant: the verify commit does NOT consume lp_n0[s] -- T workgroups read it, and no workgroup reads a word another
+// workgroup of its launch writes.  It need not: every step in which a row asks rewrites lp_n0 in its scan (n0, or -1
+// for a finished row), the verify scan and the plain scan alike.  The plain commit's own consume is unaffected.
+// Plain vector stores only.  ops/reference.py logprob_scan / logprob_commit / spec_logprob_scan / spec_logprob_commit
+// are the host twins.
 #include "common.h"
 
 #define LP_CHUNK 2048
@@ -39,22 +58,13 @@ __device__ __forceinline__ unsigned long long lp_block_max_u64(unsigned long lon
   return lsa_umax64(lsa_umax64(red[0], red[1]), lsa_umax64(red[2], red[3]));
 }
 
-__global__ __launch_bounds__(256) void logprob_scan_kernel(const float* __restrict__ logits, int V, int vec,
-                                                           const int* __restrict__ lp_k,
-                                                           const int* __restrict__ finished,
-                                                           const int* __restrict__ gen_len, float* __restrict__ lp_raw,
-                                                           float* __restrict__ lp_ms,
-                                                           unsigned long long* __restrict__ lp_cand,
-                                                           int* __restrict__ lp_n0, int nch) {
-  const int c = blockIdx.x, b = blockIdx.y;
-  if (lp_k[b] < 0) return;
+// One chunk of one raw row, the body of both scan kernels: chunk c of ``row`` (V words) is read ONCE into registers and
+// copied into ``raw``; (m_c, s_c) goes to ms[0 .. 1] and the chunk's best LP_CAND packed keys to out[0 .. 31].  The one
+// workgroup that announces the record index gets n0_dst (else nullptr): *n0_dst = *n0_src, the gen_len before the commit.
+__device__ __forceinline__ void lp_scan_chunk(const float* __restrict__ row, float* __restrict__ raw, int V, int vec,
+                                              int c, float* __restrict__ ms, unsigned long long* __restrict__ out,
+                                              int* __restrict__ n0_dst, const int* __restrict__ n0_src) {
   const int t = threadIdx.x;
-  if (finished[b]) {  // no record this step, whatever an earlier step left in lp_n0
-    if (c == 0 && t == 0) lp_n0[b] = -1;
-    return;
-  }
-  const float* row = logits + (size_t)b * V;
-  float* raw = lp_raw + (size_t)b * V;
   const int lo = c * LP_CHUNK;
   // element j of this thread: lo + 1024 * (j / 4) + 4 * t + j % 4 (two 16-byte accesses per thread when rows are aligned)
   float v[8];
@@ -95,16 +105,14 @@ __global__ __launch_bounds__(256) void logprob_scan_kernel(const float* __restri
   if ((t & 63) == 0) fred[4 + (t >> 6)] = s;
   __syncthreads();
   if (t == 0) {
-    float* ms = lp_ms + ((size_t)b * nch + c) * 2;
     ms[0] = m;
     ms[1] = (fred[4] + fred[5]) + (fred[6] + fred[7]);
-    if (c == 0) lp_n0[b] = gen_len[b];
+    if (n0_dst != nullptr) *n0_dst = *n0_src;
   }
   // the chunk's best LP_CAND keys: LP_CAND rounds of a block-wide max, the winner knocked out of its owner's registers
   unsigned long long key[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) key[j] = idx[j] < V ? lp_pack_key(v[j], idx[j]) : 0ull;
-  unsigned long long* out = lp_cand + ((size_t)b * nch + c) * LP_CAND;
   for (int r = 0; r < LP_CAND; ++r) {
     unsigned long long best = key[0];
 #pragma unroll
@@ -113,6 +121,92 @@ __global__ __launch_bounds__(256) void logprob_scan_kernel(const float* __restri
     if (t == 0) out[r] = best;
 #pragma unroll
     for (int j = 0; j < 8; ++j) key[j] = key[j] == best ? 0ull : key[j];
+  }
+}
+
+__global__ __launch_bounds__(256) void logprob_scan_kernel(const float* __restrict__ logits, int V, int vec,
+                                                           const int* __restrict__ lp_k,
+                                                           const int* __restrict__ finished,
+                                                           const int* __restrict__ gen_len, float* __restrict__ lp_raw,
+                                                           float* __restrict__ lp_ms,
+                                                           unsigned long long* __restrict__ lp_cand,
+                                                           int* __restrict__ lp_n0, int nch) {
+  const int c = blockIdx.x, b = blockIdx.y;
+  if (lp_k[b] < 0) return;
+  if (finished[b]) {  // no record this step, whatever an earlier step left in lp_n0
+    if (c == 0 && threadIdx.x == 0) lp_n0[b] = -1;
+    return;
+  }
+  lp_scan_chunk(logits + (size_t)b * V, lp_raw + (size_t)b * V, V, vec, c, lp_ms + ((size_t)b * nch + c) * 2,
+                lp_cand + ((size_t)b * nch + c) * LP_CAND, c == 0 ? lp_n0 + b : nullptr, gen_len + b);
+}
+
+// The verify-step scan: sequence s = blockIdx.z, verify row r = s * T + blockIdx.y of logits [S * T, V]; the raw rows and
+// the chunk partials go into the spec-side buffers of 32 rows (sp_raw [32, V], sp_ms, sp_cand), indexed by r.
+__global__ __launch_bounds__(256) void spec_logprob_scan_kernel(const float* __restrict__ logits, int V, int vec, int T,
+                                                                const int* __restrict__ lp_k,
+                                                                const int* __restrict__ finished,
+                                                                const int* __restrict__ gen_len,
+                                                                float* __restrict__ sp_raw, float* __restrict__ sp_ms,
+                                                                unsigned long long* __restrict__ sp_cand,
+                                                                int* __restrict__ lp_n0, int nch) {
+  const int c = blockIdx.x, s = blockIdx.z;
+  if (lp_k[s] < 0) return;
+  if (finished[s]) {
+    if (c == 0 && blockIdx.y == 0 && threadIdx.x == 0) lp_n0[s] = -1;
+    return;
+  }
+  const int r = s * T + blockIdx.y;
+  // workgroup (0, 0, s) alone announces n0 = gen_len[s]: one writer per word
+  lp_scan_chunk(logits + (size_t)r * V, sp_raw + (size_t)r * V, V, vec, c, sp_ms + ((size_t)r * nch + c) * 2,
+                sp_cand + ((size_t)r * nch + c) * LP_CAND, (c == 0 && blockIdx.y == 0) ? lp_n0 + s : nullptr,
+                gen_len + s);
+}
+
+// One record, the body of both commit kernels: from a row's chunk partials ``ms`` / ``cand`` (nch chunks) and its raw copy
+// ``raw``, *tok_dst = raw[tok] - lse and, for K > 0, the K best into ids_dst / top_dst[0 .. K - 1].
+__device__ __forceinline__ void lp_commit_row(const float* __restrict__ raw, int V, const float* __restrict__ ms,
+                                              const unsigned long long* __restrict__ cand, int nch, int K, int tok,
+                                              float* __restrict__ tok_dst, int* __restrict__ ids_dst,
+                                              float* __restrict__ top_dst) {
+  const int t = threadIdx.x;
+  __shared__ float term[LP_MAXCH];
+  __shared__ float fred[4];
+  __shared__ unsigned long long kred[2][4];
+  __shared__ unsigned long long win[LP_KMAX];
+  // lse: M = max m_c (order-free), S = sum s_c exp(m_c - M) serially in chunk order
+  float m = -INFINITY;
+  for (int c = t; c < nch; c += 256) m = fmaxf(m, ms[2 * c]);
+  m = wave_max(m);
+  if ((t & 63) == 0) fred[t >> 6] = m;
+  __syncthreads();
+  const float M = fmaxf(fmaxf(fred[0], fred[1]), fmaxf(fred[2], fred[3]));
+  for (int c = t; c < nch; c += 256) term[c] = ms[2 * c + 1] * expf(ms[2 * c] - M);
+  __syncthreads();
+  float S = 0.f;
+  for (int c = 0; c < nch; ++c) S += term[c];
+  const float lse = M + logf(S);
+  if (t == 0) *tok_dst = (tok >= 0 && tok < V) ? raw[tok] - lse : -INFINITY;
+  if (K <= 0) return;
+  // the K best of the nch * LP_CAND candidates (<= 16 per thread, in registers)
+  const int ncand = nch * LP_CAND;
+  unsigned long long key[16];
+#pragma unroll
+  for (int j = 0; j < 16; ++j) key[j] = (t + 256 * j) < ncand ? cand[t + 256 * j] : 0ull;
+  for (int r = 0; r < K; ++r) {
+    unsigned long long best = key[0];
+#pragma unroll
+    for (int j = 1; j < 16; ++j) best = lsa_umax64(best, key[j]);
+    best = lp_block_max_u64(best, kred[r & 1]);
+    if (t == 0) win[r] = best;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) key[j] = key[j] == best ? 0ull : key[j];
+  }
+  __syncthreads();
+  if (t < K) {
+    const unsigned long long w = win[t];
+    ids_dst[t] = w ? (int)(0xffffffffu - (uint32_t)(w & 0xffffffffull)) : -1;
+    top_dst[t] = w ? key_float((uint32_t)(w >> 32)) - lse : -INFINITY;
   }
 }
 
@@ -133,50 +227,38 @@ __global__ __launch_bounds__(256) void logprob_commit_kernel(const float* __rest
   if (t == 0) lp_n0[b] = -1;
   if (gen_len[b] != n0 + 1 || n0 >= max_new) return;
   K = min(K, kcap);
-  __shared__ float term[LP_MAXCH];
-  __shared__ float fred[4];
-  __shared__ unsigned long long kred[2][4];
-  __shared__ unsigned long long win[LP_KMAX];
-  const float* ms = lp_ms + (size_t)b * nch * 2;
-  // lse: M = max m_c (order-free), S = sum s_c exp(m_c - M) serially in chunk order
-  float m = -INFINITY;
-  for (int c = t; c < nch; c += 256) m = fmaxf(m, ms[2 * c]);
-  m = wave_max(m);
-  if ((t & 63) == 0) fred[t >> 6] = m;
-  __syncthreads();
-  const float M = fmaxf(fmaxf(fred[0], fred[1]), fmaxf(fred[2], fred[3]));
-  for (int c = t; c < nch; c += 256) term[c] = ms[2 * c + 1] * expf(ms[2 * c] - M);
-  __syncthreads();
-  float S = 0.f;
-  for (int c = 0; c < nch; ++c) S += term[c];
-  const float lse = M + logf(S);
-  if (t == 0) {
-    const int tok = out_tokens[(size_t)b * max_new + n0];
-    lp_tok[(size_t)b * max_new + n0] = (tok >= 0 && tok < V) ? lp_raw[(size_t)b * V + tok] - lse : -INFINITY;
-  }
-  if (K <= 0) return;
-  // the K best of the nch * LP_CAND candidates (<= 16 per thread, in registers)
-  const int ncand = nch * LP_CAND;
-  const unsigned long long* cand = lp_cand + (size_t)b * ncand;
-  unsigned long long key[16];
-#pragma unroll
-  for (int j = 0; j < 16; ++j) key[j] = (t + 256 * j) < ncand ? cand[t + 256 * j] : 0ull;
-  for (int r = 0; r < K; ++r) {
-    unsigned long long best = key[0];
-#pragma unroll
-    for (int j = 1; j < 16; ++j) best = lsa_umax64(best, key[j]);
-    best = lp_block_max_u64(best, kred[r & 1]);
-    if (t == 0) win[r] = best;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) key[j] = key[j] == best ? 0ull : key[j];
-  }
-  __syncthreads();
-  if (t < K) {
-    const unsigned long long w = win[t];
-    const size_t o = ((size_t)b * max_new + n0) * kcap + t;
-    lp_ids[o] = w ? (int)(0xffffffffu - (uint32_t)(w & 0xffffffffull)) : -1;
-    lp_top[o] = w ? key_float((uint32_t)(w >> 32)) - lse : -INFINITY;
-  }
+  const size_t o = (size_t)b * max_new + n0;
+  lp_commit_row(lp_raw + (size_t)b * V, V, lp_ms + (size_t)b * nch * 2, lp_cand + (size_t)b * nch * LP_CAND, nch, K,
+                out_tokens[o], lp_tok + o, lp_ids + o * kcap, lp_top + o * kcap);
+}
+
+// The verify-step commit, after spec_commit / spec_sample_commit (and dfa_spec_advance): workgroup (t, s) records
+// generated token n0 + t of sequence s from verify row s * T + t exactly when the sequence asked, this step's scan
+// announced n0 = lp_n0[s] >= 0 and the step committed more than t tokens (c = gen_len[s] - n0, 0 .. T, already cut by EOS
+// and the limit), at index n0 + t < max_new.  Row t is the distribution of generated token n0 + t: row 0 follows the
+// input token, row t draft t.  lp_n0[s] is NOT consumed here: T workgroups read it, and no workgroup reads a word
+// another workgroup of its launch writes.  It need not be: every step in which a row asks rewrites lp_n0 in its scan
+// (n0, or -1 for a finished row), the verify scan and the plain scan alike, so a stale n0 is never read.
+__global__ __launch_bounds__(256) void spec_logprob_commit_kernel(const float* __restrict__ sp_raw, int V, int T,
+                                                                  const float* __restrict__ sp_ms,
+                                                                  const unsigned long long* __restrict__ sp_cand,
+                                                                  int nch, const int* __restrict__ lp_k,
+                                                                  const int* __restrict__ lp_n0,
+                                                                  const int* __restrict__ gen_len,
+                                                                  const int* __restrict__ out_tokens, int max_new,
+                                                                  float* __restrict__ lp_tok, int* __restrict__ lp_ids,
+                                                                  float* __restrict__ lp_top, int kcap) {
+  const int t = blockIdx.x, s = blockIdx.y;
+  int K = lp_k[s];
+  if (K < 0) return;
+  const int n0 = lp_n0[s];
+  if (n0 < 0) return;
+  if (t >= gen_len[s] - n0 || n0 + t >= max_new) return;
+  K = min(K, kcap);
+  const int r = s * T + t;
+  const size_t o = (size_t)s * max_new + n0 + t;
+  lp_commit_row(sp_raw + (size_t)r * V, V, sp_ms + (size_t)r * nch * 2, sp_cand + (size_t)r * nch * LP_CAND, nch, K,
+                out_tokens[o], lp_tok + o, lp_ids + o * kcap, lp_top + o * kcap);
 }
 
 // workspace: lp_ms (B * ceil(V / 2048) * 2 f32) + lp_cand (B * ceil(V / 2048) * 32 u64).  Refused before any launch:
@@ -202,5 +284,34 @@ extern "C" int lsa_logprob_commit(const float* lp_raw, int B, int V, const float
   const int nch = (V + LP_CHUNK - 1) / LP_CHUNK;
   hipLaunchKernelGGL(logprob_commit_kernel, dim3(B), dim3(256), 0, s, lp_raw, V, lp_ms, lp_cand, nch, lp_k, lp_n0,
                      gen_len, out_tokens, max_new, lp_tok, lp_ids, lp_top, kcap);
+  return (int)hipGetLastError();
+}
+
+// The verify-step pair.  sp_raw f32 [32, V], sp_ms (32 * ceil(V / 2048) * 2 f32), sp_cand (32 * ceil(V / 2048) * 32 u64):
+// the spec-side workspace of the S * T <= 32 verify rows.  Refused before any launch: T or S outside 1 .. 8 (-3),
+// S * T > 32 (-3), V outside 1 .. 262144 (-1), kcap outside 0 .. 20 (-2).
+#define LP_SPEC_ROWS 32
+extern "C" int lsa_spec_logprob_scan(const float* logits, int S, int T, int V, const int* lp_k, const int* finished,
+                                     const int* gen_len, float* sp_raw, float* sp_ms, unsigned long long* sp_cand,
+                                     int* lp_n0, hipStream_t st) {
+  if (V < 1 || V > LP_MAXCH * LP_CHUNK) return -1;
+  if (T < 1 || T > 8 || S < 1 || S > 8 || S * T > LP_SPEC_ROWS) return -3;
+  const int nch = (V + LP_CHUNK - 1) / LP_CHUNK;
+  const int vec = (V % 4 == 0) && (((uintptr_t)logits | (uintptr_t)sp_raw) % 16 == 0);
+  hipLaunchKernelGGL(spec_logprob_scan_kernel, dim3(nch, T, S), dim3(256), 0, st, logits, V, vec, T, lp_k, finished,
+                     gen_len, sp_raw, sp_ms, sp_cand, lp_n0, nch);
+  return (int)hipGetLastError();
+}
+
+extern "C" int lsa_spec_logprob_commit(const float* sp_raw, int S, int T, int V, const float* sp_ms,
+                                       const unsigned long long* sp_cand, const int* lp_k, const int* lp_n0,
+                                       const int* gen_len, const int* out_tokens, int max_new, float* lp_tok,
+                                       int* lp_ids, float* lp_top, int kcap, hipStream_t st) {
+  if (V < 1 || V > LP_MAXCH * LP_CHUNK || max_new < 1) return -1;
+  if (kcap < 0 || kcap > LP_KMAX) return -2;
+  if (T < 1 || T > 8 || S < 1 || S > 8 || S * T > LP_SPEC_ROWS) return -3;
+  const int nch = (V + LP_CHUNK - 1) / LP_CHUNK;
+  hipLaunchKernelGGL(spec_logprob_commit_kernel, dim3(T, S), dim3(256), 0, st, sp_raw, V, T, sp_ms, sp_cand, nch, lp_k,
+                     lp_n0, gen_len, out_tokens, max_new, lp_tok, lp_ids, lp_top, kcap);
   return (int)hipGetLastError();
 }

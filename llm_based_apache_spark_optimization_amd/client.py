@@ -306,6 +306,8 @@ class EngineService(Backend):
                                 "spec_batch_guided": bool(getattr(getattr(lp.engine, "runner", None),
                                                                   "spec_batch_guided", False)),
                                 "logprobs": bool(getattr(lp.engine, "logprobs", False)),
+                                "spec_logprobs": bool(getattr(getattr(lp.engine, "runner", None),
+                                                              "spec_logprobs", False)),
                                 **lp.engine.stats} for m, lp in self._loops.items()}}
 
 

@@ -92,6 +92,9 @@ class Settings:
     # job result add sql_mean_logprob / sql_min_logprob of the generated statement
     logprobs: bool = dataclasses.field(default_factory=lambda: _env("LOGPROBS", False, bool))
     sql_logprobs: bool = dataclasses.field(default_factory=lambda: _env("SQL_LOGPROBS", False, bool))
+    # a request that asked for logprobs speculates too (off: it takes plain steps and makes a spec_batch run plain).
+    # Needs logprobs and spec_tokens; the records are the log-softmax of the raw verify rows
+    spec_logprobs: bool = dataclasses.field(default_factory=lambda: _env("SPEC_LOGPROBS", False, bool))
     tp: int = dataclasses.field(default_factory=lambda: _env("TP", 1, int))
     dp: int = dataclasses.field(default_factory=lambda: _env("DP", 1, int))
     max_batch: int = dataclasses.field(default_factory=lambda: _env("MAX_BATCH", 32, int))

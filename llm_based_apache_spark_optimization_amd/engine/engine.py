@@ -411,8 +411,10 @@ class LLMEngine:
                 return []
             sample = any(self._reqs[rid].params.needs_sampler for rid in running)
             guided = self.guided and any(self._reqs[rid].dfa is not None for rid in running)
-            # the logprob graph variant exactly while a running request asked; such a request never speculates
+            # the logprob graph variant exactly while a running request asked; such a request speculates only with
+            # the runner's ``spec_logprobs`` (the verify graph with the two logprob launches)
             lp = self.logprobs and any(self._reqs[rid].params.logprobs for rid in running)
+            lp_spec = not lp or bool(getattr(r, "spec_logprobs", False))
             # steps until the earliest request can hit its length limit; with EOS possible, at most
             # sync_every steps between host checks
             reqs = [self._reqs[rid] for rid in running]
@@ -423,7 +425,7 @@ class LLMEngine:
                 n_steps = remaining if self.run_ahead is None else min(self.run_ahead, remaining)
             else:
                 n_steps = min(self.sync_every, remaining)
-            spec_T = self._spec_run(reqs, n_steps, remaining) if (n_steps and not lp) else 0
+            spec_T = self._spec_run(reqs, n_steps, remaining) if (n_steps and lp_spec) else 0
             if spec_T:  # verify steps: each commits 1 .. spec_T tokens, so fewer cover the same budget
                 n_steps = min(n_steps, -(-remaining // spec_T))
             elif n_steps:
@@ -445,20 +447,23 @@ class LLMEngine:
             if self.device_timing:
                 ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
                 ev[0].record()
+            # verify steps of a run in which a request asked: the "lp" verify graph (spec_logprobs); a run in which
+            # nobody asked keeps today's verify graphs and their call
+            lpk = dict(logprobs=True) if (lp and spec_T) else {}
             if spec_T and spec_S > 1 and guided:  # spec_batch_guided: the mask of every constrained sequence's rows,
                 # only while a running request is constrained (then the sampled commit, if one needs the sampler)
-                r.decode_spec(n_steps, max_ctx=max_ctx, guided=True, sample=sample, S=spec_S)
+                r.decode_spec(n_steps, max_ctx=max_ctx, guided=True, sample=sample, S=spec_S, **lpk)
             elif spec_T and spec_S > 1 and sample:  # spec_batch_sampled: the sampled commit over the spec_S sequences
-                r.decode_spec(n_steps, max_ctx=max_ctx, sample=True, S=spec_S)
+                r.decode_spec(n_steps, max_ctx=max_ctx, sample=True, S=spec_S, **lpk)
             elif spec_T and spec_S > 1:  # spec_batch: greedy, unconstrained verify steps over slots 0 .. spec_S - 1
-                r.decode_spec(n_steps, max_ctx=max_ctx, S=spec_S)
+                r.decode_spec(n_steps, max_ctx=max_ctx, S=spec_S, **lpk)
             elif spec_T:
                 if sample:  # spec_sampled: the verify graph that ends in the sampled commit (masked too, if guided)
-                    r.decode_spec(n_steps, max_ctx=max_ctx, guided=guided, sample=True)
+                    r.decode_spec(n_steps, max_ctx=max_ctx, guided=guided, sample=True, **lpk)
                 elif guided:  # spec_guided: the verify graph with the mask of the T verify rows
-                    r.decode_spec(n_steps, max_ctx=max_ctx, guided=True)
+                    r.decode_spec(n_steps, max_ctx=max_ctx, guided=True, **lpk)
                 else:
-                    r.decode_spec(n_steps, max_ctx=max_ctx)
+                    r.decode_spec(n_steps, max_ctx=max_ctx, **lpk)
             elif lp:  # the variant with the two logprob launches (masked too, if a row is constrained)
                 r.decode(B, n_steps, sample, max_ctx=max_ctx, guided=guided, logprobs=True)
             else:
@@ -477,7 +482,8 @@ class LLMEngine:
                 REGISTRY.inc("lsa_guided_steps_total", n_steps, "decode steps run with the regex mask", model=self.name)
             if spec_T and n_steps:
                 self._spec_account(reqs)
-            if lp:  # the records of this sync's new tokens, for the rows that asked, in one transfer
+            if lp:  # the records of this sync's new tokens (up to T per verify step), for the rows that asked, in one
+                # transfer; logprob_steps counts plain and verify steps alike
                 self.stats["logprob_steps"] += n_steps
                 asked = [(q, min(int(gl[i]), q.params.max_tokens)) for i, q in enumerate(reqs) if q.params.logprobs]
                 self._read_logprobs([q for q, _ in asked], [n for _, n in asked])
@@ -556,8 +562,9 @@ class LLMEngine:
         has not opted out or been dropped by the acceptance guard; room for every position the run may write inside the model window; and the KV blocks of those
         positions without preempting anyone: the worst case is T committed tokens per step plus T - 1 rows of
         lookahead (also reserved so that a finished row, which rewrites its last T positions while the graph replays,
-        stays in its own blocks).  A run in which a request asked for per-token logprobs is never one (``step`` does not
-        ask: the verify graphs record none), which for ``spec_batch`` is one more reason of the all-or-nothing rule."""
+        stays in its own blocks).  A run in which a request asked for per-token logprobs is one only with the runner's
+        ``spec_logprobs`` (``step`` does not ask otherwise: the plain verify graphs record none, which for ``spec_batch``
+        is one more reason of the all-or-nothing rule); with it, every other condition here holds unchanged."""
         r = self.runner
         if not (getattr(r, "spec_tokens", 0) > 0 and r.spec_supported()):
             return 0

@@ -22,7 +22,8 @@ def build_engine(model: str, device: Optional[str] = None, checkpoint: Optional[
                  prefix_cow_min_tokens: Optional[int] = None, spec_quantized: bool = False,
                  guided: bool = False, spec_guided: bool = False, spec_sampled: bool = False,
                  spec_batch: int = 1, spec_batch_sampled: bool = False,
-                 spec_batch_guided: bool = False, logprobs: bool = False) -> LLMEngine:
+                 spec_batch_guided: bool = False, logprobs: bool = False,
+                 spec_logprobs: bool = False) -> LLMEngine:
     """kv_dtype: paged KV cache dtype, "bf16" | "fp8" (None: LSA_KV_FP8, default bf16).
     max_new_cap: generated-token cap per request (None: the context window).
     kv_reserve_tokens: generated tokens whose KV is reserved at admission (the rest grows lazily; < 0 reserves
@@ -57,7 +58,10 @@ def build_engine(model: str, device: Optional[str] = None, checkpoint: Optional[
     of them.
     logprobs: per-token log-probabilities for requests that carry ``SamplingParams.logprobs`` (off by default: such a
     request is then rejected); allocates the per-slot record buffers and captures a logprob variant of each decode
-    graph, replayed only while a running request asked."""
+    graph, replayed only while a running request asked.
+    spec_logprobs: a request that asked for logprobs speculates wherever one that did not ask would (off: it takes plain
+    steps, and makes a spec_batch run plain); its records are the log-softmax of the raw verify rows.  Needs logprobs
+    and spec_tokens, and is inert without either."""
     if device is None:
         device = f"cuda:{torch.cuda.current_device()}" if torch.cuda.is_available() else "cpu"
     t0 = time.perf_counter()
@@ -73,7 +77,8 @@ def build_engine(model: str, device: Optional[str] = None, checkpoint: Optional[
                          num_kv_blocks=num_kv_blocks, kv_memory_fraction=kv_memory_fraction, kv_dtype=kv_dtype,
                          max_new_cap=max_new_cap, spec_tokens=spec_tokens, spec_quantized=spec_quantized,
                          spec_guided=spec_guided, spec_sampled=spec_sampled, spec_batch=spec_batch,
-                         spec_batch_sampled=spec_batch_sampled, spec_batch_guided=spec_batch_guided)
+                         spec_batch_sampled=spec_batch_sampled, spec_batch_guided=spec_batch_guided,
+                         spec_logprobs=spec_logprobs)
     eng = LLMEngine(runner, tok, sync_every=sync_every, max_prefill_tokens=max_prefill_tokens, name=model,
                     prefill_chunk=prefill_chunk or None, kv_reserve_tokens=kv_reserve_tokens, spec_tokens=spec_tokens,
                     prefix_cache=prefix_cache, prefix_cow_min_tokens=prefix_cow_min_tokens, guided=guided,

@@ -51,7 +51,8 @@ class ModelRunner:
                  fuse_rope: Optional[bool] = None, seq_parallel: Optional[bool] = None, sp_min_tokens: Optional[int] = None,
                  kv_dtype: Optional[str] = None, spec_tokens: int = 0, spec_ngram: tuple = (3, 1),
                  spec_quantized: bool = False, spec_guided: bool = False, spec_sampled: bool = False,
-                 spec_batch: int = 1, spec_batch_sampled: bool = False, spec_batch_guided: bool = False):
+                 spec_batch: int = 1, spec_batch_sampled: bool = False, spec_batch_guided: bool = False,
+                 spec_logprobs: bool = False):
         self.w = weights
         # prompt-lookup speculative decoding (``_verify_step``): tokens drafted per step (0 = off) and the drafter's
         # (longest, shortest) n-gram.  Plain attributes: an experiment may set them on a built runner.
@@ -80,6 +81,10 @@ class ModelRunner:
         # sequence beside it is untouched).  Inert without ``enable_guided``, ``spec_guided`` and ``spec_batch`` > 1; a
         # constrained request that needs the sampler needs ``spec_batch_sampled`` as well.
         self.spec_batch_guided = bool(spec_batch_guided)
+        # opt-in: verify steps for requests that asked for per-token logprobs too (``_verify_step(logprobs=True)``: the
+        # scan of the S * T raw verify rows after the lm_head and the record of the tokens the step committed after its
+        # commit, kernels/logprobs.hip).  Inert without ``enable_logprobs`` and ``spec_tokens``.
+        self.spec_logprobs = bool(spec_logprobs)
         # acceptance guard of the engine: a request whose accepted-per-verify-step mean falls below this after 16
         # verify steps takes plain steps for the rest of its life.  Break-even = verify-step time / plain-step time - 1.
         # Measured on MI355X (scripts/bench_spec.py, profiles/spec/spec_decode_mi355x.jsonl; plain vs verify step, k = 3):
@@ -715,18 +720,32 @@ class ModelRunner:
     def count_step_kernels(self, B: int, sample: bool = False, logprobs: bool = False) -> int:
         """Kernel launches of one captured decode step of bucket B (a throw-away capture whose graph is kept and
         walked with hipGraphGetNodes): the launch-count check of the fused TP step (tests/test_tp_launches_gpu.py)."""
-        import ctypes
-
         assert self.use_graphs, "needs graph capture"
         plan = tuple(self.ctx_plan(B))
         if self.tp is not None and self.tp.size > 1:
             self.tp.warmup()
+        return self._count_kernels(lambda: self._decode_step(B, sample, plan, False, logprobs))
+
+    def count_verify_kernels(self, S: int = 1, guided: bool = False, sample: bool = False,
+                             logprobs: bool = False) -> int:
+        """Kernel launches of one captured verify step over S sequences (``count_step_kernels`` for ``_verify_step``)."""
+        assert self.use_graphs, "needs graph capture"
+        plan = tuple(self.ctx_plan(S))
+        self._spec_bufs()
+        if logprobs:
+            self._spec_lp_ws()
+        return self._count_kernels(lambda: self._verify_step(plan, guided, sample, S, logprobs))
+
+    def _count_kernels(self, step) -> int:
+        """The kernel nodes of a throw-away capture of ``step()``."""
+        import ctypes
+
         s = torch.cuda.Stream(device=self.device)
         s.wait_stream(torch.cuda.current_stream(self.device))
         g = torch.cuda.CUDAGraph(keep_graph=True)
         with torch.cuda.stream(s):
             with torch.cuda.graph(g, stream=s):
-                self._decode_step(B, sample, plan, False, logprobs)
+                step()
         torch.cuda.current_stream(self.device).wait_stream(s)
         lib = ctypes.CDLL("libamdhip64.so")
         graph = ctypes.c_void_p(g.raw_cuda_graph())
@@ -884,7 +903,8 @@ class ModelRunner:
         buf.copy_(table.to(torch.int32))
         self._spec_forced = buf
 
-    def _verify_step(self, plan: Optional[tuple] = None, guided: bool = False, sample: bool = False, S: int = 1) -> None:
+    def _verify_step(self, plan: Optional[tuple] = None, guided: bool = False, sample: bool = False, S: int = 1,
+                     logprobs: bool = False) -> None:
         """One speculative-decoding step of the request in slot 0: a forward pass over T = k + 1 rows -- the row's input
         token and k drafted tokens at positions p .. p + T - 1 -- and the in-order commit of the tokens greedy decoding
         would have produced (``ops.spec_commit``): between 1 and T per step, the same sequence as plain steps.
@@ -936,9 +956,18 @@ class ModelRunner:
         gen_len and its T states in row s of ``g_spec`` for the hand-over after the commit; a sequence without a
         constraint (or finished, or an idle slot) is untouched, as an unconstrained row is in the plain ``dfa_mask``.
         Each request's tokens are those of its plain guided steps.  With ``sample`` the mask runs before the sampled
-        commit over the S sequences, as in the one-sequence step."""
+        commit over the S sequences, as in the one-sequence step.
+
+        ``logprobs`` (a running request asked, ``spec_logprobs``): ``spec_logprob_scan`` between the lm_head and the mask
+        keeps the raw rows of every sequence that asked (the raw rule: before ``dfa_mask_verify``, the penalties and
+        the sampler) and announces n0 = gen_len[s]; ``spec_logprob_commit`` at the end records the c = gen_len[s] - n0
+        tokens the step committed, token n0 + t from verify row t, into the per-slot records of slot s.  A sequence
+        that did not ask (lp_k[s] < 0), a finished one and an idle slot record nothing."""
         w, d, Ts = self.w, self.d, self.spec_k() + 1
         sb = self._spec_bufs()
+        assert not logprobs or (self.spec_logprobs and self.logprobs), \
+            "logprob verify steps need spec_logprobs and enable_logprobs()"
+        lp_ws = self._spec_lp_ws() if logprobs else None
         assert S == 1 or not guided or (self.spec_batch_guided and self.spec_guided and self.guided), \
             "guided verify steps are one-sequence"
         assert S == 1 or not sample or (self.spec_sampled and self.spec_batch_sampled), \
@@ -998,6 +1027,8 @@ class ModelRunner:
         ops.add_rmsnorm(h, w.final_norm, self.eps, xn, parts=d_parts, rows=T)
         logits = sb["logits"][:T]
         lin(xn, w.lm_head, "f32", out=logits, splitk=1)
+        if logprobs:  # the raw rows: ahead of the mask and the sampled commit, which rewrite ``logits`` in place
+            ops.spec_logprob_scan(logits, Ts, self.lp_k[:S], st[4], st[1], self.lp_n0[:S], lp_ws)
         if guided:
             ops.dfa_mask_verify(logits, self.g_tok_off, self.g_tok_blob, self.g_cls, self.g_trans, self.g_accept,
                                 self.g_dim, self.g_on, self.g_state, self.g_base, st[1], st[2], st[4], self.eos,
@@ -1014,6 +1045,9 @@ class ModelRunner:
                             self.eos_on[:S], part=sb["amax_part"] if self.on_gpu else None)
         if guided:
             ops.dfa_spec_advance(self.g_on, self.g_state, self.g_spec[0] if S == 1 else self.g_spec[:S], st[1], Ts - 1)
+        if logprobs:
+            ops.spec_logprob_commit(Ts, self.lp_k[:S], self.lp_n0[:S], st[1], self.out_tokens, self.lp_tok, self.lp_ids,
+                                    self.lp_top, lp_ws)
 
     def _verify_linear_cpu(self, x, wt, epi, out, splitk=1, rownorm=None, pre=False):
         """CPU twin of the verify step's GEMMs, one row at a time with the rounding points of the plain batch-1 step's
@@ -1049,6 +1083,13 @@ class ModelRunner:
         rows = self._spec_bufs()["logits"][: S * T]
         return rows if S == 1 else rows.view(S, T, -1)
 
+    def spec_lp_raw(self, S: int = 1) -> torch.Tensor:
+        """[T, V] f32: the raw verify rows ``spec_logprob_scan`` kept in the last logprob verify step, as the lm_head
+        wrote them (rows of sequences that asked and were not finished; other rows are stale).  ``S`` > 1: [S, T, V]."""
+        T = self.spec_k() + 1
+        rows = self._spec_lp_ws()[0][: S * T]
+        return rows if S == 1 else rows.view(S, T, -1)
+
     def spec_drafts(self, S: int = 1) -> torch.Tensor:
         """[k] int32: the drafts of the last verify step (-1 = none).  ``S`` > 1: [S, k]."""
         k = self.spec_k()
@@ -1056,7 +1097,7 @@ class ModelRunner:
         return d if S == 1 else d.view(S, k)
 
     def decode_spec(self, steps: int, max_ctx: Optional[int] = None, guided: bool = False,
-                    sample: bool = False, S: int = 1) -> None:
+                    sample: bool = False, S: int = 1, logprobs: bool = False) -> None:
         """Run ``steps`` verify steps of the request in slot 0 (the analogue of ``decode`` at bucket 1); ``max_ctx``
         bounds pos0 + T during the run (picks the split plan's tier).  ``guided``: the variant with the regex mask of
         the verify rows, for a constrained request (its graph key is the unguided one with a trailing True).
@@ -1066,11 +1107,15 @@ class ModelRunner:
         plan, forced buffer): the split plan is the decode plan of bucket S, the key the one-sequence key with S
         appended.  ``sample`` with ``S`` > 1 needs ``spec_batch_sampled``; its key is the greedy key, then "sample",
         then S.  ``guided`` with ``S`` > 1 needs ``spec_batch_guided``; its key is the one-sequence key, then True, then
-        "sample" if sampled, then S."""
+        "sample" if sampled, then S.  ``logprobs``: the variant with the two logprob launches of the verify step, for
+        runs in which a request asked (``spec_logprobs``): its key is the key above with a trailing "lp" (after S where
+        present); every other key is unchanged."""
         assert self.spec_supported(), ("speculative decoding: TP = 1, spec_tokens > 0, bf16 weights and KV cache "
                                        "(or spec_quantized)")
         assert not guided or (self.guided and self.spec_guided), "guided verify steps need enable_guided() and spec_guided"
         assert not sample or self.spec_sampled, "sampled verify steps need spec_sampled"
+        assert not logprobs or (self.spec_logprobs and self.logprobs), \
+            "logprob verify steps need spec_logprobs and enable_logprobs()"
         assert S == 1 or (S <= self.spec_s() and (not guided or self.spec_batch_guided)
                           and (not sample or self.spec_batch_sampled)), \
             "verify steps over several sequences: S <= spec_batch (clamped), constrained only with " \
@@ -1078,7 +1123,7 @@ class ModelRunner:
         plan = tuple(self.ctx_plan(S, max_ctx))
         if not self.use_graphs:
             for _ in range(steps):
-                self._verify_step(plan, guided, sample, S)
+                self._verify_step(plan, guided, sample, S, logprobs)
             return
         key = ("spec", self.spec_k() + 1, plan, 0 if self._spec_forced is None else self._spec_forced.data_ptr())
         if guided:
@@ -1087,14 +1132,18 @@ class ModelRunner:
             key += ("sample",)
         if S > 1:
             key += (S,)
+        if logprobs:
+            key += ("lp",)
         if key not in self.graphs:
             self._spec_bufs()
+            if logprobs:
+                self._spec_lp_ws()
             s = torch.cuda.Stream(device=self.device)
             s.wait_stream(torch.cuda.current_stream(self.device))
             g = torch.cuda.CUDAGraph()
             with torch.cuda.stream(s):
                 with torch.cuda.graph(g, stream=s):
-                    self._verify_step(plan, guided, sample, S)
+                    self._verify_step(plan, guided, sample, S, logprobs)
             torch.cuda.current_stream(self.device).wait_stream(s)
             self.graphs[key] = g
         g = self.graphs[key]
@@ -1195,12 +1244,25 @@ class ModelRunner:
         self.lp_raw = torch.zeros(S, V, **f32)
         self.lp_ws = ops.logprob_workspace(S, V, dev)
         self.logprobs = True
+        if self.spec_logprobs:
+            self._spec_lp_ws()
+
+    def _spec_lp_ws(self) -> tuple:
+        """The spec-side raw rows and chunk workspace of logprob verify steps (32 rows; ``ops.spec_logprob_workspace``):
+        allocated only when both ``enable_logprobs()`` and ``spec_logprobs`` hold."""
+        assert self.logprobs and self.spec_logprobs, "logprob verify steps need spec_logprobs and enable_logprobs()"
+        ws = self.__dict__.get("spec_lp_ws")
+        if ws is None:
+            ws = self.spec_lp_ws = ops.spec_logprob_workspace(self.V, self.device)
+        return ws
 
     def logprobs_bytes(self) -> int:
-        """Device bytes ``enable_logprobs`` holds (records + raw rows + chunk workspaces)."""
+        """Device bytes ``enable_logprobs`` holds (records + raw rows + chunk workspaces; with ``spec_logprobs`` the
+        32 raw rows and chunk workspace of the verify step too)."""
         if not self.logprobs:
             return 0
-        ts = (self.lp_k, self.lp_n0, self.lp_tok, self.lp_ids, self.lp_top, self.lp_raw, *self.lp_ws)
+        ts = (self.lp_k, self.lp_n0, self.lp_tok, self.lp_ids, self.lp_top, self.lp_raw, *self.lp_ws,
+              *(self.__dict__.get("spec_lp_ws") or ()))
         return sum(t.numel() * t.element_size() for t in ts)
 
     def _logprob_scan(self, logits, lp_k, finished, gen_len, lp_n0) -> None:

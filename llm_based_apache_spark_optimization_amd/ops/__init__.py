@@ -1623,6 +1623,80 @@ def logprob_commit(lp_raw, lp_k, lp_n0, gen_len, out_tokens, lp_tok, lp_ids, lp_
     ext().logprob_commit(lp_raw, workspace[0], workspace[1], lp_k, lp_n0, gen_len, out_tokens, lp_tok, lp_ids, lp_top, B)
 
 
+LOGPROB_SPEC_ROWS = ref.LOGPROB_SPEC_ROWS
+
+
+def spec_logprob_workspace(V: int, device) -> tuple:
+    """(sp_raw f32 [32, V], ms f32 [32 * nch * 2], cand int64 [32 * nch * 32]): the raw rows and chunk partials of the
+    S * T <= 32 rows of a verify step, between ``spec_logprob_scan`` and ``spec_logprob_commit`` (the per-slot
+    ``lp_raw [max_slots, V]`` may have fewer rows than a verify step)."""
+    R = LOGPROB_SPEC_ROWS
+    return (torch.zeros(R, V, device=device, dtype=torch.float32),) + logprob_workspace(R, V, device)
+
+
+def _spec_logprob_check(op: str, T: int, V: int, lp_k, tensors: dict, workspace) -> int:
+    """The refusals of both verify-step ops before any launch: ``_logprob_check``'s, and T / S / S * T."""
+    if lp_k.dim() != 1:
+        raise ValueError(f"{op}: lp_k must be [S]")
+    S = lp_k.shape[0]
+    if not (isinstance(T, int) and 1 <= T <= 8 and 1 <= S <= 8 and S * T <= LOGPROB_SPEC_ROWS):
+        raise ValueError(f"{op}: T = {T} and S = {S} must be in 1 .. 8 with S * T <= {LOGPROB_SPEC_ROWS}")
+    if workspace is None or len(workspace) != 3:
+        raise ValueError(f"{op}: needs spec_logprob_workspace (raw rows, ms, cand)")
+    raw, ms, cand = workspace
+    _logprob_check(op, LOGPROB_SPEC_ROWS, V, dict(tensors, sp_raw=(raw, torch.float32), ms=(ms, torch.float32),
+                                                  cand=(cand, torch.int64)), raw)
+    nch = (V + LOGPROB_CHUNK - 1) // LOGPROB_CHUNK
+    if ms.numel() < LOGPROB_SPEC_ROWS * nch * 2 or cand.numel() < LOGPROB_SPEC_ROWS * nch * LOGPROB_CAND:
+        raise ValueError(f"{op}: chunk workspaces too small for {LOGPROB_SPEC_ROWS} rows")
+    for name, (t, _) in tensors.items():
+        if name in ("lp_n0", "gen_len", "finished") and (t.dim() != 1 or t.shape[0] < S):
+            raise ValueError(f"{op}: {name} must be [>= {S}]")
+    return S
+
+
+def spec_logprob_scan(logits, T: int, lp_k, finished, gen_len, lp_n0, workspace):
+    """``logprob_scan`` of a verify step (kernels/logprobs.hip spec_logprob_scan_kernel), right after its lm_head and
+    ahead of ``dfa_mask_verify`` and the verify commit: S = lp_k.shape[0] sequences of T rows, ``logits`` [S * T, V].
+    The T raw rows of every sequence that asked and is not finished go into ``workspace`` (``spec_logprob_workspace``)
+    and ``gen_len[s]`` into ``lp_n0[s]`` (-1 for a finished sequence that asked).  ``logits`` is only read."""
+    if logits.dim() != 2:
+        raise ValueError("spec_logprob_scan: logits must be [S * T, V]")
+    i32, f32 = torch.int32, torch.float32
+    S = _spec_logprob_check("spec_logprob_scan", T, logits.shape[1], lp_k,
+                            {"logits": (logits, f32), "lp_k": (lp_k, i32), "finished": (finished, i32),
+                             "gen_len": (gen_len, i32), "lp_n0": (lp_n0, i32)}, workspace)
+    if logits.shape[0] != S * T:
+        raise ValueError(f"spec_logprob_scan: logits must have S * T = {S * T} rows")
+    if not _gpu(logits):
+        return ref.spec_logprob_scan(logits, T, lp_k, finished, gen_len, lp_n0, workspace[0])
+    ext().spec_logprob_scan(logits, T, lp_k, finished, gen_len, workspace[0], workspace[1], workspace[2], lp_n0)
+
+
+def spec_logprob_commit(T: int, lp_k, lp_n0, gen_len, out_tokens, lp_tok, lp_ids, lp_top, workspace):
+    """``logprob_commit`` of a verify step, after its token commit (and ``dfa_spec_advance``): sequence s records the
+    c = gen_len[s] - lp_n0[s] tokens the step committed, index n0 + t from verify row s T + t and
+    ``out_tokens[s, n0 + t]``, straight into the per-slot records (``ops.reference.spec_logprob_commit`` states the
+    rule).  ``lp_n0`` is only read."""
+    i32, f32 = torch.int32, torch.float32
+    raw = workspace[0] if workspace is not None and len(workspace) == 3 else None
+    V = raw.shape[1] if raw is not None and raw.dim() == 2 else 0
+    S = _spec_logprob_check("spec_logprob_commit", T, V, lp_k,
+                            {"lp_k": (lp_k, i32), "lp_n0": (lp_n0, i32), "gen_len": (gen_len, i32),
+                             "out_tokens": (out_tokens, i32), "lp_tok": (lp_tok, f32), "lp_ids": (lp_ids, i32),
+                             "lp_top": (lp_top, f32)}, workspace)
+    if lp_ids.dim() != 3 or not 0 <= lp_ids.shape[2] <= LOGPROB_KMAX:
+        raise ValueError(f"spec_logprob_commit: top_logprobs K must be in 0 .. {LOGPROB_KMAX}")
+    if (out_tokens.dim() != 2 or out_tokens.shape[0] < S or lp_tok.shape != out_tokens.shape
+            or lp_ids.shape != lp_top.shape or tuple(lp_ids.shape[:2]) != tuple(out_tokens.shape)):
+        raise ValueError("spec_logprob_commit: record buffers must match out_tokens ([rows, max_new] / "
+                         "[rows, max_new, K])")
+    if not _gpu(raw):
+        return ref.spec_logprob_commit(T, lp_k, lp_n0, gen_len, out_tokens, lp_tok, lp_ids, lp_top, raw)
+    ext().spec_logprob_commit(T, raw, workspace[1], workspace[2], lp_k, lp_n0, gen_len, out_tokens, lp_tok, lp_ids,
+                              lp_top)
+
+
 # ----------------------------------------------------------------------------------- speculative decoding
 def verify_split_plan(Hkv: int, max_ctx: int, S: int = 1) -> tuple[int, int, int]:
     """(chunk_blocks, nsplit, unsplit_max) of ``attn_verify`` over S sequences for contexts (pos0 + T) up to max_ctx:

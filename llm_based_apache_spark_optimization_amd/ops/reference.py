@@ -339,6 +339,53 @@ def logprob_commit(lp_raw, lp_k, lp_n0, gen_len, out_tokens, lp_tok, lp_ids, lp_
             lp_top[b, n0, :K] = top[0]
 
 
+LOGPROB_SPEC_ROWS = 32  # the rows of the spec-side raw buffer and chunk workspace: S * T <= 32
+
+
+def spec_logprob_scan(logits, T: int, lp_k, finished, gen_len, lp_n0, sp_raw):
+    """Host twin of spec_logprob_scan_kernel (state level), over the S = len(lp_k) sequences of a verify step with T
+    rows each (``logits`` [S * T, V]): a sequence s that asked and is not finished keeps its T raw rows in
+    ``sp_raw[s T .. s T + T - 1]`` (the spec-side buffer of 32 rows, not the per-slot ``lp_raw``) and n0 = gen_len[s]
+    in ``lp_n0[s]``; a finished sequence that asked gets ``lp_n0[s] = -1``; one that did not ask is left alone."""
+    for s in range(lp_k.shape[0]):
+        if int(lp_k[s]) < 0:
+            continue
+        if int(finished[s]) != 0:
+            lp_n0[s] = -1
+            continue
+        sp_raw[s * T:(s + 1) * T].copy_(logits[s * T:(s + 1) * T])
+        lp_n0[s] = int(gen_len[s])
+
+
+def spec_logprob_commit(T: int, lp_k, lp_n0, gen_len, out_tokens, lp_tok, lp_ids, lp_top, sp_raw):
+    """Host twin of spec_logprob_commit_kernel, after the verify commit.  Sequence s records exactly when it asked and
+    ``lp_n0[s]`` = n0 >= 0: with c = gen_len[s] - n0 the tokens this step committed (0 .. T, already cut by EOS and the
+    limit), for t < min(c, T) and n0 + t < max_new, index n0 + t gets ``logprob_rows`` of verify row s T + t (the
+    distribution of generated token n0 + t: row 0 follows the input token, row t draft t) and ``out_tokens[s, n0 + t]``,
+    K = min(lp_k[s], lp_ids.shape[2]).  Nothing else is written.
+
+    Invariant: ``lp_n0`` is NOT consumed (on the device T workgroups read it).  It need not be: every step in which a
+    row asks rewrites ``lp_n0`` in its scan (n0, or -1 for a finished row), the verify scan and the plain scan alike."""
+    max_new = out_tokens.shape[1]
+    for s in range(lp_k.shape[0]):
+        K = int(lp_k[s])
+        n0 = int(lp_n0[s])
+        if K < 0 or n0 < 0:
+            continue
+        K = min(K, lp_ids.shape[2])
+        c = int(gen_len[s]) - n0
+        for t in range(min(c, T)):
+            n = n0 + t
+            if n >= max_new:
+                break
+            r = s * T + t
+            chosen, ids, top = logprob_rows(sp_raw[r:r + 1], out_tokens[s:s + 1, n], K)
+            lp_tok[s, n] = chosen[0]
+            if K > 0:
+                lp_ids[s, n, :K] = ids[0]
+                lp_top[s, n, :K] = top[0]
+
+
 # ----------------------------------------------------------------------------------- regex-constrained decoding
 DFA_DEAD = 0xFFFF
 DFA_MAX_TABLE = 32768

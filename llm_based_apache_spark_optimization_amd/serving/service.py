@@ -35,7 +35,8 @@ def engine_factory(settings: Settings, tp_factory=None):
                            prefix_cow_min_tokens=settings.prefix_cow_min_tokens, guided=settings.guided,
                            spec_guided=settings.spec_guided, spec_sampled=settings.spec_sampled,
                            spec_batch=settings.spec_batch, spec_batch_sampled=settings.spec_batch_sampled,
-                           spec_batch_guided=settings.spec_batch_guided, logprobs=settings.logprobs)
+                           spec_batch_guided=settings.spec_batch_guided, logprobs=settings.logprobs,
+                           spec_logprobs=settings.spec_logprobs)
         if settings.spec_min_accept >= 0:
             eng.runner.spec_min_accept = settings.spec_min_accept
         return eng

@@ -9,7 +9,15 @@ Each window is ITERS launches (or graph replays) between two device events; the 
 by window in one process; a row reports the median window and its spread (min, max) in microseconds per launch.
 Scan rows also report the bytes the scan moves (it reads V * 4 and writes V * 4 per row) over its median time, as a
 share of ``--hbm-gbs`` (the MI355X's 8 TB/s by default).  The cost is reported, not gated.  ``--table`` prints the README table
-from the rows of ``--out`` instead of measuring."""
+from the rows of ``--out`` instead of measuring.
+
+  python scripts/bench_logprobs.py --spec --out profiles/logprobs/spec_logprobs_mi355x.jsonl
+
+``--spec`` measures the verify-step pair instead (``spec_logprobs``): ``spec_logprob_scan`` / ``spec_logprob_commit``
+standalone at (S, T) = (1, 4) and (4, 8) with every sequence recording all T rows, and the captured verify step of the
+two models (k = 3 drafts; one sequence, and four with ``spec_batch``) with nobody asking (the plain verify graph and the
+"lp" graph with lp_k = -1), all asking K = 0 and all asking K = 20, next to the plain decode step of the same bucket
+with and without logprobs -- same windows, arms alternated, same state restored before every window."""
 import argparse
 import json
 import statistics
@@ -152,13 +160,102 @@ def steps(model, B, dev, iters, windows):
     return out
 
 
+def spec_kernels(V, S, T, dev, iters, windows, hbm_gbs):
+    """The verify-step pair standalone: every sequence asks K = 0 / K = 20 and records all T rows, or nobody asks."""
+    g = torch.Generator().manual_seed(V + S * T)
+    logits = (torch.randn(S * T, V, generator=g) * 2).to(dev)
+    i32 = dict(dtype=torch.int32, device=dev)
+    max_new = 16
+    st = dict(gen_len=torch.zeros(S, **i32), finished=torch.zeros(S, **i32), out_tokens=torch.zeros(S, max_new, **i32),
+              lp_n0=torch.full((S,), -1, **i32), lp_tok=torch.zeros(S, max_new, device=dev),
+              lp_ids=torch.zeros(S, max_new, ops.LOGPROB_KMAX, **i32),
+              lp_top=torch.zeros(S, max_new, ops.LOGPROB_KMAX, device=dev))
+    ws = ops.spec_logprob_workspace(V, dev)
+    ks = {"k0": torch.zeros(S, **i32), "k20": torch.full((S,), 20, **i32), "off": torch.full((S,), -1, **i32)}
+    rows = []
+
+    def scan(k):
+        return lambda: ops.spec_logprob_scan(logits, T, ks[k], st["finished"], st["gen_len"], st["lp_n0"], ws)
+
+    for k, ts in alternate({k: scan(k) for k in ks}, iters, windows).items():
+        r = row_of(ts, what="spec_logprob_scan", V=V, S=S, T=T, case=k, iters=iters)
+        if k != "off":
+            r["bytes"] = 2 * 4 * V * S * T
+            r["hbm_share"] = round(r["bytes"] / (r["us_median"] * 1e-6) / (hbm_gbs * 1e9), 4)
+        rows.append(r)
+    # the verify commit does not consume lp_n0: after one scan (n0 = 0) every launch records T tokens per sequence
+    scan("k20")()
+    after = torch.full((S,), T, **i32)
+
+    def commit(k):
+        return lambda: ops.spec_logprob_commit(T, ks[k], st["lp_n0"], after, st["out_tokens"], st["lp_tok"],
+                                               st["lp_ids"], st["lp_top"], ws)
+
+    for k, ts in alternate({k: commit(k) for k in ks}, iters, windows).items():
+        rows.append(row_of(ts, what="spec_logprob_commit", V=V, S=S, T=T, case=k, iters=iters))
+    return rows
+
+
+def spec_steps(model, S, dev, iters, windows, k=3):
+    """The captured verify step of ``model`` over S sequences of T = k + 1 rows: the plain verify graph, the "lp" graph
+    with nobody asking, all asking K = 0 and all asking K = 20; and the plain decode step of bucket S without and with
+    logprobs (K = 20), for the acceptance a speculating request with logprobs needs."""
+    from llm_based_apache_spark_optimization_amd.engine import SamplingParams, build_engine
+
+    arms = ("verify", "verify_lp_off", "verify_lp_k0", "verify_lp_k20", "plain", "plain_lp_k20")
+    T = k + 1
+    budget = iters * T + 64  # a window of ``iters`` verify steps commits at most iters * T tokens: nobody finishes
+    eng = build_engine(model, device=dev, max_slots=max(S, 2), max_model_len=256 + budget, kv_reserve_tokens=-1,
+                       logprobs=True, spec_tokens=k, spec_batch=S, spec_logprobs=True)
+    r = eng.runner
+    assert T == r.spec_k() + 1
+    sp = SamplingParams(max_tokens=budget, ignore_eos=True, logprobs=True, top_logprobs=20)
+    for i in range(S):
+        eng.add_request([1] + list(range(10 + i, 138 + i)), sp)
+    eng.run_ahead = 1
+    eng.step()
+    assert eng.sched.num_running == S and eng.stats["spec_steps"] > 0
+    i32 = dict(dtype=torch.int32, device=dev)
+    ks = {"off": torch.full((S,), -1, **i32), "k0": torch.zeros(S, **i32), "k20": torch.full((S,), 20, **i32)}
+    max_ctx = 160 + budget
+    state = (r.gen_len, r.positions, r.input_ids, r.finished)
+    snap = [t.clone() for t in state]
+
+    def restore():
+        for t, s0 in zip(state, snap):
+            t.copy_(s0)
+
+    def run(name):
+        if name.startswith("verify"):
+            return lambda: r.decode_spec(1, max_ctx=max_ctx, S=r.bucket(S), logprobs=name != "verify")
+        return lambda: r.decode(r.bucket(S), 1, False, max_ctx=max_ctx, logprobs=name != "plain")
+
+    runs = {name: run(name) for name in arms}
+    times = {name: [] for name in arms}
+    for w in range(windows + 1):  # window 0 warms every graph up
+        for name in arms:
+            r.lp_k[:S].copy_(ks[name.rsplit("_", 1)[-1]] if "lp_" in name else ks["off"])
+            restore()  # every window runs the same ``iters`` steps from the same state
+            t = timed(runs[name], iters)
+            if w:
+                times[name].append(t)
+    out = [row_of(ts, what="spec_step", model=model, V=r.V, S=S, T=T, case=name, iters=iters)
+           for name, ts in times.items()]
+    eng.abort_all("measurement over")
+    del eng, r
+    torch.cuda.empty_cache()
+    return out
+
+
 def table(path):
     rows = [json.loads(x) for x in open(path)]
     print("| what | V | B | case | us median (min .. max) |")
     print("|---|---|---|---|---|")
     for r in rows:
         extra = f", {100 * r['hbm_share']:.1f} % of HBM" if "hbm_share" in r else ""
-        print(f"| {r['what']} | {r['V']} | {r['B']} | {r['case']} | {r['us_median']} ({r['us_min']} .. {r['us_max']})"
+        rows_of = r["B"] if "B" in r else f"{r['S']} x {r['T']}"
+        what = r["what"] + (f" {r['model']}" if "model" in r else "")
+        print(f"| {what} | {r['V']} | {rows_of} | {r['case']} | {r['us_median']} ({r['us_min']} .. {r['us_max']})"
               f"{extra} |")
 
 
@@ -172,6 +269,7 @@ def main():
     ap.add_argument("--no-steps", action="store_true")
     ap.add_argument("--no-kernels", action="store_true")
     ap.add_argument("--table", action="store_true")
+    ap.add_argument("--spec", action="store_true", help="measure the verify-step pair (spec_logprobs) instead")
     args = ap.parse_args()
     if args.table:
         table(args.out)
@@ -187,6 +285,16 @@ def main():
                 out.write(json.dumps(r) + "\n")
             out.flush()
 
+        if args.spec:
+            if not args.no_kernels:
+                for V in (32000, 128256):
+                    for S, T in ((1, 4), (4, 8)):
+                        emit(spec_kernels(V, S, T, dev, args.iters, args.windows, args.hbm_gbs))
+            if not args.no_steps:
+                for model in ("duckdb-nsql", "llama3.2"):
+                    for S in (1, 4):
+                        emit(spec_steps(model, S, dev, args.step_iters, args.windows))
+            return 0
         if not args.no_kernels:
             for V in (32000, 128256):
                 for B in (1, 32):
