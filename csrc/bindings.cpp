@@ -76,6 +76,11 @@ int lsa_spec_logprob_commit(const float* sp_raw, int S, int T, int V, const floa
                             const unsigned long long* sp_cand, const int* lp_k, const int* lp_n0, const int* gen_len,
                             const int* out_tokens, int max_new, float* lp_tok, int* lp_ids, float* lp_top, int kcap,
                             hipStream_t st);
+int lsa_prompt_logprob_scan(const float* logits, int R, int V, const int* targets, int any_k, float* ms,
+                            unsigned long long* cand, hipStream_t s);
+int lsa_prompt_logprob_commit(const float* logits, int R, int V, const float* ms, const unsigned long long* cand,
+                              const int* targets, const int* row_k, int any_k, float* dst_tok, int* dst_ids,
+                              float* dst_top, int kcap, hipStream_t s);
 int lsa_dfa_mask(float* logits, int B, int V, const int* tok_off, const uint8_t* tok_blob, const uint8_t* cls,
                  const uint16_t* trans, const uint8_t* accept, const int* g_dim, const int* g_on, int* g_state,
                  const int* g_base, const int* rows, const int* gen_len, const int* input_ids, const int* finished,
@@ -1204,6 +1209,58 @@ void spec_logprob_commit(int64_t T, const at::Tensor& sp_raw, const at::Tensor& 
         "spec_logprob_commit");
 }
 
+// the prompt pair (prompt-token logprobs): R scored prefill rows of logits [R, V] with their targets (< 0: no record) and
+// K per row; ms f32 [>= R * ceil(V / 2048) * 2], cand int64 [>= R * ceil(V / 2048) * 32].  any_k: some row has K > 0
+// (the launch form that writes and reads the candidates).
+void check_prompt_logprob(const char* op, const at::Tensor& logits, const at::Tensor& targets, const at::Tensor& row_k,
+                          const at::Tensor& ms, const at::Tensor& cand) {
+  need(logits, at::kFloat, "logits");
+  TORCH_CHECK(logits.dim() == 2 && logits.is_contiguous(), op, ": logits contiguous f32 [R, V]");
+  const int64_t R = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(R >= 1 && V >= 1 && V <= 262144, op, ": 1 <= V <= 262144 (the sampler's bound), R >= 1");
+  for (const at::Tensor* t : {&targets, &row_k}) {
+    need(*t, at::kInt, "prompt logprob row operand");
+    TORCH_CHECK(t->dim() == 1 && t->is_contiguous() && t->numel() == R, op, ": targets / row_k contiguous int32 [R]");
+  }
+  need(ms, at::kFloat, "ms");
+  need(cand, at::kLong, "cand");
+  const int64_t nch = (V + 2047) / 2048;
+  TORCH_CHECK(ms.is_contiguous() && cand.is_contiguous() && ms.numel() >= R * nch * 2 && cand.numel() >= R * nch * 32,
+              op, ": chunk workspaces too small");
+}
+
+void prompt_logprob_scan(const at::Tensor& logits, const at::Tensor& targets, const at::Tensor& row_k, bool any_k,
+                         at::Tensor& ms, at::Tensor& cand) {
+  check_prompt_logprob("prompt_logprob_scan", logits, targets, row_k, ms, cand);
+  check(lsa_prompt_logprob_scan(logits.data_ptr<float>(), (int)logits.size(0), (int)logits.size(1),
+                                targets.data_ptr<int>(), any_k ? 1 : 0, ms.data_ptr<float>(),
+                                reinterpret_cast<unsigned long long*>(cand.data_ptr()), cur_stream()),
+        "prompt_logprob_scan");
+}
+
+// records: dst_tok f32 [R], dst_ids int32 / dst_top f32 [R, kcap] with 0 <= kcap <= 20
+void prompt_logprob_commit(const at::Tensor& logits, const at::Tensor& ms, const at::Tensor& cand,
+                           const at::Tensor& targets, const at::Tensor& row_k, bool any_k, at::Tensor& dst_tok,
+                           at::Tensor& dst_ids, at::Tensor& dst_top) {
+  check_prompt_logprob("prompt_logprob_commit", logits, targets, row_k, ms, cand);
+  const int64_t R = logits.size(0);
+  need(dst_tok, at::kFloat, "dst_tok");
+  need(dst_ids, at::kInt, "dst_ids");
+  need(dst_top, at::kFloat, "dst_top");
+  TORCH_CHECK(dst_tok.dim() == 1 && dst_tok.numel() == R && dst_tok.is_contiguous(),
+              "prompt_logprob_commit: dst_tok contiguous f32 [R]");
+  TORCH_CHECK(dst_ids.dim() == 2 && dst_ids.sizes() == dst_top.sizes() && dst_ids.size(0) == R &&
+                  dst_ids.is_contiguous() && dst_top.is_contiguous(),
+              "prompt_logprob_commit: dst_ids / dst_top contiguous [R, K]");
+  TORCH_CHECK(dst_ids.size(1) >= 0 && dst_ids.size(1) <= 20, "prompt_logprob_commit: top_logprobs K must be in 0 .. 20");
+  check(lsa_prompt_logprob_commit(logits.data_ptr<float>(), (int)R, (int)logits.size(1), ms.data_ptr<float>(),
+                                  reinterpret_cast<const unsigned long long*>(cand.data_ptr()),
+                                  targets.data_ptr<int>(), row_k.data_ptr<int>(), any_k ? 1 : 0,
+                                  dst_tok.data_ptr<float>(), dst_ids.data_ptr<int>(), dst_top.data_ptr<float>(),
+                                  (int)dst_ids.size(1), cur_stream()),
+        "prompt_logprob_commit");
+}
+
 // regex-constrained decoding: -inf into every logit whose token would kill the row's DFA (kernels/guided.hip).
 // Table rows are indexed by rows[b] when given (prefill tail: the sequence's slot), else by b.
 void dfa_mask(at::Tensor& logits, const at::Tensor& tok_off, const at::Tensor& tok_blob, const at::Tensor& cls,
@@ -1686,6 +1743,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("spec_logprob_commit", &spec_logprob_commit, py::arg("T"), py::arg("sp_raw"), py::arg("sp_ms"),
         py::arg("sp_cand"), py::arg("lp_k"), py::arg("lp_n0"), py::arg("gen_len"), py::arg("out_tokens"),
         py::arg("lp_tok"), py::arg("lp_ids"), py::arg("lp_top"));
+  m.def("prompt_logprob_scan", &prompt_logprob_scan, py::arg("logits"), py::arg("targets"), py::arg("row_k"),
+        py::arg("any_k"), py::arg("ms"), py::arg("cand"));
+  m.def("prompt_logprob_commit", &prompt_logprob_commit, py::arg("logits"), py::arg("ms"), py::arg("cand"),
+        py::arg("targets"), py::arg("row_k"), py::arg("any_k"), py::arg("dst_tok"), py::arg("dst_ids"),
+        py::arg("dst_top"));
   m.def("dfa_mask", &dfa_mask, py::arg("logits"), py::arg("tok_off"), py::arg("tok_blob"), py::arg("cls"),
         py::arg("trans"), py::arg("accept"), py::arg("g_dim"), py::arg("g_on"), py::arg("g_state"), py::arg("g_base"),
         py::arg("rows"), py::arg("gen_len"), py::arg("input_ids"), py::arg("finished"), py::arg("eos"));

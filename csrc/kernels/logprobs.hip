@@ -34,6 +34,22 @@
 //                            t < c and n0 + t < max_new: index n0 + t from row s T + t and out_tokens[s, n0 + t] (row
 //                            t is the distribution of generated token n0 + t), straight into the per-slot records.
 //
+// Prompt-token logprobs (teacher-forced scoring in the prefill): the target token of every scored row is known before
+// the lm_head runs and nothing overwrites the rows, so the pair below runs the same two bodies without what a decode
+// step needs only because its token comes later: no raw-row copy, and no candidate rounds when no row asked for K > 0.
+//
+//   lsa_prompt_logprob_scan    grid (ceil(V / 2048), R) over logits [R, V] (read only), targets [R], row_k [R].  A row
+//                              with targets[r] < 0 returns after one scalar load.  Otherwise workgroup (c, r) writes
+//                              the chunk's (m_c, s_c) by lp_scan_chunk's very expressions, and the chunk's best 32
+//                              keys only in the launch form that was told some row has K > 0 (a template argument,
+//                              not a per-lane branch).
+//   lsa_prompt_logprob_commit  grid (R).  A row with a target runs lp_commit_row(raw = the logits row itself, tok =
+//                              targets[r], K = min(row_k[r], kcap)) into dst_tok [R], dst_ids / dst_top [R, kcap]; rows
+//                              without a target write nothing.  ``logits`` must stay intact between the two launches.
+//
+// A prompt record is therefore one expression with a generated-token record: for equal row values and token the two
+// are bitwise equal, chosen value and top-K alike.
+//
 // Invariant: the verify commit does NOT consume lp_n0[s] -- T workgroups read it, and no workgroup reads a word another
 // workgroup of its launch writes.  It need not: every step in which a row asks rewrites lp_n0 in its scan (n0, or -1
 // for a finished row), the verify scan and the plain scan alike.  The plain commit's own consume is unaffected.
@@ -58,9 +74,12 @@ __device__ __forceinline__ unsigned long long lp_block_max_u64(unsigned long lon
   return lsa_umax64(lsa_umax64(red[0], red[1]), lsa_umax64(red[2], red[3]));
 }
 
-// One chunk of one raw row, the body of both scan kernels: chunk c of ``row`` (V words) is read ONCE into registers and
-// copied into ``raw``; (m_c, s_c) goes to ms[0 .. 1] and the chunk's best LP_CAND packed keys to out[0 .. 31].  The one
-// workgroup that announces the record index gets n0_dst (else nullptr): *n0_dst = *n0_src, the gen_len before the commit.
+// One chunk of one raw row, the body of every scan kernel: chunk c of ``row`` (V words) is read ONCE into registers and
+// (COPY) copied into ``raw``; (m_c, s_c) goes to ms[0 .. 1] and (CAND) the chunk's best LP_CAND packed keys to
+// out[0 .. 31].  The one workgroup that announces the record index gets n0_dst (else nullptr): *n0_dst = *n0_src, the
+// gen_len before the commit.  COPY / CAND are compile-time: the decode and verify scans take both, the prompt scan
+// neither (K = 0 everywhere) or the candidates alone; the expressions of m_c, s_c and the keys are the same in all.
+template <bool COPY, bool CAND>
 __device__ __forceinline__ void lp_scan_chunk(const float* __restrict__ row, float* __restrict__ raw, int V, int vec,
                                               int c, float* __restrict__ ms, unsigned long long* __restrict__ out,
                                               int* __restrict__ n0_dst, const int* __restrict__ n0_src) {
@@ -74,14 +93,14 @@ __device__ __forceinline__ void lp_scan_chunk(const float* __restrict__ row, flo
     const int i0 = lo + 1024 * h + 4 * t;
     if (vec && i0 + 4 <= V) {
       const float4 x = *reinterpret_cast<const float4*>(row + i0);
-      *reinterpret_cast<float4*>(raw + i0) = x;
+      if (COPY) *reinterpret_cast<float4*>(raw + i0) = x;
       v[4 * h] = x.x; v[4 * h + 1] = x.y; v[4 * h + 2] = x.z; v[4 * h + 3] = x.w;
     } else {
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const bool in = i0 + j < V;
         const float x = in ? row[i0 + j] : 0.f;
-        if (in) raw[i0 + j] = x;
+        if (COPY && in) raw[i0 + j] = x;
         v[4 * h + j] = x;
       }
     }
@@ -109,6 +128,7 @@ __device__ __forceinline__ void lp_scan_chunk(const float* __restrict__ row, flo
     ms[1] = (fred[4] + fred[5]) + (fred[6] + fred[7]);
     if (n0_dst != nullptr) *n0_dst = *n0_src;
   }
+  if (!CAND) return;
   // the chunk's best LP_CAND keys: LP_CAND rounds of a block-wide max, the winner knocked out of its owner's registers
   unsigned long long key[8];
 #pragma unroll
@@ -137,8 +157,9 @@ __global__ __launch_bounds__(256) void logprob_scan_kernel(const float* __restri
     if (c == 0 && threadIdx.x == 0) lp_n0[b] = -1;
     return;
   }
-  lp_scan_chunk(logits + (size_t)b * V, lp_raw + (size_t)b * V, V, vec, c, lp_ms + ((size_t)b * nch + c) * 2,
-                lp_cand + ((size_t)b * nch + c) * LP_CAND, c == 0 ? lp_n0 + b : nullptr, gen_len + b);
+  lp_scan_chunk<true, true>(logits + (size_t)b * V, lp_raw + (size_t)b * V, V, vec, c,
+                            lp_ms + ((size_t)b * nch + c) * 2, lp_cand + ((size_t)b * nch + c) * LP_CAND,
+                            c == 0 ? lp_n0 + b : nullptr, gen_len + b);
 }
 
 // The verify-step scan: sequence s = blockIdx.z, verify row r = s * T + blockIdx.y of logits [S * T, V]; the raw rows and
@@ -158,9 +179,9 @@ __global__ __launch_bounds__(256) void spec_logprob_scan_kernel(const float* __r
   }
   const int r = s * T + blockIdx.y;
   // workgroup (0, 0, s) alone announces n0 = gen_len[s]: one writer per word
-  lp_scan_chunk(logits + (size_t)r * V, sp_raw + (size_t)r * V, V, vec, c, sp_ms + ((size_t)r * nch + c) * 2,
-                sp_cand + ((size_t)r * nch + c) * LP_CAND, (c == 0 && blockIdx.y == 0) ? lp_n0 + s : nullptr,
-                gen_len + s);
+  lp_scan_chunk<true, true>(logits + (size_t)r * V, sp_raw + (size_t)r * V, V, vec, c,
+                            sp_ms + ((size_t)r * nch + c) * 2, sp_cand + ((size_t)r * nch + c) * LP_CAND,
+                            (c == 0 && blockIdx.y == 0) ? lp_n0 + s : nullptr, gen_len + s);
 }
 
 // One record, the body of both commit kernels: from a row's chunk partials ``ms`` / ``cand`` (nch chunks) and its raw copy
@@ -261,6 +282,36 @@ __global__ __launch_bounds__(256) void spec_logprob_commit_kernel(const float* _
                 out_tokens[o], lp_tok + o, lp_ids + o * kcap, lp_top + o * kcap);
 }
 
+// The prompt pair: R scored prefill rows, each with its target token (< 0: the row records nothing) and its K.  CAND:
+// the launch was told that some row has K > 0.  Nothing but ms / cand is written by the scan: ``logits`` is the raw row
+// the commit reads.
+template <bool CAND>
+__global__ __launch_bounds__(256) void prompt_logprob_scan_kernel(const float* __restrict__ logits, int V, int vec,
+                                                                  const int* __restrict__ targets,
+                                                                  float* __restrict__ ms,
+                                                                  unsigned long long* __restrict__ cand, int nch) {
+  const int c = blockIdx.x, r = blockIdx.y;
+  if (targets[r] < 0) return;
+  lp_scan_chunk<false, CAND>(logits + (size_t)r * V, nullptr, V, vec, c, ms + ((size_t)r * nch + c) * 2,
+                             cand + ((size_t)r * nch + c) * LP_CAND, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__(256) void prompt_logprob_commit_kernel(const float* __restrict__ logits, int V,
+                                                                    const float* __restrict__ ms,
+                                                                    const unsigned long long* __restrict__ cand,
+                                                                    int nch, const int* __restrict__ targets,
+                                                                    const int* __restrict__ row_k,
+                                                                    float* __restrict__ dst_tok,
+                                                                    int* __restrict__ dst_ids,
+                                                                    float* __restrict__ dst_top, int kcap) {
+  const int r = blockIdx.x;
+  const int tok = targets[r];
+  if (tok < 0) return;
+  const int K = min(row_k[r], kcap);
+  lp_commit_row(logits + (size_t)r * V, V, ms + (size_t)r * nch * 2, cand + (size_t)r * nch * LP_CAND, nch, K, tok,
+                dst_tok + r, dst_ids + (size_t)r * kcap, dst_top + (size_t)r * kcap);
+}
+
 // workspace: lp_ms (B * ceil(V / 2048) * 2 f32) + lp_cand (B * ceil(V / 2048) * 32 u64).  Refused before any launch:
 // B < 1, V < 1 or V > 262144 (4096 candidates: lsa_sample_commit's bound).
 extern "C" int lsa_logprob_scan(const float* logits, int B, int V, const int* lp_k, const int* finished,
@@ -313,5 +364,35 @@ extern "C" int lsa_spec_logprob_commit(const float* sp_raw, int S, int T, int V,
   const int nch = (V + LP_CHUNK - 1) / LP_CHUNK;
   hipLaunchKernelGGL(spec_logprob_commit_kernel, dim3(T, S), dim3(256), 0, st, sp_raw, V, T, sp_ms, sp_cand, nch, lp_k,
                      lp_n0, gen_len, out_tokens, max_new, lp_tok, lp_ids, lp_top, kcap);
+  return (int)hipGetLastError();
+}
+
+// The prompt pair.  ms (R * ceil(V / 2048) * 2 f32), cand (R * ceil(V / 2048) * 32 u64; written and read only when
+// any_k).  any_k: some row_k[r] > 0 -- with any_k = 0 the commit must be given kcap = 0 or rows with row_k <= 0 only.
+// Refused before any launch: R < 1, V outside 1 .. 262144 (-1), kcap outside 0 .. 20 (-2).
+extern "C" int lsa_prompt_logprob_scan(const float* logits, int R, int V, const int* targets, int any_k, float* ms,
+                                       unsigned long long* cand, hipStream_t s) {
+  if (R < 1 || V < 1 || V > LP_MAXCH * LP_CHUNK) return -1;
+  const int nch = (V + LP_CHUNK - 1) / LP_CHUNK;
+  const int vec = (V % 4 == 0) && ((uintptr_t)logits % 16 == 0);
+  if (any_k)
+    hipLaunchKernelGGL(prompt_logprob_scan_kernel<true>, dim3(nch, R), dim3(256), 0, s, logits, V, vec, targets, ms,
+                       cand, nch);
+  else
+    hipLaunchKernelGGL(prompt_logprob_scan_kernel<false>, dim3(nch, R), dim3(256), 0, s, logits, V, vec, targets, ms,
+                       cand, nch);
+  return (int)hipGetLastError();
+}
+
+// any_k = 0: the scan wrote no candidates, so every row commits with K = 0 whatever row_k says
+extern "C" int lsa_prompt_logprob_commit(const float* logits, int R, int V, const float* ms,
+                                         const unsigned long long* cand, const int* targets, const int* row_k,
+                                         int any_k, float* dst_tok, int* dst_ids, float* dst_top, int kcap,
+                                         hipStream_t s) {
+  if (R < 1 || V < 1 || V > LP_MAXCH * LP_CHUNK) return -1;
+  if (kcap < 0 || kcap > LP_KMAX) return -2;
+  const int nch = (V + LP_CHUNK - 1) / LP_CHUNK;
+  hipLaunchKernelGGL(prompt_logprob_commit_kernel, dim3(R), dim3(256), 0, s, logits, V, ms, cand, nch, targets, row_k,
+                     dst_tok, dst_ids, dst_top, any_k ? kcap : 0);
   return (int)hipGetLastError();
 }

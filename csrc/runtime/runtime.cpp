@@ -47,10 +47,10 @@ PYBIND11_MODULE(_lsa_runtime, m) {
            py::arg("reserve_tokens") = 64, py::arg("prefix_cache") = false,
            py::arg("cow_min_tokens") = Scheduler::kCowMinTokens)
       .def("add", &Scheduler::add, py::arg("id"), py::arg("prompt_len"), py::arg("max_new"),
-           py::arg("tokens") = std::vector<int>(), py::arg("cacheable") = true)
+           py::arg("tokens") = std::vector<int>(), py::arg("cacheable") = true, py::arg("match_limit") = -1)
       .def("grow", &Scheduler::grow, py::arg("id"), py::arg("tokens"))
       .def("preempt", &Scheduler::preempt, py::arg("id"), py::arg("prompt_len"), py::arg("max_new"),
-           py::arg("tokens") = std::vector<int>())
+           py::arg("tokens") = std::vector<int>(), py::arg("match_limit") = -1)
       .def("cached_tokens", &Scheduler::cached_tokens)
       .def("shared_blocks", &Scheduler::shared_blocks)
       .def("take_copies", &Scheduler::take_copies)

@@ -109,6 +109,7 @@ struct Req {
   bool cacheable = false;
   bool published = false;
   int cached = 0;           // prompt tokens whose KV the request found in the cache at admission
+  int match_limit = -1;     // leading tokens that may be served from cached blocks; < 0 = prompt_len - 1
   std::vector<int> nodes;   // index nodes behind blocks[0 .. nodes.size()): the shared head of the table
 };
 
@@ -163,8 +164,11 @@ class Scheduler {
   static constexpr int kCowMinTokens = 8;
 
   // tokens: the prompt's token ids, required (and length-checked) when the prefix cache is on and the request is
-  // cacheable; ignored otherwise.
-  void add(long long id, int prompt_len, int max_new, const std::vector<int>& tokens = {}, bool cacheable = true) {
+  // cacheable; ignored otherwise.  match_limit: the number of leading prompt tokens that may be served from cached
+  // blocks (full blocks and the fork alike); < 0 = prompt_len - 1, the rule that at least the last prompt token is
+  // computed.  A request whose prompt rows from some position on must be computed (prompt-token logprobs) passes less.
+  void add(long long id, int prompt_len, int max_new, const std::vector<int>& tokens = {}, bool cacheable = true,
+           int match_limit = -1) {
     if (reqs_.count(id)) throw std::invalid_argument("duplicate request id");
     if (prompt_len < 1 || max_new < 1) throw std::invalid_argument("empty prompt or max_new < 1");
     const int need = alloc_.blocks_for(prompt_len + max_new);
@@ -176,6 +180,7 @@ class Scheduler {
     if (cache) {
       r.tokens = tokens;
       r.cacheable = true;
+      r.match_limit = match_limit;
     }
     waiting_.push_back(id);
   }
@@ -253,7 +258,8 @@ class Scheduler {
   // (prompt, max_new): the engine folds the tokens generated so far into the prompt and re-prefills them.
   // With the prefix cache on, tokens are the resumed prompt's ids (as in add): the request can then hit its own
   // earlier blocks on re-admission if they survived.
-  void preempt(long long id, int prompt_len, int max_new, const std::vector<int>& tokens = {}) {
+  // match_limit: as in add, for the resumed prompt.
+  void preempt(long long id, int prompt_len, int max_new, const std::vector<int>& tokens = {}, int match_limit = -1) {
     Req& r = reqs_.at(id);
     if (r.slot < 0) throw std::invalid_argument("preempt: request is not running");
     if (prompt_len < 1 || max_new < 1 || alloc_.blocks_for(prompt_len + max_new) > max_blocks_per_seq_)
@@ -266,6 +272,7 @@ class Scheduler {
     r.prompt_len = prompt_len;
     r.max_new = max_new;
     if (r.cacheable) r.tokens = tokens;
+    r.match_limit = match_limit;
     waiting_.push_front(id);
   }
 
@@ -429,10 +436,12 @@ class Scheduler {
   }
 
   // Longest chain of cached blocks that prefixes the prompt, capped so that at least the last prompt token is
-  // computed, then the best partial match among the last node's children (the fork).
+  // computed (and no more than the request's match_limit tokens are served), then the best partial match among the
+  // last node's children (the fork), under the same cap.
   Match match(const Req& r) const {
     Match m;
-    const int bs = alloc_.block_size(), max_full = (r.prompt_len - 1) / bs;
+    const int cap = r.match_limit < 0 ? r.prompt_len - 1 : std::min(r.match_limit, r.prompt_len - 1);
+    const int bs = alloc_.block_size(), max_full = cap / bs;
     int node = 0;
     for (int i = 0; i < max_full; ++i) {
       const int c = find_child(node, r.tokens.data() + (size_t)i * bs);
@@ -440,7 +449,7 @@ class Scheduler {
       m.chain.push_back(c);
       node = c;
     }
-    const int base = (int)m.chain.size() * bs, limit = std::min(bs - 1, r.prompt_len - 1 - base);
+    const int base = (int)m.chain.size() * bs, limit = std::min(bs - 1, cap - base);
     for (int c : nodes_[node].children) {
       const std::vector<int>& t = nodes_[c].toks;
       int p = 0;

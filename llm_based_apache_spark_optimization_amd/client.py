@@ -51,6 +51,16 @@ class GenerateResponse:
     # per-token logprobs, when the request asked ("logprobs": true): one {"token", "logprob", "bytes", "top_logprobs":
     # [{"token", "logprob", "bytes"}]} per generated token (a streamed chunk: those of the tokens read at its sync)
     logprobs: Optional[list] = None
+    # prompt-token logprobs, when the request asked ("prompt_logprobs": true): one entry per prompt token
+    # (prompt_eval_count of them), null below max(1, prompt_logprobs_from), else the shape of a ``logprobs`` entry; a
+    # streamed request carries the whole list in its final chunk.  An init-only argument kept as a plain attribute and
+    # not a dataclass field, because tests/test_logprobs_cpu.py::test_response_key_only_when_asked pins the keys of a
+    # response that did not ask to ``dataclasses.fields`` less ``logprobs``; ``to_dict`` adds the key when it is set, and
+    # ``dataclasses.replace`` carries the attribute over (it reads an InitVar that has a default from the object)
+    prompt_logprobs: dataclasses.InitVar[Optional[list]] = None
+
+    def __post_init__(self, prompt_logprobs=None):
+        self.prompt_logprobs = prompt_logprobs
 
     def __getitem__(self, k):
         return getattr(self, k)
@@ -62,6 +72,8 @@ class GenerateResponse:
         d = dataclasses.asdict(self)
         if d["logprobs"] is None:  # nothing asked: the response is key for key what it is without the feature
             del d["logprobs"]
+        if self.prompt_logprobs is not None:
+            d["prompt_logprobs"] = self.prompt_logprobs
         return d
 
     @property
@@ -86,6 +98,12 @@ class Backend:
         r = self.generate(model, prompt, system, options, raw)
         yield GenerateResponse(model=model, response=r.response, done=False, done_reason="", created_at=r.created_at)
         yield dataclasses.replace(r, response="")
+
+    def score(self, model: str, prompt: str, completions, system: str = "", options: Optional[dict] = None,
+              raw: bool = False, top_logprobs: int = 0) -> dict:
+        """Teacher-forced scoring: the log-likelihood the model gives each of ``completions`` after the rendered prompt
+        (``EngineService.score`` states the answer's shape)."""
+        raise NotImplementedError
 
     def models(self) -> list:
         return []
@@ -144,6 +162,15 @@ class _EngineLoop:
         self._err: Optional[BaseException] = None
         self._t = threading.Thread(target=self._run, name=f"engine-{engine.name}", daemon=True)
         self._t.start()
+
+    def submit_many(self, prompts, params) -> list:
+        """``submit`` for several prompts that should be admitted together (``LLMEngine.add_requests``)."""
+        if not self.alive():
+            raise EngineUnavailable(f"engine {self.engine.name} is down: {self._err!r}")
+        reqs = self.engine.add_requests(prompts, params)
+        with self._cv:
+            self._cv.notify()
+        return reqs
 
     def submit(self, ids, params, stream: bool = False):
         if not self.alive():
@@ -258,7 +285,8 @@ class EngineService(Backend):
                                 total_duration=r.total_duration_ns, load_duration=r.load_duration_ns,
                                 prompt_eval_count=r.prompt_tokens, prompt_eval_duration=r.prompt_eval_duration_ns,
                                 eval_count=r.eval_count, eval_duration=r.eval_duration_ns,
-                                prompt_cached_count=r.cached_prompt_tokens, logprobs=r.logprobs)
+                                prompt_cached_count=r.cached_prompt_tokens, logprobs=r.logprobs,
+                                prompt_logprobs=r.prompt_logprobs)
 
     def generate(self, model, prompt, system="", options=None, raw=False) -> GenerateResponse:
         eng, req = self._submit(model, prompt, system, options, raw)
@@ -289,7 +317,62 @@ class EngineService(Backend):
         last = self._final(model, eng, req)
         if last.logprobs is not None:  # what no earlier chunk carried; over the chunks: the non-streamed list
             last = dataclasses.replace(last, logprobs=last.logprobs[sent:])
-        yield dataclasses.replace(last, response="")
+        yield dataclasses.replace(last, response="")  # (prompt_logprobs rides whole with this final chunk)
+
+    MAX_SCORE_COMPLETIONS = 64
+
+    def score(self, model, prompt, completions, system="", options=None, raw=False, top_logprobs=0) -> dict:
+        """The log-likelihood of each completion given the prompt, through the prefill (prompt-token logprobs).
+
+        The rendered prompt is tokenised as ``generate`` tokenises it; each completion is tokenised on its own, without
+        BOS, and appended (the lm-eval-harness convention: a joint tokenisation of prompt + completion could merge
+        across the seam and differ).  Each completion is one ordinary engine request -- max_tokens 1 (the token is
+        discarded), prompt_logprobs_from = the prompt's length, logprobs off -- and all are submitted together, so they
+        batch and, with the prefix cache, share the prompt's blocks.  Scoring never truncates: what does not fit the
+        context window is refused (``SamplingOptionError``), as are an empty completion and more than 64 of them.
+
+        -> {"model", "prompt_eval_count", "scores": [{"completion", "tokens", "logprob" (sum), "mean_logprob",
+        "min_logprob", "token_logprobs": [entries]}], "total_duration"}"""
+        t0 = time.perf_counter()
+        if isinstance(completions, str):
+            completions = [completions]
+        completions = list(completions)
+        if not completions:
+            raise SamplingOptionError("score needs at least one completion")
+        if len(completions) > self.MAX_SCORE_COMPLETIONS:
+            raise SamplingOptionError(f"score takes at most {self.MAX_SCORE_COMPLETIONS} completions a call")
+        lp = self.loop(model)
+        eng = lp.engine
+        opts = dict(self.defaults)
+        opts.update(options or {})
+        opts.update(num_predict=1, logprobs=False, prompt_logprobs=True, top_logprobs=top_logprobs)
+        params = SamplingParams.from_ollama_options(opts)
+        ids = eng.tok.encode(eng.render(prompt, system, raw), add_bos=True)
+        window = eng.runner.max_model_len if params.num_ctx is None else min(eng.runner.max_model_len,
+                                                                            int(params.num_ctx))
+        seqs = []
+        for c in completions:
+            cids = eng.tok.encode(c, add_bos=False) if isinstance(c, str) else []
+            if not cids:
+                raise SamplingOptionError("score: a completion is empty (no tokens)")
+            if len(ids) + len(cids) > window - 1:
+                raise SamplingOptionError(f"score: prompt ({len(ids)} tokens) + completion ({len(cids)}) does not fit "
+                                          f"the context window ({window}); scoring never truncates")
+            seqs.append(ids + cids)
+        params = dataclasses.replace(params, prompt_logprobs_from=len(ids), max_tokens=1)
+        reqs = lp.submit_many(seqs, params)  # admitted together: one packed prefill, one shared prompt
+        scores = []
+        for c, req in zip(completions, reqs):
+            if not req.done.wait(self.timeout_s):
+                raise TimeoutError(f"scoring on {model} timed out after {self.timeout_s}s")
+            if req.error:
+                raise RuntimeError(f"engine {model} failed: {req.error}")
+            ents = eng.result(req).prompt_logprobs[len(ids):]
+            lps = [float(e["logprob"]) for e in ents]
+            scores.append({"completion": c, "tokens": len(ents), "logprob": sum(lps), "mean_logprob": sum(lps) / len(lps),
+                           "min_logprob": min(lps), "token_logprobs": ents})
+        return {"model": model, "prompt_eval_count": len(ids), "scores": scores,
+                "total_duration": int((time.perf_counter() - t0) * 1e9)}
 
     def models(self) -> list:
         return sorted(self._loops)
@@ -306,6 +389,7 @@ class EngineService(Backend):
                                 "spec_batch_guided": bool(getattr(getattr(lp.engine, "runner", None),
                                                                   "spec_batch_guided", False)),
                                 "logprobs": bool(getattr(lp.engine, "logprobs", False)),
+                                "prompt_logprobs": bool(getattr(lp.engine, "prompt_logprobs_supported", False)),
                                 "spec_logprobs": bool(getattr(getattr(lp.engine, "runner", None),
                                                               "spec_logprobs", False)),
                                 **lp.engine.stats} for m, lp in self._loops.items()}}
@@ -330,7 +414,7 @@ class FakeBackend(Backend):
             if self.fail_next is not None:
                 e, self.fail_next = self.fail_next, None
                 raise e
-        if options and (options.get("logprobs") or options.get("top_logprobs")):
+        if options and (options.get("logprobs") or options.get("top_logprobs") or options.get("prompt_logprobs")):
             raise SamplingOptionError("the fake backend has no model distribution: logprobs cannot be served")
         t0 = time.perf_counter()
         if options and options.get("fake_delay"):
@@ -339,6 +423,9 @@ class FakeBackend(Backend):
         dt = int((time.perf_counter() - t0) * 1e9)
         return GenerateResponse(model=model, response=text, created_at=_now(), total_duration=dt,
                                 eval_count=len(text.split()), eval_duration=dt, prompt_eval_count=len(prompt.split()))
+
+    def score(self, model, prompt, completions, system="", options=None, raw=False, top_logprobs=0) -> dict:
+        raise SamplingOptionError("the fake backend has no model distribution: completions cannot be scored")
 
     def models(self):
         return ["duckdb-nsql", "llama3.2", "mistral"]
@@ -358,8 +445,24 @@ class RemoteBackend(Backend):
         req = urllib.request.Request(self.url + "/api/generate", data=body, headers={"Content-Type": "application/json"})
         with urllib.request.urlopen(req, timeout=self.timeout_s) as f:
             d = json.loads(f.read())
-        fields = {f.name for f in dataclasses.fields(GenerateResponse)}
+        fields = {f.name for f in dataclasses.fields(GenerateResponse)} | {"prompt_logprobs"}
         return GenerateResponse(**{k: v for k, v in d.items() if k in fields})
+
+    def score(self, model, prompt, completions, system="", options=None, raw=False, top_logprobs=0) -> dict:
+        import urllib.error
+        import urllib.request
+
+        body = json.dumps({"model": model, "prompt": prompt, "system": system, "options": options or {}, "raw": raw,
+                           "completions": [completions] if isinstance(completions, str) else list(completions),
+                           "top_logprobs": top_logprobs}).encode()
+        req = urllib.request.Request(self.url + "/api/score", data=body, headers={"Content-Type": "application/json"})
+        try:
+            with urllib.request.urlopen(req, timeout=self.timeout_s) as f:
+                return json.loads(f.read())
+        except urllib.error.HTTPError as e:
+            if e.code == 400:  # what the engine refused, as the in-process backend raises it
+                raise SamplingOptionError(e.read().decode(errors="replace")) from None
+            raise
 
 
 # -------------------------------------------------------------------------------------- module API
@@ -385,9 +488,19 @@ def get_backend() -> Backend:
 
 
 def generate(model: str, prompt: str = "", system: str = "", options: Optional[dict] = None, raw: bool = False,
-             logprobs: bool = False, top_logprobs: int = 0, **_ignored) -> GenerateResponse:
+             logprobs: bool = False, top_logprobs: int = 0, prompt_logprobs: bool = False,
+             **_ignored) -> GenerateResponse:
     """Drop-in for ``ollama.generate(model=, system=, prompt=)``.  ``logprobs`` / ``top_logprobs`` (Ollama's top-level
-    request fields) travel to the backend inside ``options``."""
+    request fields) and ``prompt_logprobs`` travel to the backend inside ``options``."""
     if logprobs or top_logprobs:
         options = dict(options or {}, logprobs=bool(logprobs), top_logprobs=top_logprobs)
+    if prompt_logprobs:
+        options = dict(options or {}, prompt_logprobs=True)
     return get_backend().generate(model, prompt, system, options, raw)
+
+
+def score(model: str, prompt: str = "", completions=(), system: str = "", options: Optional[dict] = None,
+          raw: bool = False, top_logprobs: int = 0) -> dict:
+    """The log-likelihood the model gives each of ``completions`` (a string or a list) after the prompt:
+    ``EngineService.score`` through the configured backend."""
+    return get_backend().score(model, prompt, completions, system, options, raw, top_logprobs)

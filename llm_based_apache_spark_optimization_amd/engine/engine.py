@@ -51,6 +51,14 @@ def _top_logprobs_option(v) -> int:
         raise SamplingOptionError("top_logprobs must be an integer in 0 .. 20") from None
 
 
+def _prompt_logprobs_from_option(v) -> int:
+    if v is None:
+        return 0
+    if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+        raise SamplingOptionError("prompt_logprobs_from must be a non-negative integer")
+    return v
+
+
 @dataclasses.dataclass
 class SamplingParams:
     """Ollama-compatible options (temperature 0 = greedy, as the benchmark configs require)."""
@@ -96,6 +104,12 @@ class SamplingParams:
     # temperature / top-k / top-p / min-p.  A request that asks never speculates; its tokens are what they are without.
     logprobs: bool = False
     top_logprobs: int = 0
+    # prompt-token log-probabilities (OpenAI's echo + logprobs, vLLM's prompt_logprobs; same engine flag): entry j of
+    # the response list is the log-probability the model gives prompt token j after prompt tokens 0 .. j - 1 -- the
+    # raw rule above, at the prefill row of position j - 1 -- for max(1, prompt_logprobs_from) <= j < prompt length;
+    # entries below are null.  top_logprobs applies to them as to generated tokens.  Generation is what it is without.
+    prompt_logprobs: bool = False
+    prompt_logprobs_from: int = 0
 
     @property
     def needs_sampler(self) -> bool:
@@ -126,7 +140,9 @@ class SamplingParams:
                               cache_prompt=bool(opts.get("cache_prompt", True)),
                               regex=(str(opts["regex"]) if opts.get("regex") else None),
                               logprobs=bool(opts.get("logprobs", False)),
-                              top_logprobs=_top_logprobs_option(opts.get("top_logprobs", 0)))
+                              top_logprobs=_top_logprobs_option(opts.get("top_logprobs", 0)),
+                              prompt_logprobs=bool(opts.get("prompt_logprobs", False)),
+                              prompt_logprobs_from=_prompt_logprobs_from_option(opts.get("prompt_logprobs_from")))
 
 
 @dataclasses.dataclass
@@ -164,6 +180,12 @@ class Request:
     # kept on the host across preemptions; lp_read = device records of the current incarnation already read
     logprobs: list = dataclasses.field(default_factory=list)
     lp_read: int = 0
+    # prompt-token logprobs (params.prompt_logprobs): prompt_lp[j] = None or the record of prompt token j, kept on the
+    # host across preemptions; plp_next = the next prompt index to score (records are made in prompt order);
+    # plp_pending = device records of prefill calls not read yet: (records, first row, rows, first prompt index)
+    prompt_lp: list = dataclasses.field(default_factory=list)
+    plp_next: int = 0
+    plp_pending: list = dataclasses.field(default_factory=list)
 
     @property
     def ctx_ids(self) -> list:
@@ -186,6 +208,9 @@ class GenerationResult:
     # params.logprobs: one {"token", "logprob", "bytes", "top_logprobs": [{"token", "logprob", "bytes"}]} per generated
     # token (len == eval_count); None when the request did not ask
     logprobs: Optional[list] = None
+    # params.prompt_logprobs: one entry per prompt token (len == prompt_tokens): None below max(1, prompt_logprobs_from),
+    # else the same shape as a ``logprobs`` entry; None when the request did not ask
+    prompt_logprobs: Optional[list] = None
 
 
 class LLMEngine:
@@ -262,7 +287,8 @@ class LLMEngine:
         if self.logprobs:
             if not getattr(runner, "logprobs", False):
                 runner.enable_logprobs()
-            self.stats.update(logprob_requests=0, logprob_steps=0)
+            self.stats.update(logprob_requests=0, logprob_steps=0, prompt_logprob_requests=0, prompt_logprob_rows=0)
+        self._plp_live = 0  # live requests that asked for prompt-token logprobs: 0 = every prefill call is today's
         # per-decode-run device timing (hipEvents around the graph replays, read after the host sync the
         # run ends with anyway): lsa_decode_step_device_seconds{model} = GPU time per token step
         self.device_timing = runner.on_gpu
@@ -304,11 +330,17 @@ class LLMEngine:
             raise SamplingOptionError("min_p must lie in [0, 1]")
         if not isinstance(p.top_logprobs, int) or isinstance(p.top_logprobs, bool) or not 0 <= p.top_logprobs <= 20:
             raise SamplingOptionError("top_logprobs must be an integer in 0 .. 20")
-        if p.top_logprobs and not p.logprobs:
-            raise SamplingOptionError("top_logprobs needs logprobs: true")
-        if p.logprobs and not self.logprobs:
+        if p.top_logprobs and not (p.logprobs or p.prompt_logprobs):
+            raise SamplingOptionError("top_logprobs needs logprobs: true (or prompt_logprobs: true)")
+        if (p.logprobs or p.prompt_logprobs) and not self.logprobs:
             raise SamplingOptionError("this engine was built without per-token logprobs (logprobs=True / "
                                       "LSA_LOGPROBS=1 enables it)")
+        if (isinstance(p.prompt_logprobs_from, bool) or not isinstance(p.prompt_logprobs_from, int)
+                or p.prompt_logprobs_from < 0):
+            raise SamplingOptionError("prompt_logprobs_from must be a non-negative integer")
+        if p.prompt_logprobs and not self.prompt_logprobs_supported:
+            raise SamplingOptionError("prompt_logprobs is not served under tensor parallelism (the sequence-parallel "
+                                      "prefill keeps a share of the rows per rank)")
         dfa = None
         if p.regex is not None:  # compiled here, so that a bad pattern fails the request, not the engine loop
             if not self.guided:
@@ -321,16 +353,58 @@ class LLMEngine:
                       stream=queue.Queue() if stream else None, dfa=dfa)
         if p.logprobs:
             self.stats["logprob_requests"] += 1
+        match_limit = -1
+        if p.prompt_logprobs:
+            self.stats["prompt_logprob_requests"] += 1
+            req.prompt_lp = [None] * len(req.prompt_ids)
+            req.plp_next = max(1, p.prompt_logprobs_from)
+            match_limit = self._plp_match_limit(req)
         if dfa is not None:
             self.stats["guided_requests"] += 1
             REGISTRY.inc("lsa_guided_requests_total", 1, "requests with a regex constraint", model=self.name)
         with self._lock:
-            if self.prefix_cache:
+            if self.prefix_cache and match_limit >= 0:  # the scored rows must be computed, not found in the cache
+                self.sched.add(req.rid, len(req.prompt_ids), p.max_tokens, req.prompt_ids, bool(p.cache_prompt),
+                               match_limit)
+            elif self.prefix_cache:
                 self.sched.add(req.rid, len(req.prompt_ids), p.max_tokens, req.prompt_ids, bool(p.cache_prompt))
             else:
                 self.sched.add(req.rid, len(req.prompt_ids), p.max_tokens)
             self._reqs[req.rid] = req
+            if p.prompt_logprobs:
+                self._plp_live += 1
         return req
+
+    def add_requests(self, prompts: Sequence[Sequence[int]], params: SamplingParams) -> list:
+        """``add_request`` for several prompts under one hold of the engine's lock: a loop thread stepping the engine
+        meanwhile admits them together (one packed prefill, one shared prefix), not the first one alone.  All or none:
+        if a prompt is refused, the ones queued before it are withdrawn and the refusal is raised."""
+        with self._lock:
+            reqs = []
+            try:
+                for ids in prompts:
+                    reqs.append(self.add_request(ids, params))
+            except Exception:
+                for q in reqs:  # still waiting: nothing was admitted while the lock was held
+                    self.sched.finish(q.rid)
+                    self._reqs.pop(q.rid, None)
+                    if q.params.prompt_logprobs:
+                        self._plp_live -= 1
+                raise
+            return reqs
+
+    @property
+    def prompt_logprobs_supported(self) -> bool:
+        """Prompt-token logprobs are served: the engine runs per-token logprobs and is not tensor-parallel."""
+        tp = getattr(self.runner, "tp", None)
+        return bool(self.logprobs) and (tp is None or tp.size == 1)
+
+    def _plp_match_limit(self, q: Request) -> int:
+        """Leading tokens of ``q``'s (resumed) prompt that may come from the prefix cache: the row of position
+        plp_next - 1 is the first that must be computed; -1 = today's rule, once every prompt index is scored."""
+        if q.plp_next >= len(q.prompt_ids):
+            return -1
+        return min(len(q.ctx_ids) - 1, max(0, q.plp_next - 1))
 
     def has_work(self) -> bool:
         return self.sched.num_waiting > 0 or self.sched.num_running > 0 or bool(self._prefilling)
@@ -487,6 +561,8 @@ class LLMEngine:
                 self.stats["logprob_steps"] += n_steps
                 asked = [(q, min(int(gl[i]), q.params.max_tokens)) for i, q in enumerate(reqs) if q.params.logprobs]
                 self._read_logprobs([q for q, _ in asked], [n for _, n in asked])
+            if self._plp_live:  # prompt records of the requests whose first token this sync made host-visible
+                self._read_prompt_logprobs(reqs)
             if ev is not None:
                 dev_s = ev[0].elapsed_time(ev[1]) / 1e3  # both recorded before read_rows' sync
                 self.stats["decode_device_s"] += dev_s
@@ -509,6 +585,8 @@ class LLMEngine:
                         q.stream.put(("tokens", q.resumed + r.tokens_of(q.slot, n)))
                 if int(fin[i]):
                     req = self._reqs.pop(rid)
+                    if req.params.prompt_logprobs:
+                        self._plp_live -= 1
                     req.output_ids = req.resumed + fin_toks[req.slot]
                     n = len(req.output_ids)
                     self._admit_hold = False
@@ -647,6 +725,50 @@ class LLMEngine:
             q.logprobs.extend(rec)
             q.lp_read = n
 
+    def _read_prompt_logprobs(self, reqs: list) -> None:
+        """Move the pending device records of prompt tokens to ``q.prompt_lp`` (one transfer for all of ``reqs``)."""
+        sel = [(q, pend) for q in reqs for pend in q.plp_pending]
+        if not sel:
+            return
+        got = self.runner.prompt_logprobs_of([(rec, a, n, int(q.params.top_logprobs)) for q, (rec, a, n, _) in sel])
+        for (q, (_, _, n, j0)), rows in zip(sel, got):
+            q.prompt_lp[j0:j0 + n] = rows
+        for q in reqs:
+            q.plp_pending = []
+
+    def _score_seg(self, slot: int, a: int, b: int):
+        """The rows of a prefill segment (positions [a, b) of the request in ``slot``) that a prompt-logprob request
+        still has to score: (request, (first row in the segment, K, targets)) or None.  The row of position p gives
+        prompt index p + 1, so the rows are plp_next - 1 .. prompt length - 2, never a row of ``resumed`` tokens."""
+        q = self._reqs.get(self._slot_owner.get(slot, -1))
+        if q is None or not q.params.prompt_logprobs:
+            return None
+        lo, hi = max(a, q.plp_next - 1), min(b, len(q.prompt_ids) - 1)
+        if hi <= lo:
+            return None
+        return q, (lo - a, int(q.params.top_logprobs), q.ctx_ids[lo + 1:hi + 1])
+
+    def _run_prefill(self, batch: list, commit: bool, any_sample: bool = False) -> None:
+        """One runner prefill call.  While no live request asked for prompt logprobs it is today's call; else the
+        segments' rows to score ride along and the call's device records are kept with their requests, unread."""
+        r = self.runner
+        segs = [self._score_seg(slot, p0, p0 + len(ids)) for slot, ids, p0 in batch] if self._plp_live else []
+        if not any(segs):
+            if commit:
+                r.prefill(batch, any_sample)
+            else:
+                r.prefill_chunk(batch)
+            return
+        score = [sg[1] if sg else None for sg in segs]
+        recs = r.prefill(batch, any_sample, score=score) if commit else r.prefill_chunk(batch, score=score)
+        for i, row0, rows in recs[3]:
+            q = segs[i][0]
+            q.plp_pending.append((recs[:3], row0, rows, q.plp_next))
+            q.plp_next += rows
+            self.stats["prompt_logprob_rows"] += rows
+            REGISTRY.inc("lsa_prompt_logprob_tokens_total", rows, "prompt tokens scored (prompt_logprobs)",
+                         model=self.name)
+
     def _lp_piece(self, tid: int) -> tuple:
         """(decoded piece, byte values) of a token id: the bytes come from the tokenizer's ``token_bytes`` table."""
         got = self._lp_pieces.get(tid)
@@ -659,11 +781,20 @@ class LLMEngine:
             got = self._lp_pieces[tid] = (self.tok.decode([tid]), list(raw))
         return got
 
-    def logprob_entries(self, req: Request, token_ids: Sequence[int], start: int = 0) -> list:
-        """The response entries of generated tokens ``token_ids`` = output tokens [start, start + len) of ``req``."""
+    def prompt_logprob_entries(self, req: Request) -> list:
+        """The response list of a request that asked for prompt logprobs: one entry per prompt token, None where no
+        record is defined (index 0 and below prompt_logprobs_from)."""
+        return [None if rec is None else self.logprob_entries(req, [tid], records=[rec])[0]
+                for tid, rec in zip(req.prompt_ids, req.prompt_lp)]
+
+    def logprob_entries(self, req: Request, token_ids: Sequence[int], start: int = 0,
+                        records: Optional[list] = None) -> list:
+        """The response entries of generated tokens ``token_ids`` = output tokens [start, start + len) of ``req``
+        (``records``: of these records instead of the generated tokens')."""
         out = []
+        src = req.logprobs if records is None else records
         for j, tid in enumerate(token_ids):
-            lpv, top = req.logprobs[start + j]
+            lpv, top = src[start + j]
             piece, raw = self._lp_piece(int(tid))
             ent = {"token": piece, "logprob": float(lpv), "bytes": raw}
             if req.params.top_logprobs:
@@ -707,11 +838,20 @@ class LLMEngine:
         if q.params.logprobs:  # its unread records, before the slot goes: they stay with the request on the host
             self._read_logprobs([q], [n])
             q.lp_read = 0
+        if q.plp_pending:  # the prompt records too; the re-admitted request scores only indices from plp_next on
+            self._read_prompt_logprobs([q])
+        if q in self._prefilling:  # not reached by the engine itself: ``_grow_kv`` picks its victims among requests
+            # whose prompt is complete.  A caller that preempts a request in the middle of its chunked prompt (the
+            # tests do, to hold that such a request scores only the prompt indices it lacks) must not leave it there
+            self._prefilling.remove(q)
         q.resumed = q.resumed + toks
         q.params = dataclasses.replace(q.params, max_tokens=q.params.max_tokens - n)
         self.runner.release_slot(q.slot)
         self._slot_owner.pop(q.slot, None)
-        if self.prefix_cache:  # with its tokens, so that the resumed request can hit its own blocks if they survive
+        limit = self._plp_match_limit(q) if q.params.prompt_logprobs else -1
+        if self.prefix_cache and limit >= 0:  # prompt indices still to score: their rows must be computed again
+            self.sched.preempt(q.rid, len(q.ctx_ids), q.params.max_tokens, q.ctx_ids, limit)
+        elif self.prefix_cache:  # with its tokens, so that the resumed request can hit its own blocks if they survive
             self.sched.preempt(q.rid, len(q.ctx_ids), q.params.max_tokens, q.ctx_ids)
         else:
             self.sched.preempt(q.rid, len(q.ctx_ids), q.params.max_tokens)
@@ -755,6 +895,7 @@ class LLMEngine:
                 self.sched.copies_done()
                 self.sched.reset_prefix_cache()
             self._reqs.clear()
+            self._plp_live = 0
             self._slot_owner.clear()
             self._prefilling.clear()
             self.stats["aborted"] += len(out)
@@ -787,7 +928,7 @@ class LLMEngine:
                 if budget <= 0:
                     break
         if partial:  # KV only (no token commit); chunks of different requests pack into one launch sequence
-            self.runner.prefill_chunk(partial)
+            self._run_prefill(partial, False)
         if final:
             self._prefill_packed(final, any_sample)
         if self.prefix_cache:  # the prompt's last chunk is launched: its full blocks may be shared from now on
@@ -797,26 +938,25 @@ class LLMEngine:
 
     def _prefill_packed(self, seqs, any_sample: bool) -> None:
         """Prefill in chunks of at most max_prefill_tokens tokens (long prompts split across calls)."""
-        r = self.runner
         batch, tokens = [], 0
         for slot, ids, p0 in seqs:
             if len(ids) > self.max_prefill_tokens:  # chunked prefill of one long prompt
                 if batch:
-                    r.prefill(batch, any_sample)
+                    self._run_prefill(batch, True, any_sample)
                     batch, tokens = [], 0
                 c = self.max_prefill_tokens
                 for s in range(0, len(ids) - c, c):
-                    r.prefill_chunk([(slot, ids[s:s + c], p0 + s)])
+                    self._run_prefill([(slot, ids[s:s + c], p0 + s)], False)
                 s = ((len(ids) - 1) // c) * c
-                r.prefill([(slot, ids[s:], p0 + s)], any_sample)
+                self._run_prefill([(slot, ids[s:], p0 + s)], True, any_sample)
                 continue
             if tokens + len(ids) > self.max_prefill_tokens and batch:
-                r.prefill(batch, any_sample)
+                self._run_prefill(batch, True, any_sample)
                 batch, tokens = [], 0
             batch.append((slot, ids, p0))
             tokens += len(ids)
         if batch:
-            r.prefill(batch, any_sample)
+            self._run_prefill(batch, True, any_sample)
 
     def run_until_done(self, reqs: Sequence[Request]) -> None:
         while not all(q.done.is_set() for q in reqs):
@@ -836,7 +976,8 @@ class LLMEngine:
             prompt_eval_duration_ns=ns(req.first_token - req.admitted),
             eval_duration_ns=ns(req.finished_at - req.first_token), done_reason="stop" if ended_eos else "length",
             cached_prompt_tokens=req.cached_tokens,
-            logprobs=self.logprob_entries(req, req.output_ids) if req.params.logprobs else None)
+            logprobs=self.logprob_entries(req, req.output_ids) if req.params.logprobs else None,
+            prompt_logprobs=self.prompt_logprob_entries(req) if req.params.prompt_logprobs else None)
 
     def text_of(self, token_ids: Sequence[int], req: Request) -> str:
         """The response text of ``token_ids`` exactly as ``result`` builds it (stop strings applied)."""

@@ -301,6 +301,9 @@ class ModelRunner:
         self._g_host_on: set = set()  # slots whose current request carries a constraint (host mirror of g_on)
         # per-token logprobs (``enable_logprobs``): off = no buffer, launch or graph differs
         self.logprobs = False
+        # prompt-token logprobs: the scored prefill rows go through the lm_head in tiles of at most this many rows (the
+        # transient logits are tile x V x 4 bytes; <= 64 rows take the skinny GEMMs, more the stream-K kernel)
+        self.score_tile_rows = 256
         if self.tp is not None and self.tp.size > 1 and self.on_gpu:
             self.tp.warmup()  # communicators (RCCL + the one-shot IPC all-reduce) before any launch
             if not self.tp.capturable():  # gloo without the IPC kernel (test boxes): eager decode steps
@@ -1262,11 +1265,61 @@ class ModelRunner:
         if not self.logprobs:
             return 0
         ts = (self.lp_k, self.lp_n0, self.lp_tok, self.lp_ids, self.lp_top, self.lp_raw, *self.lp_ws,
-              *(self.__dict__.get("spec_lp_ws") or ()))
+              *(self.__dict__.get("spec_lp_ws") or ()), *(self.__dict__.get("prompt_lp_ws") or ()))
         return sum(t.numel() * t.element_size() for t in ts)
 
     def _logprob_scan(self, logits, lp_k, finished, gen_len, lp_n0) -> None:
         ops.logprob_scan(logits, lp_k, finished, gen_len, self.lp_raw, lp_n0, workspace=self.lp_ws)
+
+    # prompt-token logprobs: teacher-forced scoring of prefill rows (kernels/logprobs.hip, the prompt pair)
+    def _prompt_lp_ws(self, rows: int) -> tuple:
+        """The chunk workspace of one lm_head tile of scored rows (``ops.prompt_logprob_workspace``): allocated by the
+        first prefill that scores, regrown if ``score_tile_rows`` was raised since."""
+        ws = self.__dict__.get("prompt_lp_ws")
+        nch = (self.V + ops.LOGPROB_CHUNK - 1) // ops.LOGPROB_CHUNK
+        if ws is None or ws[0].numel() < rows * nch * 2:
+            ws = self.prompt_lp_ws = ops.prompt_logprob_workspace(rows, self.V, self.device)
+        return ws
+
+    def _prompt_logprob_scan(self, logits, targets, row_k, any_k: bool = True) -> None:
+        ops.prompt_logprob_scan(logits, targets, row_k, workspace=self._prompt_lp_ws(logits.shape[0]), any_k=any_k)
+
+    def _score_rows(self, xs, targets, row_k, any_k: bool) -> tuple:
+        """Records of R scored prefill rows: ``xs`` [R, d] are their final-norm states, ``targets`` / ``row_k`` [R] the
+        token and the K of each.  The rows go through the lm_head in tiles of at most ``score_tile_rows``, each tile
+        followed by the scan / commit pair over the tile's logits.  -> (tok f32 [R], ids int32 [R, 20], top f32
+        [R, 20]) on the device; nothing is synchronised."""
+        R, K, dev = xs.shape[0], ops.LOGPROB_KMAX, self.device
+        tok = torch.zeros(R, dtype=torch.float32, device=dev)
+        ids = torch.full((R, K), -1, dtype=torch.int32, device=dev)
+        top = torch.zeros(R, K, dtype=torch.float32, device=dev)
+        tile = max(1, int(self.score_tile_rows))
+        ws = self._prompt_lp_ws(min(tile, R))
+        # a quantised lm_head is dequantised once for all the tiles of more than 64 rows, not once per tile
+        wf = ops.tile_weight(self.w.lm_head, dev) if min(tile, R) > 64 else None
+        for a in range(0, R, tile):
+            b = min(R, a + tile)
+            logits = ops.linear(xs[a:b], self.w.lm_head, "f32", splitk=1, wf=wf).view(b - a, self.V)
+            self._prompt_logprob_scan(logits, targets[a:b], row_k[a:b], any_k)
+            ops.prompt_logprob_commit(logits, targets[a:b], row_k[a:b], tok[a:b], ids[a:b], top[a:b], workspace=ws,
+                                      any_k=any_k)
+        return tok, ids, top
+
+    def prompt_logprobs_of(self, recs: Sequence[tuple]) -> list[list[tuple]]:
+        """``recs``: (records of one ``prefill`` call, first row, rows, K) per wanted run of rows.  One device -> host
+        transfer; per run a list of (logprob, [(token id, logprob)] * K), the shape ``logprobs_of_many`` gives."""
+        if not recs:
+            return []
+        KM = ops.LOGPROB_KMAX
+        pack = torch.cat([torch.cat([r[0][a:a + n].unsqueeze(-1), r[2][a:a + n], r[1][a:a + n].view(torch.float32)],
+                                    dim=-1) for r, a, n, _ in recs]).cpu()
+        tok, top = pack[:, 0].tolist(), pack[:, 1:1 + KM].tolist()
+        ids = pack[:, 1 + KM:].contiguous().view(torch.int32).tolist()
+        out, o = [], 0
+        for _, _, n, k in recs:
+            out.append([(tok[o + j], list(zip(ids[o + j][:k], top[o + j][:k]))) for j in range(n)])
+            o += n
+        return out
 
     def logprobs_of_many(self, slots: Sequence[int], lo: Sequence[int], hi: Sequence[int]) -> list[list[tuple]]:
         """Records [lo[i], hi[i]) of slot row ``slots[i]`` in one device -> host transfer: per row a list of
@@ -1439,19 +1492,26 @@ class ModelRunner:
         self.block_tables[slot].zero_()
 
     # ------------------------------------------------------------------------------------ prefill
-    def prefill(self, seqs: list[tuple[int, Sequence[int], int]], sample_any: bool = False) -> None:
+    def prefill(self, seqs: list[tuple[int, Sequence[int], int]], sample_any: bool = False,
+                score: Optional[Sequence] = None):
         """Prefill ``seqs`` = [(slot, token_ids, start_pos)] and commit each first token into its slot.
 
         ``start_pos`` > 0 continues a chunked prefill (the cache already holds positions < start_pos);
         only the final chunk of a prompt should be passed with ``commit=True`` semantics — a chunk whose
         prompt continues is passed through ``prefill_chunk``.
+
+        ``score`` (prompt-token logprobs, ``enable_logprobs``): per sequence None or (first scored row, K, targets) --
+        rows first .. first + len(targets) - 1 of the sequence's tokens in this call are scored, row first + k against
+        ``targets[k]`` (the token that follows it in the prompt: the next token of this call, or for its last row the
+        first token of the next chunk, which the caller knows).  Returns None, or the call's device records
+        (tok, ids, top, [(sequence index, first record row, rows)]) for ``prompt_logprobs_of``; no host sync.
         """
-        self._prefill(seqs, commit=True, sample_any=sample_any)
+        return self._prefill(seqs, commit=True, sample_any=sample_any, score=score)
 
-    def prefill_chunk(self, seqs: list[tuple[int, Sequence[int], int]]) -> None:
-        self._prefill(seqs, commit=False)
+    def prefill_chunk(self, seqs: list[tuple[int, Sequence[int], int]], score: Optional[Sequence] = None):
+        return self._prefill(seqs, commit=False, score=score)
 
-    def _prefill(self, seqs, commit: bool, sample_any: bool = False) -> None:
+    def _prefill(self, seqs, commit: bool, sample_any: bool = False, score: Optional[Sequence] = None):
         dev, w, d = self.device, self.w, self.d
         n = len(seqs)
         lens = [len(t) for _, t, _ in seqs]
@@ -1466,7 +1526,22 @@ class ModelRunner:
             tseq.extend([i] * len(t))
         ctx = [p0 + len(t) for _, t, p0 in seqs]
         slots = [s for s, _, _ in seqs]
-        host = torch.tensor(toks + pos + tseq + cu + ctx + [c - 1 for c in cu[1:]], dtype=torch.int32)
+        # scored rows (prompt-token logprobs): packed row index, target token and K of each, known before any launch
+        srow, stgt, sk, smeta = [], [], [], []
+        for i, sc in enumerate(score or ()):
+            if sc is None or not len(sc[2]):
+                continue
+            first, K, tg = int(sc[0]), int(sc[1]), sc[2]
+            assert self.logprobs, "a sequence asks for prompt logprobs but the runner was built without logprobs"
+            assert self.tp is None or self.tp.size == 1, "prompt logprobs are not served under tensor parallelism"
+            assert 0 <= first and first + len(tg) <= lens[i] and 0 <= K <= ops.LOGPROB_KMAX, (first, len(tg), lens[i], K)
+            smeta.append((i, len(srow), len(tg)))
+            srow.extend(range(cu[i] + first, cu[i] + first + len(tg)))
+            stgt.extend(int(x) for x in tg)
+            sk.extend([K] * len(tg))
+        R = len(srow)
+        host = torch.tensor(toks + pos + tseq + cu + ctx + [c - 1 for c in cu[1:]] + srow + stgt + sk,
+                            dtype=torch.int32)
         if self.on_gpu:
             host = host.pin_memory()
         dv = host.to(dev, non_blocking=True)
@@ -1477,6 +1552,9 @@ class ModelRunner:
         cud = dv[o:o + n + 1]; o += n + 1
         ctxd = dv[o:o + n]; o += n
         last = dv[o:o + n]
+        if R:  # the final norm gathers the scored rows behind (commit) or instead of (chunk) the last rows, in one launch
+            last = dv[o:o + n + R] if commit else dv[o + n:o + n + R]
+            tgt_d, k_d = dv[o + n + R:o + n + 2 * R], dv[o + n + 2 * R:o + n + 3 * R]
         slot_t = torch.tensor(slots, dtype=torch.long, device=dev)
         bt = self.block_tables.index_select(0, slot_t)
         for i, sl in enumerate(slots):  # deferred tables: prefill writes through them; the commit publishes
@@ -1497,9 +1575,14 @@ class ModelRunner:
         if self.seq_parallel and tps > 1 and T >= self.sp_min_tokens:
             xl = self._prefill_layers_sp(T, ids, posd, tsd, bt, cud, ctxd, last, work, n, commit)
         else:
-            xl = self._prefill_layers(T, ids, posd, tsd, bt, cud, ctxd, last, work, n, commit)
+            xl = self._prefill_layers(T, ids, posd, tsd, bt, cud, ctxd, last, work, last.numel() if R else n,
+                                      commit or R > 0)
+        recs = None
+        if R:
+            recs = (*self._score_rows(xl[-R:], tgt_d, k_d, max(sk) > 0), smeta)
+            xl = xl[:n]
         if not commit:
-            return
+            return recs
         logits = self._lm_head(xl, n)
         # commit the first generated token of each sequence into its slot row
         i32 = dict(dtype=torch.int32, device=dev)
@@ -1547,9 +1630,12 @@ class ModelRunner:
         self.input_ids.index_copy_(0, slot_t, iid)
         self.positions.index_copy_(0, slot_t, pp + fin if self.park_past_prompt else pp)
         self.finished.index_copy_(0, slot_t, fin)
+        return recs
 
     def _prefill_layers(self, T, ids, posd, tsd, bt, cud, ctxd, last, work, n, commit):
-        """Prefill layer stack with full-sequence residuals; returns the last rows' normalised states."""
+        """Prefill layer stack with full-sequence residuals; returns the normalised states of the n rows ``last``
+        names (each sequence's last row, and / or the rows a prompt-logprob request scores), None when not ``commit``
+        (a chunk that neither commits a token nor scores a row)."""
         dev, w, d = self.device, self.w, self.d
         f32 = dict(dtype=torch.float32, device=dev)
         bf = dict(dtype=torch.bfloat16, device=dev)

@@ -666,9 +666,11 @@ PREFILL_XF = os.environ.get("LSA_PREFILL_XF", "1") != "0"
 
 def linear(x: torch.Tensor, w: PackedWeight, epi: str = "bf16", out: Optional[torch.Tensor] = None,
            splitk: Optional[int] = None, nb: Optional[int] = None, waves: Optional[int] = None,
-           div: Optional[int] = None, rownorm=None, res=None, _xf: bool = False) -> torch.Tensor:
+           div: Optional[int] = None, rownorm=None, res=None, _xf: bool = False,
+           wf: Optional[torch.Tensor] = None) -> torch.Tensor:
     """y = x @ W^T with a fused epilogue.  epi='f32' returns [splitk, M, N] partial slabs.
-    rownorm / res (epi='res'): the decode epilogue extensions, see ``_epi_kw``."""
+    rownorm / res (epi='res'): the decode epilogue extensions, see ``_epi_kw``.  wf: ``tile_weight(w, device)`` of a
+    caller that runs several M > 64 products over one weight, so that a quantised weight is dequantised once."""
     M, K = x.shape
     assert K == w.K, (K, w.K)
     assert (epi == "res") == (res is not None), "epi='res' needs res=(h, xout, ss_out)"
@@ -691,7 +693,8 @@ def linear(x: torch.Tensor, w: PackedWeight, epi: str = "bf16", out: Optional[to
         if out is None:
             out = torch.empty(*((1, M, w.N) if epi == "f32" else (M, w.N // 2 if epi == "silu" else w.N)),
                               device=x.device, dtype=torch.float32 if epi == "f32" else torch.bfloat16)
-        wf = w.data if w.kind == "bf16" else _dequant_scratch(w, x.device)
+        if wf is None:
+            wf = w.data if w.kind == "bf16" else _dequant_scratch(w, x.device)
         return gemm_sk(x, wf, w.N, out, epi)
     nb0, sk0, wv0, dv0 = pick_gemm_config(M, w.N, K, epi, kind=w.kind)
     nb = nb0 if nb is None else nb
@@ -726,6 +729,16 @@ def linear(x: torch.Tensor, w: PackedWeight, epi: str = "bf16", out: Optional[to
 
 
 FP8_W8A8 = os.environ.get("LSA_FP8_W8A8", "1") != "0"
+
+
+def tile_weight(w: PackedWeight, device) -> Optional[torch.Tensor]:
+    """The bf16 fragment-layout weight the stream-K route of ``linear`` (M > 64) multiplies by, for a caller that runs
+    several such products over ``w`` back to back and passes it on as ``linear(..., wf=)``: the weight itself (bf16),
+    one dequantisation into the stream's scratch (MXFP4; fp8 where the W8A8 tile kernel does not apply), or None where
+    that route is not taken (CPU, W8A8 fp8).  Valid until the next dequantisation on the same stream."""
+    if torch.device(device).type != "cuda" or (w.kind == "fp8" and FP8_W8A8 and w.K % 128 == 0):
+        return None
+    return w.data if w.kind == "bf16" else _dequant_scratch(w, device)
 
 
 def _dequant_scratch(w: PackedWeight, device) -> torch.Tensor:
@@ -1621,6 +1634,67 @@ def logprob_commit(lp_raw, lp_k, lp_n0, gen_len, out_tokens, lp_tok, lp_ids, lp_
     if workspace is None:
         raise ValueError("logprob_commit: the device path needs logprob_scan's workspace")
     ext().logprob_commit(lp_raw, workspace[0], workspace[1], lp_k, lp_n0, gen_len, out_tokens, lp_tok, lp_ids, lp_top, B)
+
+
+def prompt_logprob_workspace(R: int, V: int, device) -> tuple:
+    """(ms f32 [R * nch * 2], cand int64 [R * nch * 32]), nch = ceil(V / 2048): what ``prompt_logprob_scan`` hands
+    ``prompt_logprob_commit`` for up to R scored rows (the raw rows stay in ``logits``: no copy)."""
+    return logprob_workspace(R, V, device)
+
+
+def _prompt_logprob_check(op: str, logits, targets, row_k, extra: dict) -> tuple:
+    """The refusals both prompt ops make before any launch (``_logprob_check``'s; the binding repeats them)."""
+    if logits.dim() != 2:
+        raise ValueError(f"{op}: logits must be [R, V]")
+    R, V = logits.shape
+    i32, f32 = torch.int32, torch.float32
+    _logprob_check(op, R, V, dict({"logits": (logits, f32), "targets": (targets, i32), "row_k": (row_k, i32)}, **extra),
+                   logits)
+    if targets.dim() != 1 or row_k.dim() != 1 or targets.shape[0] != R or row_k.shape[0] != R:
+        raise ValueError(f"{op}: targets / row_k must be [{R}]")
+    return R, V
+
+
+def _prompt_ws_check(op: str, R: int, V: int, workspace) -> None:
+    nch = (V + LOGPROB_CHUNK - 1) // LOGPROB_CHUNK
+    if (workspace is None or len(workspace) != 2 or workspace[0].dtype != torch.float32
+            or workspace[1].dtype != torch.int64 or workspace[0].numel() < R * nch * 2
+            or workspace[1].numel() < R * nch * LOGPROB_CAND):
+        raise ValueError(f"{op}: the device path needs prompt_logprob_workspace of at least {R} rows")
+
+
+def prompt_logprob_scan(logits, targets, row_k, workspace=None, any_k: bool = True):
+    """First half of a prompt-token logprob record (kernels/logprobs.hip prompt_logprob_scan_kernel), right after the
+    lm_head of R scored prefill rows: for every row with a target (``targets[r] >= 0``) the chunk partials of its
+    log-sum-exp and -- ``any_k``: some ``row_k[r] > 0``, a launch-level switch the host decides -- its per-chunk best 32
+    go into ``workspace`` (``prompt_logprob_workspace``).  ``logits`` is only read and must stay intact until
+    ``prompt_logprob_commit`` has read it."""
+    R, V = _prompt_logprob_check("prompt_logprob_scan", logits, targets, row_k, {})
+    if not _gpu(logits):
+        return ref.prompt_logprob_scan(logits, targets, row_k)
+    _prompt_ws_check("prompt_logprob_scan", R, V, workspace)
+    ext().prompt_logprob_scan(logits, targets, row_k, bool(any_k), workspace[0], workspace[1])
+
+
+def prompt_logprob_commit(logits, targets, row_k, dst_tok, dst_ids, dst_top, workspace=None, any_k: bool = True):
+    """Second half: row r with a target records ``dst_tok[r]`` (the log-probability of ``targets[r]`` under the row's
+    softmax) and its K = min(row_k[r], dst_ids.shape[1]) most likely tokens into ``dst_ids / dst_top[r, :K]``
+    (``ops.reference.prompt_logprob_commit`` states the rule, ``logprob_rows`` the values); rows without a target
+    write nothing.  ``any_k`` must be what the scan was given: without it every row records with K = 0."""
+    R, V = _prompt_logprob_check("prompt_logprob_commit", logits, targets, row_k,
+                                 {"dst_tok": (dst_tok, torch.float32), "dst_ids": (dst_ids, torch.int32),
+                                  "dst_top": (dst_top, torch.float32)})
+    if dst_ids.dim() != 2 or not 0 <= dst_ids.shape[1] <= LOGPROB_KMAX:
+        raise ValueError(f"prompt_logprob_commit: top_logprobs K must be in 0 .. {LOGPROB_KMAX}")
+    if dst_tok.dim() != 1 or dst_tok.shape[0] != R or dst_ids.shape != dst_top.shape or dst_ids.shape[0] != R:
+        raise ValueError("prompt_logprob_commit: record buffers must be [R] / [R, K]")
+    if not _gpu(logits):
+        if not any_k:
+            row_k = torch.zeros_like(row_k)
+        return ref.prompt_logprob_commit(logits, targets, row_k, dst_tok, dst_ids, dst_top)
+    _prompt_ws_check("prompt_logprob_commit", R, V, workspace)
+    ext().prompt_logprob_commit(logits, workspace[0], workspace[1], targets, row_k, bool(any_k), dst_tok, dst_ids,
+                                dst_top)
 
 
 LOGPROB_SPEC_ROWS = ref.LOGPROB_SPEC_ROWS

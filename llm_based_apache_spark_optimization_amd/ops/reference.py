@@ -386,6 +386,29 @@ def spec_logprob_commit(T: int, lp_k, lp_n0, gen_len, out_tokens, lp_tok, lp_ids
                 lp_top[s, n, :K] = top[0]
 
 
+def prompt_logprob_scan(logits, targets, row_k):
+    """Host twin of prompt_logprob_scan_kernel (state level): the scan of scored prefill rows keeps nothing but chunk
+    partials the commit reads, so on the host it is the statement that ``logits`` is not modified."""
+    return None
+
+
+def prompt_logprob_commit(logits, targets, row_k, dst_tok, dst_ids, dst_top):
+    """Host twin of prompt_logprob_commit_kernel.  Row r of ``logits`` [R, V] records exactly when it has a target
+    (``targets[r] >= 0``): ``dst_tok[r]`` and, for K = min(row_k[r], dst_ids.shape[1]) > 0, ``dst_ids / dst_top
+    [r, :K]`` -- ``logprob_rows`` of the row as it stands and ``targets[r]``, the rule of a generated-token record.
+    Nothing else is written."""
+    for r in range(logits.shape[0]):
+        tok = int(targets[r])
+        if tok < 0:
+            continue
+        K = max(0, min(int(row_k[r]), dst_ids.shape[1]))
+        chosen, ids, top = logprob_rows(logits[r:r + 1], [tok], K)
+        dst_tok[r] = chosen[0]
+        if K > 0:
+            dst_ids[r, :K] = ids[0]
+            dst_top[r, :K] = top[0]
+
+
 # ----------------------------------------------------------------------------------- regex-constrained decoding
 DFA_DEAD = 0xFFFF
 DFA_MAX_TABLE = 32768

@@ -96,7 +96,7 @@ class _PyScheduler:
         self._clock = 0
         self._copies, self._pins = [], []
 
-    def add(self, rid, prompt_len, max_new, tokens=(), cacheable=True):
+    def add(self, rid, prompt_len, max_new, tokens=(), cacheable=True, match_limit=-1):
         if rid in self._reqs:
             raise ValueError("duplicate request id")
         if prompt_len < 1 or max_new < 1:
@@ -111,7 +111,8 @@ class _PyScheduler:
             raise ValueError("tokens must hold prompt_len ids")
         self._reqs[rid] = {"p": prompt_len, "n": max_new, "slot": -1, "blocks": [], "seq": -1,
                            "tokens": [int(t) for t in tokens] if cache else [], "cacheable": cache,
-                           "published": False, "cached": 0, "nodes": []}
+                           "published": False, "cached": 0, "nodes": [],
+                           "match_limit": int(match_limit) if cache else -1}
         self._waiting.append(rid)
 
     def _admit_blocks(self, r):
@@ -147,17 +148,19 @@ class _PyScheduler:
 
     def _match(self, r):
         """(chain, src, p): the longest chain of cached blocks that prefixes the prompt (at least the last prompt
-        token stays to be computed), then the best partial match among the last node's children (the fork)."""
+        token stays to be computed, and no more than the request's ``match_limit`` tokens are served), then the best
+        partial match among the last node's children (the fork), under the same cap."""
         bs, toks = self._alloc.block_size, r["tokens"]
+        cap = r["p"] - 1 if r["match_limit"] < 0 else min(r["match_limit"], r["p"] - 1)
         chain, node = [], 0
-        for i in range((r["p"] - 1) // bs):
+        for i in range(cap // bs):
             c = self._find_child(node, tuple(toks[i * bs:(i + 1) * bs]))
             if c < 0:
                 break
             chain.append(c)
             node = c
         base = len(chain) * bs
-        limit = min(bs - 1, r["p"] - 1 - base)
+        limit = min(bs - 1, cap - base)
         best, src = 0, -1
         for c in self._nodes[node]["children"]:
             t, p = self._nodes[c]["toks"], 0
@@ -314,7 +317,7 @@ class _PyScheduler:
         r["blocks"] += self._take(add)
         return add
 
-    def preempt(self, rid, prompt_len, max_new, tokens=()):
+    def preempt(self, rid, prompt_len, max_new, tokens=(), match_limit=-1):
         r = self._reqs[rid]
         if r["slot"] < 0:
             raise ValueError("preempt: request is not running")
@@ -324,7 +327,7 @@ class _PyScheduler:
             raise ValueError("tokens must hold prompt_len ids")
         self._slots[r["slot"]] = -1
         self._release_blocks(r)
-        r.update(slot=-1, seq=-1, p=prompt_len, n=max_new)
+        r.update(slot=-1, seq=-1, p=prompt_len, n=max_new, match_limit=int(match_limit))
         if r["cacheable"]:
             r["tokens"] = [int(t) for t in tokens]
         self._waiting.appendleft(rid)

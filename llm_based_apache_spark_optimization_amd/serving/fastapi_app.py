@@ -68,12 +68,27 @@ class GenerateRequest(BaseModel):
     # per-token logprobs: Ollama's top-level request fields (also accepted inside ``options``)
     logprobs: Optional[bool] = None
     top_logprobs: Optional[int] = None
+    # prompt-token logprobs (OpenAI's echo + logprobs), next to them; prompt_logprobs_from travels in ``options``
+    prompt_logprobs: Optional[bool] = None
 
     def merged_options(self) -> Optional[dict]:
-        if self.logprobs is None and self.top_logprobs is None:
+        if self.logprobs is None and self.top_logprobs is None and self.prompt_logprobs is None:
             return self.options
-        top = {k: v for k, v in (("logprobs", self.logprobs), ("top_logprobs", self.top_logprobs)) if v is not None}
+        top = {k: v for k, v in (("logprobs", self.logprobs), ("top_logprobs", self.top_logprobs),
+                                 ("prompt_logprobs", self.prompt_logprobs)) if v is not None}
         return dict(self.options or {}, **top)
+
+
+class ScoreRequest(BaseModel):
+    """Teacher-forced scoring: the log-likelihood of ``completion`` / each of ``completions`` after the prompt."""
+    model: str
+    prompt: str = ""
+    system: str = ""
+    raw: bool = False
+    completion: Optional[str] = None
+    completions: Optional[list[str]] = None
+    top_logprobs: int = 0
+    options: Optional[dict] = None
 
 
 def create_app(ctx: Optional[AppContext] = None) -> FastAPI:
@@ -183,6 +198,24 @@ def create_app(ctx: Optional[AppContext] = None) -> FastAPI:
         r = ctx.backend.generate(req.model, req.prompt, req.system, req.merged_options(), req.raw)
         record_generation(r, "api_generate")
         return r.to_dict()
+
+    @app.post("/api/score")
+    def api_score(req: ScoreRequest):
+        # what the engine refuses (no logprobs, TP > 1, an empty completion, more than 64 of them, a sequence that does
+        # not fit the context window: scoring never truncates) is a SamplingOptionError: 400 through the handler above
+        t0 = time.perf_counter()
+        if (req.completion is None) == (req.completions is None):
+            raise HTTPException(400, "exactly one of completion and completions is required")
+        comps = [req.completion] if req.completions is None else list(req.completions)
+        if not comps:
+            raise HTTPException(400, "completions is empty")
+        try:
+            out = ctx.backend.score(req.model, req.prompt, comps, req.system, req.options, req.raw, req.top_logprobs)
+        except NotImplementedError:
+            raise HTTPException(501, "this backend does not score completions") from None
+        REGISTRY.observe("lsa_request_seconds", time.perf_counter() - t0, "e2e latency", route="api_score")
+        REGISTRY.inc("lsa_requests_total", 1, "requests", route="api_score", outcome="ok")
+        return out
 
     @app.get("/api/tags")
     def api_tags():
