@@ -51,6 +51,16 @@ PYBIND11_MODULE(_lsa_runtime, m) {
       .def("grow", &Scheduler::grow, py::arg("id"), py::arg("tokens"))
       .def("preempt", &Scheduler::preempt, py::arg("id"), py::arg("prompt_len"), py::arg("max_new"),
            py::arg("tokens") = std::vector<int>(), py::arg("match_limit") = -1)
+      .def("shift",
+           [](Scheduler& s, long long id, int keep, int discard) -> py::object {  // (moves, table), None = refused
+             const Scheduler::ShiftPlan p = s.shift(id, keep, discard);
+             if (!p.ok) return py::none();
+             py::list moves;
+             for (const auto& mv : p.moves) moves.append(py::make_tuple(mv[0], mv[1], mv[2], mv[3], mv[4]));
+             return py::make_tuple(moves, p.table);
+           },
+           py::arg("id"), py::arg("keep"), py::arg("discard"))
+      .def("shift_done", &Scheduler::shift_done)
       .def("cached_tokens", &Scheduler::cached_tokens)
       .def("shared_blocks", &Scheduler::shared_blocks)
       .def("take_copies", &Scheduler::take_copies)

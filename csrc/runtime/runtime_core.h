@@ -297,6 +297,79 @@ class Scheduler {
     reqs_.erase(it);
   }
 
+  // ---------------------------------------------------------------------------------- context shift
+  // Plan of one context shift (shift): the KV moves (src block, dst block, row_lo, row_hi, delta) for ops.kv_shift
+  // and the request's new block table.  ok = false: refused, nothing changed.
+  struct ShiftPlan {
+    bool ok = false;
+    std::vector<std::vector<int>> moves;
+    std::vector<int> table;
+  };
+
+  // Drop the tokens at positions [keep, keep + discard) of a running request's cache, discard a positive multiple of
+  // the block size: the token at old position p >= keep + discard moves to p - discard, i.e. down discard / bs table
+  // entries in the same row of its block, its K rotated by -discard.  For each new logical block j >= keep / bs the
+  // rows come from old logical block j + discard / bs -- except rows below keep % bs of block keep / bs, which are
+  // copied from old block keep / bs (delta 0).  The destination is the source block itself when the request owns it
+  // privately (the rotation is then in place), else a fresh block: a block the index holds is never written (the
+  // invariant above).  Blocks below keep / bs stay as they are and may stay shared; from keep / bs on every block of
+  // the new table is private.  Every other old block is released: private ones to the free list, index nodes
+  // unreferenced -- a suffix of the request's chain, so a holder still holds every ancestor.  Fresh blocks are taken
+  // first (evicting unreferenced cached blocks as grow does); if the arena cannot supply them the plan is refused and
+  // nothing changes.  The released blocks are still read by the planned moves, so they stay out of the free list,
+  // and the nodes referenced, until shift_done(), which the engine calls once the moves are enqueued.
+  ShiftPlan shift(long long id, int keep, int discard) {
+    Req& r = reqs_.at(id);
+    const int bs = alloc_.block_size(), nb = (int)r.blocks.size();
+    if (r.slot < 0) throw std::invalid_argument("shift: request is not running");
+    if (keep < 0 || discard <= 0 || discard % bs) throw std::invalid_argument("shift: bad keep or discard");
+    const int k0 = keep / bs, rem = keep % bs, m = discard / bs, shared = (int)r.nodes.size();
+    if (k0 + m >= nb) throw std::invalid_argument("shift: nothing left behind the discarded tokens");
+    ShiftPlan plan;
+    int fresh = 0;
+    for (int j = k0; j + m < nb; ++j) fresh += (j + m) < shared;
+    if (available() < fresh) return plan;
+    const std::vector<int> got = take(fresh);
+    plan.ok = true;
+    plan.table.assign(r.blocks.begin(), r.blocks.begin() + k0);
+    int g = 0;
+    for (int j = k0; j + m < nb; ++j) {
+      const int src = r.blocks[j + m], dst = (j + m) < shared ? got[g++] : src;
+      if (j == k0 && rem) {
+        plan.moves.push_back({r.blocks[k0], dst, 0, rem, 0});
+        plan.moves.push_back({src, dst, rem, bs, discard});
+      } else {
+        plan.moves.push_back({src, dst, 0, bs, discard});
+      }
+      plan.table.push_back(dst);
+    }
+    for (int j = k0; j < nb; ++j) {  // old blocks that the new table does not keep
+      if (j < shared) shift_nodes_.push_back(r.nodes[j]);
+      else if (j < k0 + m) shift_blocks_.push_back(r.blocks[j]);
+    }
+    if (shared > k0) r.nodes.resize(k0);
+    r.blocks = plan.table;
+    r.published = true;  // the blocks of a shifted cache are never published: only a prompt's prefill publishes
+    return plan;
+  }
+
+  // The moves of every shift() since the last call are enqueued: release what they still read.
+  void shift_done() {
+    if (!shift_blocks_.empty()) alloc_.release(shift_blocks_);
+    shift_blocks_.clear();
+    if (!shift_nodes_.empty()) {
+      ++clock_;
+      for (auto it = shift_nodes_.rbegin(); it != shift_nodes_.rend(); ++it) {  // leaf first
+        nodes_[*it].tick = clock_;
+        unref_node(*it);
+      }
+    }
+    shift_nodes_.clear();
+  }
+
+  // private blocks released by shift() and not yet returned by shift_done() (tests: they are in nobody's table)
+  int shift_held_blocks() const { return (int)shift_blocks_.size(); }
+
   // ---------------------------------------------------------------------------------- prefix cache
   // Prompt tokens of a running request whose KV was found in the cache at its admission (shared blocks + fork).
   int cached_tokens(long long id) const { return reqs_.at(id).cached; }
@@ -527,4 +600,6 @@ class Scheduler {
   long long clock_ = 0;
   std::vector<std::pair<int, int>> copies_;
   std::vector<int> pins_;
+  // context shift: private blocks / index nodes released by shift(), held until shift_done()
+  std::vector<int> shift_blocks_, shift_nodes_;
 };

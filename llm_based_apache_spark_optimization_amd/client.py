@@ -58,9 +58,13 @@ class GenerateResponse:
     # response that did not ask to ``dataclasses.fields`` less ``logprobs``; ``to_dict`` adds the key when it is set, and
     # ``dataclasses.replace`` carries the attribute over (it reads an InitVar that has a default from the object)
     prompt_logprobs: dataclasses.InitVar[Optional[list]] = None
+    # context shifts of the request, on an engine that runs context shift (None, and no key, on any other); an
+    # init-only argument for the same reason
+    context_shifts: dataclasses.InitVar[Optional[int]] = None
 
-    def __post_init__(self, prompt_logprobs=None):
+    def __post_init__(self, prompt_logprobs=None, context_shifts=None):
         self.prompt_logprobs = prompt_logprobs
+        self.context_shifts = context_shifts
 
     def __getitem__(self, k):
         return getattr(self, k)
@@ -74,6 +78,8 @@ class GenerateResponse:
             del d["logprobs"]
         if self.prompt_logprobs is not None:
             d["prompt_logprobs"] = self.prompt_logprobs
+        if self.context_shifts is not None:
+            d["context_shifts"] = self.context_shifts
         return d
 
     @property
@@ -286,7 +292,8 @@ class EngineService(Backend):
                                 prompt_eval_count=r.prompt_tokens, prompt_eval_duration=r.prompt_eval_duration_ns,
                                 eval_count=r.eval_count, eval_duration=r.eval_duration_ns,
                                 prompt_cached_count=r.cached_prompt_tokens, logprobs=r.logprobs,
-                                prompt_logprobs=r.prompt_logprobs)
+                                prompt_logprobs=r.prompt_logprobs,
+                                context_shifts=r.context_shifts if getattr(eng, "context_shift", False) else None)
 
     def generate(self, model, prompt, system="", options=None, raw=False) -> GenerateResponse:
         eng, req = self._submit(model, prompt, system, options, raw)
@@ -392,6 +399,7 @@ class EngineService(Backend):
                                 "prompt_logprobs": bool(getattr(lp.engine, "prompt_logprobs_supported", False)),
                                 "spec_logprobs": bool(getattr(getattr(lp.engine, "runner", None),
                                                               "spec_logprobs", False)),
+                                "context_shift": bool(getattr(lp.engine, "context_shift", False)),
                                 **lp.engine.stats} for m, lp in self._loops.items()}}
 
 
@@ -445,7 +453,7 @@ class RemoteBackend(Backend):
         req = urllib.request.Request(self.url + "/api/generate", data=body, headers={"Content-Type": "application/json"})
         with urllib.request.urlopen(req, timeout=self.timeout_s) as f:
             d = json.loads(f.read())
-        fields = {f.name for f in dataclasses.fields(GenerateResponse)} | {"prompt_logprobs"}
+        fields = {f.name for f in dataclasses.fields(GenerateResponse)} | {"prompt_logprobs", "context_shifts"}
         return GenerateResponse(**{k: v for k, v in d.items() if k in fields})
 
     def score(self, model, prompt, completions, system="", options=None, raw=False, top_logprobs=0) -> dict:

@@ -95,6 +95,10 @@ class Settings:
     # a request that asked for logprobs speculates too (off: it takes plain steps and makes a spec_batch run plain).
     # Needs logprobs and spec_tokens; the records are the log-softmax of the raw verify rows
     spec_logprobs: bool = dataclasses.field(default_factory=lambda: _env("SPEC_LOGPROBS", False, bool))
+    # context shift (off by default): a request that fills its num_ctx window keeps its first num_keep tokens, drops
+    # half of the rest and goes on generating, as Ollama does, instead of ending at the window; the option extension
+    # "shift": false opts a request out.  Inert on the fp8 KV cache and with tp > 1
+    context_shift: bool = dataclasses.field(default_factory=lambda: _env("CONTEXT_SHIFT", False, bool))
     tp: int = dataclasses.field(default_factory=lambda: _env("TP", 1, int))
     dp: int = dataclasses.field(default_factory=lambda: _env("DP", 1, int))
     max_batch: int = dataclasses.field(default_factory=lambda: _env("MAX_BATCH", 32, int))

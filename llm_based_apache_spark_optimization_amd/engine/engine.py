@@ -51,6 +51,12 @@ def _top_logprobs_option(v) -> int:
         raise SamplingOptionError("top_logprobs must be an integer in 0 .. 20") from None
 
 
+def _shift_option(v) -> bool:
+    if not isinstance(v, bool):
+        raise SamplingOptionError("shift must be a boolean")
+    return v
+
+
 def _prompt_logprobs_from_option(v) -> int:
     if v is None:
         return 0
@@ -110,6 +116,10 @@ class SamplingParams:
     # entries below are null.  top_logprobs applies to them as to generated tokens.  Generation is what it is without.
     prompt_logprobs: bool = False
     prompt_logprobs_from: int = 0
+    # context shift, where the engine runs it (LLMEngine(context_shift=True)): a request that fills its num_ctx window
+    # keeps its first num_keep tokens, drops half of the rest and goes on, as Ollama does; the Ollama option extension
+    # "shift": false opts a request out -- it then ends at the window
+    shift: bool = True
 
     @property
     def needs_sampler(self) -> bool:
@@ -142,7 +152,8 @@ class SamplingParams:
                               logprobs=bool(opts.get("logprobs", False)),
                               top_logprobs=_top_logprobs_option(opts.get("top_logprobs", 0)),
                               prompt_logprobs=bool(opts.get("prompt_logprobs", False)),
-                              prompt_logprobs_from=_prompt_logprobs_from_option(opts.get("prompt_logprobs_from")))
+                              prompt_logprobs_from=_prompt_logprobs_from_option(opts.get("prompt_logprobs_from")),
+                              shift=_shift_option(opts.get("shift", True)))
 
 
 @dataclasses.dataclass
@@ -186,11 +197,32 @@ class Request:
     prompt_lp: list = dataclasses.field(default_factory=list)
     plp_next: int = 0
     plp_pending: list = dataclasses.field(default_factory=list)
+    # context shift (LLMEngine(context_shift=True)): shift_w = the window W of an eligible request, 0 = it ends at its
+    # window; shifted = tokens discarded from its cache so far; drops = the (keep, discard) of each shift, in order --
+    # the host mirror of the context as the cache holds it is ``kept_ids``
+    shift_w: int = 0
+    shifted: int = 0
+    drops: list = dataclasses.field(default_factory=list)
 
     @property
     def ctx_ids(self) -> list:
-        """Tokens the current incarnation prefills: the prompt plus anything generated before a preemption."""
+        """The prompt plus anything generated before a preemption: what the current incarnation prefills, unless the
+        request has shifted its context (``kept_ids``)."""
         return self.prompt_ids + self.resumed if self.resumed else self.prompt_ids
+
+    @property
+    def base(self) -> int:
+        """Context length of the current incarnation less its generated tokens: context = base + gen_host."""
+        return len(self.prompt_ids) + len(self.resumed) - self.shifted
+
+    @property
+    def kept_ids(self) -> list:
+        """``ctx_ids`` as the cache holds it: every shift's slice [keep, keep + discard) dropped, in order.  It is what
+        a preempted request re-prefills; len(kept_ids) == base once the shifted tokens are all in ``resumed``."""
+        ids = self.ctx_ids
+        for keep, d in self.drops:
+            ids = ids[:keep] + ids[keep + d:]
+        return ids
 
 
 @dataclasses.dataclass
@@ -205,6 +237,7 @@ class GenerationResult:
     eval_duration_ns: int
     done_reason: str
     cached_prompt_tokens: int = 0  # prompt tokens served from the prefix cache instead of being prefilled
+    context_shifts: int = 0  # times the request's context was shifted at its num_ctx window (context_shift engines)
     # params.logprobs: one {"token", "logprob", "bytes", "top_logprobs": [{"token", "logprob", "bytes"}]} per generated
     # token (len == eval_count); None when the request did not ask
     logprobs: Optional[list] = None
@@ -217,7 +250,7 @@ class LLMEngine:
     def __init__(self, runner: ModelRunner, tokenizer=None, max_prefill_tokens: int = 16384, sync_every: int = 8,
                  name: Optional[str] = None, prefill_chunk: Optional[int] = None, kv_reserve_tokens: int = BLOCK,
                  spec_tokens: int = 0, prefix_cache: bool = False, prefix_cow_min_tokens: Optional[int] = None,
-                 guided: bool = False, spec_batch: int = 0, logprobs: bool = False):
+                 guided: bool = False, spec_batch: int = 0, logprobs: bool = False, context_shift: bool = False):
         self.runner = runner
         if spec_tokens:  # speculative decoding for batch-1 greedy requests (the runner clamps it to what it supports)
             runner.spec_tokens = int(spec_tokens)
@@ -289,6 +322,14 @@ class LLMEngine:
                 runner.enable_logprobs()
             self.stats.update(logprob_requests=0, logprob_steps=0, prompt_logprob_requests=0, prompt_logprob_rows=0)
         self._plp_live = 0  # live requests that asked for prompt-token logprobs: 0 = every prefill call is today's
+        # context shift (SamplingParams.shift): a request that fills its window drops half of its context and goes on
+        # (``_shift_contexts``).  The flag is inert -- requests end at the window -- on the fp8 KV cache (the re-rotation
+        # kernel takes bf16 rows) and under tensor parallelism; off (the default) nothing is launched or counted
+        tp = getattr(runner, "tp", None)
+        self.context_shift = bool(context_shift) and getattr(runner, "kv_scale", None) is None and \
+            (tp is None or tp.size == 1)
+        if self.context_shift:
+            self.stats.update(context_shifts=0, context_shift_tokens=0)
         # per-decode-run device timing (hipEvents around the graph replays, read after the host sync the
         # run ends with anyway): lsa_decode_step_device_seconds{model} = GPU time per token step
         self.device_timing = runner.on_gpu
@@ -301,8 +342,9 @@ class LLMEngine:
     def fit_context(ids: Sequence[int], num_ctx: int, num_keep: int = 4) -> list[int]:
         """Ollama's ``num_ctx`` window: a prompt of more than num_ctx - 1 tokens keeps its
         first ``num_keep`` tokens (BOS + template head) and its tail, dropping the middle, so at least one
-        token can be generated.  Generation then stops at the window (``add_request`` caps max_tokens);
-        Ollama would shift the context instead."""
+        token can be generated.  Generation then stops at the window (``add_request`` caps max_tokens) --
+        unless the engine runs context shift (``context_shift=True``): an eligible request then drops half of the
+        context past its first ``num_keep`` tokens and goes on, as Ollama does (``_shift_contexts``)."""
         limit = max(1, int(num_ctx) - 1)
         ids = list(ids)
         if len(ids) <= limit:
@@ -322,7 +364,15 @@ class LLMEngine:
         room = window - len(prompt_ids)
         if room < 1:
             raise ValueError("prompt longer than the model context")
-        p = dataclasses.replace(params, max_tokens=max(1, min(params.max_tokens, room, self.runner.max_new_cap)))
+        if not isinstance(params.shift, bool):
+            raise SamplingOptionError("shift must be a boolean")
+        # context shift: an eligible request is not capped by the room -- it shifts when it fills the window; the
+        # scheduler is told a max_new inside the window, the device ``limit`` carries the real budget
+        shift_w = window if (self.context_shift and params.shift and window >= 128) else 0
+        budget = min(params.max_tokens, self.runner.max_new_cap) if shift_w else \
+            min(params.max_tokens, room, self.runner.max_new_cap)
+        p = dataclasses.replace(params, max_tokens=max(1, budget))
+        sched_new = min(p.max_tokens, room)
         for name in ("presence_penalty", "frequency_penalty", "min_p"):  # refused here, like a bad pattern below
             if not math.isfinite(float(getattr(p, name))):
                 raise SamplingOptionError(f"{name} must be a finite number")
@@ -350,7 +400,7 @@ class LLMEngine:
                 raise GuidedRequestError("regex cannot be combined with ignore_eos: a constrained request ends by EOS")
             dfa = compile_regex(p.regex)
         req = Request(next(self._ids), list(map(int, prompt_ids)), p, time.perf_counter(),
-                      stream=queue.Queue() if stream else None, dfa=dfa)
+                      stream=queue.Queue() if stream else None, dfa=dfa, shift_w=shift_w)
         if p.logprobs:
             self.stats["logprob_requests"] += 1
         match_limit = -1
@@ -364,12 +414,12 @@ class LLMEngine:
             REGISTRY.inc("lsa_guided_requests_total", 1, "requests with a regex constraint", model=self.name)
         with self._lock:
             if self.prefix_cache and match_limit >= 0:  # the scored rows must be computed, not found in the cache
-                self.sched.add(req.rid, len(req.prompt_ids), p.max_tokens, req.prompt_ids, bool(p.cache_prompt),
+                self.sched.add(req.rid, len(req.prompt_ids), sched_new, req.prompt_ids, bool(p.cache_prompt),
                                match_limit)
             elif self.prefix_cache:
-                self.sched.add(req.rid, len(req.prompt_ids), p.max_tokens, req.prompt_ids, bool(p.cache_prompt))
+                self.sched.add(req.rid, len(req.prompt_ids), sched_new, req.prompt_ids, bool(p.cache_prompt))
             else:
-                self.sched.add(req.rid, len(req.prompt_ids), p.max_tokens)
+                self.sched.add(req.rid, len(req.prompt_ids), sched_new)
             self._reqs[req.rid] = req
             if p.prompt_logprobs:
                 self._plp_live += 1
@@ -451,7 +501,7 @@ class LLMEngine:
                                     temperature=sp.temperature, top_k=sp.top_k, top_p=sp.top_p, seed=seed,
                                     eos_on=not sp.ignore_eos, repeat_penalty=sp.repeat_penalty,
                                     repeat_last_n=sp.repeat_last_n, presence_penalty=sp.presence_penalty,
-                                    frequency_penalty=sp.frequency_penalty, min_p=sp.min_p, prompt_ids=req.ctx_ids,
+                                    frequency_penalty=sp.frequency_penalty, min_p=sp.min_p, prompt_ids=req.kept_ids,
                                     defer_table=self.prefill_chunk is not None))
                 if sp.logprobs:  # the row records (runner.enable_logprobs): lp_k = its top_logprobs K
                     entries[-1].update(lp_k=int(sp.top_logprobs))
@@ -492,6 +542,8 @@ class LLMEngine:
             # steps until the earliest request can hit its length limit; with EOS possible, at most
             # sync_every steps between host checks
             reqs = [self._reqs[rid] for rid in running]
+            if self.context_shift:  # requests that filled their window drop half of their context, in one launch
+                self._shift_contexts(reqs)
             remaining = min(q.params.max_tokens - q.gen_host for q in reqs)
             if remaining <= 0:
                 n_steps = 0  # a request finished with its prefill token (max_tokens 1): retire it first
@@ -499,6 +551,8 @@ class LLMEngine:
                 n_steps = remaining if self.run_ahead is None else min(self.run_ahead, remaining)
             else:
                 n_steps = min(self.sync_every, remaining)
+            if self.context_shift and n_steps:  # no run takes an eligible row past its window: it shifts there first
+                n_steps = min([n_steps] + [q.shift_w - q.base - q.gen_host for q in reqs if q.shift_w])
             spec_T = self._spec_run(reqs, n_steps, remaining) if (n_steps and lp_spec) else 0
             if spec_T:  # verify steps: each commits 1 .. spec_T tokens, so fewer cover the same budget
                 n_steps = min(n_steps, -(-remaining // spec_T))
@@ -511,9 +565,9 @@ class LLMEngine:
             # host-side bound on every row's context during the run (selects the decode graph's split plan)
             spec_S = r.bucket(self.sched.highest_slot + 1) if (spec_T and len(reqs) > 1) else 1
             if spec_T:
-                max_ctx = max(len(q.ctx_ids) + q.gen_host for q in reqs) + n_steps * spec_T + spec_T
+                max_ctx = max(q.base + q.gen_host for q in reqs) + n_steps * spec_T + spec_T
             else:
-                max_ctx = max(len(q.ctx_ids) + min(q.gen_host + n_steps, q.params.max_tokens) for q in reqs) + 1
+                max_ctx = max(q.base + min(q.gen_host + n_steps, q.params.max_tokens) for q in reqs) + 1
         # the decode run needs no scheduler state: new requests may be added meanwhile
         t0 = time.perf_counter()
         ev = None
@@ -603,13 +657,51 @@ class LLMEngine:
                     done.append(req)
             return done
 
+    def _shift_contexts(self, reqs: list) -> None:
+        """Context shift, at a run boundary (the host knows every row's generated count): every unfinished eligible
+        request whose context c = base + gen_host has reached its window W keeps its first
+        keep = min(num_keep, prompt length, W - 128) tokens and drops the d = 64 * ((c - keep) // 128) after them --
+        llama.cpp's half of the rest, in whole 64-token blocks, so the survivors keep their rows and move down d / 64
+        table entries, their keys rotated by -d.  The scheduler plans the block moves (``Scheduler.shift``); all
+        requests shifting now go into one kernel launch, followed on the same stream by the new table rows and
+        positions (``ModelRunner.shift_slots``), so the next decode run reads the shifted state.  What counts
+        generated tokens (gen_len, out_tokens, limit, seeds, DFA state, logprob records) does not change, nor does
+        the penalty ring (indexed by position % 64).  A request that has shifted takes plain steps from then on (the
+        drafter's context is not compacted).  When the arena cannot supply the fresh blocks of a shared tail, the
+        request ends at the window, as it would without the feature."""
+        entries = []
+        for q in reqs:
+            c = q.base + q.gen_host
+            if not q.shift_w or c < q.shift_w or q.gen_host >= q.params.max_tokens:
+                continue
+            keep = max(0, min(int(q.params.num_keep), len(q.prompt_ids), q.shift_w - 128))
+            d = BLOCK * ((c - keep) // (2 * BLOCK))
+            plan = self.sched.shift(q.rid, keep, d)
+            if plan is None:  # end it here: the budget becomes what it has generated, the row is marked finished
+                q.params = dataclasses.replace(q.params, max_tokens=q.gen_host)
+                q.shift_w = 0
+                self.runner.end_slot(q.slot)
+                continue
+            moves, table = plan
+            entries.append((q.slot, moves, table, d))
+            q.shifted += d
+            q.drops.append((keep, d))
+            q.spec_off = True
+            self.stats["context_shifts"] += 1
+            self.stats["context_shift_tokens"] += d
+            REGISTRY.inc("lsa_context_shifts_total", 1, "context shifts at the num_ctx window", model=self.name)
+            REGISTRY.inc("lsa_context_shift_tokens_total", d, "tokens dropped by context shifts", model=self.name)
+        if entries:
+            self.runner.shift_slots(entries)
+        self.sched.shift_done()
+
     def _grow_kv(self, reqs: list, n_steps: int) -> list:
         """Lazy KV reservation: before a decode run of ``n_steps`` every running request must own the blocks of
         every cache position the run writes (the context after the run, less the last generated token, which is
         never written).  Requests grow oldest admission first; when the arena runs dry the youngest running
         request is preempted (possibly the one growing).  Returns the requests that stay in the run; the device
         block tables of the grown ones are updated in one batched transfer."""
-        need = {q.rid: len(q.ctx_ids) + min(q.gen_host - 1 + n_steps, q.params.max_tokens - 1) for q in reqs}
+        need = {q.rid: q.base + min(q.gen_host - 1 + n_steps, q.params.max_tokens - 1) for q in reqs}
         order = self.sched.youngest_first()
         alive = set(need)
         grown = {}
@@ -658,9 +750,9 @@ class LLMEngine:
             return 0  # a constrained request speculates only with the opt-in (the guided verify graph)
         T = r.spec_k() + 1
         steps = min(n_steps, -(-remaining // T))
-        if len(q.ctx_ids) + q.gen_host + steps * T + T > r.max_model_len:
+        if q.base + q.gen_host + steps * T + T > (q.shift_w or r.max_model_len):
             return 0
-        got = self.sched.grow(q.rid, len(q.ctx_ids) + q.gen_host - 1 + steps * T + T - 1)
+        got = self.sched.grow(q.rid, q.base + q.gen_host - 1 + steps * T + T - 1)
         if got < 0:
             return 0
         if got > 0:
@@ -700,11 +792,11 @@ class LLMEngine:
         if SB * T > 32:
             return 0
         steps = min(n_steps, -(-remaining // T))
-        if any(len(q.ctx_ids) + q.gen_host + steps * T + T > r.max_model_len for q in reqs):
+        if any(q.base + q.gen_host + steps * T + T > (q.shift_w or r.max_model_len) for q in reqs):
             return 0
         grown, ok = [], True
         for q in reqs:
-            got = self.sched.grow(q.rid, len(q.ctx_ids) + q.gen_host - 1 + steps * T + T - 1)
+            got = self.sched.grow(q.rid, q.base + q.gen_host - 1 + steps * T + T - 1)
             if got < 0:
                 ok = False
                 break
@@ -849,19 +941,23 @@ class LLMEngine:
         self.runner.release_slot(q.slot)
         self._slot_owner.pop(q.slot, None)
         limit = self._plp_match_limit(q) if q.params.prompt_logprobs else -1
+        # a request that has shifted re-prefills the context as its cache held it (kept_ids; ctx_ids otherwise); an
+        # eligible one tells the scheduler a max_new inside its window, as add_request does
+        ids = q.kept_ids
+        new = min(q.params.max_tokens, q.shift_w - len(ids)) if q.shift_w else q.params.max_tokens
         if self.prefix_cache and limit >= 0:  # prompt indices still to score: their rows must be computed again
-            self.sched.preempt(q.rid, len(q.ctx_ids), q.params.max_tokens, q.ctx_ids, limit)
+            self.sched.preempt(q.rid, len(ids), new, ids, limit)
         elif self.prefix_cache:  # with its tokens, so that the resumed request can hit its own blocks if they survive
-            self.sched.preempt(q.rid, len(q.ctx_ids), q.params.max_tokens, q.ctx_ids)
+            self.sched.preempt(q.rid, len(ids), new, ids)
         else:
-            self.sched.preempt(q.rid, len(q.ctx_ids), q.params.max_tokens)
+            self.sched.preempt(q.rid, len(ids), new)
         q.slot, q.gen_host, q.prefilled = -1, 0, 0
         q.preemptions += 1
         self.stats["preempted"] += 1
         reserve = self.sched.reserve_tokens
         gen = q.params.max_tokens if reserve < 0 else min(q.params.max_tokens, reserve)
         self._admit_hold = True
-        self._admit_hold_blocks = -(-(len(q.ctx_ids) + gen) // BLOCK) + self.sched.num_running
+        self._admit_hold_blocks = -(-(q.base + gen) // BLOCK) + self.sched.num_running
 
     def _trace_done(self, req: Request, n: int) -> None:
         """Engine spans of a finished request (queue -> prefill -> decode), fed to lsa_stage_seconds and,
@@ -891,6 +987,8 @@ class LLMEngine:
                 if req.stream is not None:
                     req.stream.put(("done", None))
                 out.append(req)
+            if self.context_shift:
+                self.sched.shift_done()
             if self.prefix_cache:  # the device state is suspect after a failed step: keep no KV from before it
                 self.sched.copies_done()
                 self.sched.reset_prefix_cache()
@@ -908,7 +1006,7 @@ class LLMEngine:
         final, partial, done = [], [], []
         any_sample = False
         for q in list(self._prefilling):
-            ids = q.ctx_ids
+            ids = q.kept_ids
             rest = len(ids) - q.prefilled
             take = rest if budget is None else min(rest, budget)
             if take <= 0:
@@ -975,7 +1073,7 @@ class LLMEngine:
             total_duration_ns=ns(req.finished_at - req.arrival), load_duration_ns=ns(self.load_time_s),
             prompt_eval_duration_ns=ns(req.first_token - req.admitted),
             eval_duration_ns=ns(req.finished_at - req.first_token), done_reason="stop" if ended_eos else "length",
-            cached_prompt_tokens=req.cached_tokens,
+            cached_prompt_tokens=req.cached_tokens, context_shifts=len(req.drops),
             logprobs=self.logprob_entries(req, req.output_ids) if req.params.logprobs else None,
             prompt_logprobs=self.prompt_logprob_entries(req) if req.params.prompt_logprobs else None)
 

@@ -23,7 +23,7 @@ def build_engine(model: str, device: Optional[str] = None, checkpoint: Optional[
                  guided: bool = False, spec_guided: bool = False, spec_sampled: bool = False,
                  spec_batch: int = 1, spec_batch_sampled: bool = False,
                  spec_batch_guided: bool = False, logprobs: bool = False,
-                 spec_logprobs: bool = False) -> LLMEngine:
+                 spec_logprobs: bool = False, context_shift: bool = False) -> LLMEngine:
     """kv_dtype: paged KV cache dtype, "bf16" | "fp8" (None: LSA_KV_FP8, default bf16).
     max_new_cap: generated-token cap per request (None: the context window).
     kv_reserve_tokens: generated tokens whose KV is reserved at admission (the rest grows lazily; < 0 reserves
@@ -61,7 +61,10 @@ def build_engine(model: str, device: Optional[str] = None, checkpoint: Optional[
     graph, replayed only while a running request asked.
     spec_logprobs: a request that asked for logprobs speculates wherever one that did not ask would (off: it takes plain
     steps, and makes a spec_batch run plain); its records are the log-softmax of the raw verify rows.  Needs logprobs
-    and spec_tokens, and is inert without either."""
+    and spec_tokens, and is inert without either.
+    context_shift: a request that fills its num_ctx window keeps its first num_keep tokens, drops half of the rest and
+    goes on generating, as Ollama does (off by default: it ends at the window); ``SamplingParams.shift`` = False opts
+    a request out.  Inert on the fp8 KV cache and under tensor parallelism."""
     if device is None:
         device = f"cuda:{torch.cuda.current_device()}" if torch.cuda.is_available() else "cpu"
     t0 = time.perf_counter()
@@ -82,7 +85,7 @@ def build_engine(model: str, device: Optional[str] = None, checkpoint: Optional[
     eng = LLMEngine(runner, tok, sync_every=sync_every, max_prefill_tokens=max_prefill_tokens, name=model,
                     prefill_chunk=prefill_chunk or None, kv_reserve_tokens=kv_reserve_tokens, spec_tokens=spec_tokens,
                     prefix_cache=prefix_cache, prefix_cow_min_tokens=prefix_cow_min_tokens, guided=guided,
-                    logprobs=logprobs)
+                    logprobs=logprobs, context_shift=context_shift)
     if torch.device(device).type == "cuda":
         if warm_graphs:
             runner.capture_all()

@@ -1471,6 +1471,31 @@ class ModelRunner:
         if pairs:
             ops.kv_copy_blocks(self.kv, self.kv_scale, pairs)
 
+    def shift_slots(self, entries: Sequence[tuple]) -> None:
+        """Context shift (engine.LLMEngine._shift_contexts): ``entries`` = [(slot, moves, blocks, discard)], the
+        scheduler's plan for each running slot that drops ``discard`` tokens of its cache.  One ``ops.kv_shift``
+        launch moves and re-rotates the rows of every entry; then each slot's decode-visible block-table row is
+        rewritten (zero-filled past its end) and its position lowered by ``discard`` -- one pinned transfer for the
+        rows and the deltas.  All of it runs on the engine's stream between decode runs, so a captured graph reads
+        the shifted state at its next replay.  bf16 cache only (the op refuses the fp8 one)."""
+        if not entries:
+            return
+        mb = self.max_blocks
+        for sl, _, blocks, _ in entries:
+            assert int(sl) not in self._pending_bt, "shifting a slot whose prompt is still being prefilled"
+            assert len(blocks) <= mb, "block table longer than max_model_len"
+        ops.kv_shift(self.kv, self.kv_scale, [m for _, moves, _, _ in entries for m in moves], self.cos, self.sin)
+        rows = torch.zeros(len(entries), mb + 1, dtype=torch.int32)
+        for i, (_, _, blocks, discard) in enumerate(entries):
+            rows[i, : len(blocks)] = torch.tensor(list(blocks), dtype=torch.int32)
+            rows[i, mb] = -int(discard)
+        if self.on_gpu:
+            rows = rows.pin_memory()
+        idx = torch.tensor([int(e[0]) for e in entries], dtype=torch.long).to(self.device, non_blocking=True)
+        dv = rows.to(self.device, non_blocking=True)
+        self.block_tables.index_copy_(0, idx, dv[:, :mb])
+        self.positions.index_add_(0, idx, dv[:, mb])
+
     def set_eos(self, ids: Sequence[int]) -> None:
         """Replace the stop-token set (same length keeps captured graphs valid; otherwise recapture)."""
         ids = list(ids) or [-1]
@@ -1480,6 +1505,11 @@ class ModelRunner:
         else:
             self.eos.copy_(torch.tensor(ids, dtype=torch.int32))
         self.eos_list = ids
+
+    def end_slot(self, slot: int) -> None:
+        """Mark a running row finished where it stands (a context shift the arena could not serve): the decode graphs
+        skip it and the engine's next read of the finished flags retires it with the tokens it has."""
+        self.finished[slot] = 1
 
     def release_slot(self, slot: int) -> None:
         self._pending_bt.pop(slot, None)

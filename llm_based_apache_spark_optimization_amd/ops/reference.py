@@ -567,6 +567,30 @@ def kv_copy_blocks(kv, kv_scale, pairs):
         kv_scale.index_copy_(2, dst, kv_scale.index_select(2, src))
 
 
+# ----------------------------------------------------------------------------------- context shift
+def kv_shift(kv, kv_scale, moves, cos_t, sin_t):
+    """Host twin of kv_shift_kernel (csrc/kernels/kv_shift.hip) and its oracle; kv [L, 2, NB, Hkv, 64, 128] bf16,
+    moves a validated list of (src, dst, row_lo, row_hi, delta), cos_t / sin_t the f32 RoPE tables [rows, 64].  For
+    every layer and KV head, rows row_lo <= r < row_hi: K row r of dst = K row r of src rotated by -delta (the pair
+    is (i, i + 64): lo' = lo*c + hi*s, hi' = hi*c - lo*s with c, s = cos_t / sin_t[delta, i], in f32 with each
+    product and sum rounded on its own, then one rounding to bf16; delta 0 is a copy), V row r of dst = V row r of
+    src when src != dst; the V of an in-place move is not touched."""
+    assert kv_scale is None
+    for src, dst, lo, hi, delta in moves:
+        if hi <= lo:
+            continue
+        k = kv[:, 0, src, :, lo:hi]
+        if delta == 0:
+            if src != dst:
+                kv[:, 0, dst, :, lo:hi] = k
+        else:
+            x, y = k[..., :64].float(), k[..., 64:].float()
+            c, s = cos_t[delta].float(), sin_t[delta].float()
+            kv[:, 0, dst, :, lo:hi] = torch.cat([x * c + y * s, y * c - x * s], dim=-1).to(kv.dtype)
+        if src != dst:
+            kv[:, 1, dst, :, lo:hi] = kv[:, 1, src, :, lo:hi]
+
+
 # ----------------------------------------------------------------------------------- speculative decoding
 def attn_verify(q, kc, vc, block_table, pos0, H, Hkv, scale, out, kv_scales=None):
     """Attention of the T new tokens of each sequence (their K / V already appended): q [T, H, D] with one block-table

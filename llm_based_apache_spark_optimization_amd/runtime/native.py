@@ -95,6 +95,7 @@ class _PyScheduler:
         self._evictable = 0
         self._clock = 0
         self._copies, self._pins = [], []
+        self._shift_blocks, self._shift_nodes = [], []  # released by shift(), held until shift_done()
 
     def add(self, rid, prompt_len, max_new, tokens=(), cacheable=True, match_limit=-1):
         if rid in self._reqs:
@@ -316,6 +317,53 @@ class _PyScheduler:
             return -1
         r["blocks"] += self._take(add)
         return add
+
+    def shift(self, rid, keep, discard):
+        """Scheduler::shift: (moves, new table) of a context shift, or None when the fresh blocks it needs cannot be
+        supplied (nothing changes then).  The blocks it releases are held until ``shift_done``."""
+        r = self._reqs[rid]
+        bs, nb = self._alloc.block_size, len(r["blocks"])
+        if r["slot"] < 0:
+            raise ValueError("shift: request is not running")
+        if keep < 0 or discard <= 0 or discard % bs:
+            raise ValueError("shift: bad keep or discard")
+        k0, rem, m, shared = keep // bs, keep % bs, discard // bs, len(r["nodes"])
+        if k0 + m >= nb:
+            raise ValueError("shift: nothing left behind the discarded tokens")
+        fresh = sum(1 for j in range(k0, nb - m) if j + m < shared)
+        if self._available() < fresh:
+            return None
+        got = self._take(fresh)
+        moves, table, g = [], r["blocks"][:k0], 0
+        for j in range(k0, nb - m):
+            src = dst = r["blocks"][j + m]
+            if j + m < shared:
+                dst, g = got[g], g + 1
+            if j == k0 and rem:
+                moves.append((r["blocks"][k0], dst, 0, rem, 0))
+                moves.append((src, dst, rem, bs, discard))
+            else:
+                moves.append((src, dst, 0, bs, discard))
+            table.append(dst)
+        for j in range(k0, nb):
+            if j < shared:
+                self._shift_nodes.append(r["nodes"][j])
+            elif j < k0 + m:
+                self._shift_blocks.append(r["blocks"][j])
+        del r["nodes"][k0:]
+        r["blocks"] = table
+        r["published"] = True  # the blocks of a shifted cache are never published
+        return moves, list(table)
+
+    def shift_done(self):
+        if self._shift_blocks:
+            self._alloc.release(self._shift_blocks)
+        if self._shift_nodes:
+            self._clock += 1
+            for n in reversed(self._shift_nodes):
+                self._nodes[n]["tick"] = self._clock
+                self._unref(n)
+        self._shift_blocks, self._shift_nodes = [], []
 
     def preempt(self, rid, prompt_len, max_new, tokens=(), match_limit=-1):
         r = self._reqs[rid]
