@@ -62,6 +62,8 @@ int lsa_kv_copy_blocks(void* kv, void* scale, const int* pairs, int npairs, int 
                        long long scale_bytes, hipStream_t s);
 int lsa_kv_shift(void* kv, const int* moves, int n, int layers, int nb, int hkv, const float* cos_t, const float* sin_t,
                  int table_rows, hipStream_t s);
+int lsa_kv_shift8(void* kv, float* kv_scale, const int* moves, int n, int layers, int nb, int hkv, const float* cos_t,
+                  const float* sin_t, int table_rows, hipStream_t s);
 int lsa_spec_draft(const int* prompt_tok, int prompt_ld, const int* prompt_len, const int* out_tokens, int max_new,
                    const int* gen_len, const int* input_ids, const int* positions, int rows, int k, int n_max, int n_min,
                    const int* forced, int nf, int forced_ld, int* spec_ids, int* spec_pos, int* spec_draft,
@@ -930,6 +932,32 @@ void kv_shift(at::Tensor& kv, const at::Tensor& moves, const at::Tensor& cos, co
         "kv_shift");
 }
 
+// context shift on the fp8 cache: kv the e4m3 arena [L, 2, NB, Hkv, 64, 128] (uint8, tiles in token-pair order),
+// kv_scale its f32 row scales [L, 2, NB, Hkv, 64]; rotated K rows are dequantised, rotated and quantised again with a
+// new scale, everything else is copied with its scale (kernels/kv_shift.hip).  The moves are validated on the host
+// before they are uploaded (ops.kv_shift8).
+void kv_shift8(at::Tensor& kv, at::Tensor& kv_scale, const at::Tensor& moves, const at::Tensor& cos,
+               const at::Tensor& sin) {
+  need(kv, at::kByte, "kv");
+  TORCH_CHECK(kv.dim() == 6 && kv.size(1) == 2 && kv.size(2) >= 2 && kv.size(4) == 64 && kv.size(5) == 128 &&
+                  kv.is_contiguous(), "kv must be a contiguous [L, 2, NB, Hkv, 64, 128] arena");
+  need(kv_scale, at::kFloat, "kv_scale");
+  TORCH_CHECK(kv_scale.dim() == 5 && kv_scale.sizes() == kv.sizes().slice(0, 5) && kv_scale.is_contiguous(),
+              "kv_scale must be a contiguous [L, 2, NB, Hkv, 64] tensor");
+  need(moves, at::kInt, "moves");
+  TORCH_CHECK(moves.dim() == 2 && moves.size(1) == 5 && moves.is_contiguous(), "moves must be a contiguous [n, 5] tensor");
+  need(cos, at::kFloat, "cos");
+  need(sin, at::kFloat, "sin");
+  TORCH_CHECK(cos.dim() == 2 && cos.size(1) == 64 && cos.is_contiguous() && sin.is_contiguous() &&
+                  sin.sizes() == cos.sizes() && cos.size(0) >= 1, "cos / sin must be contiguous [rows, 64] tables");
+  const int64_t L = kv.size(0), NB = kv.size(2), Hkv = kv.size(3);
+  TORCH_CHECK(NB <= INT32_MAX && cos.size(0) <= INT32_MAX && moves.size(0) <= 65535 && L <= 65535 && 2 * Hkv <= 65535,
+              "kv_shift8: arena, tables or move list too large");
+  check(lsa_kv_shift8(kv.data_ptr(), kv_scale.data_ptr<float>(), moves.data_ptr<int>(), (int)moves.size(0), (int)L,
+                      (int)NB, (int)Hkv, cos.data_ptr<float>(), sin.data_ptr<float>(), (int)cos.size(0), cur_stream()),
+        "kv_shift8");
+}
+
 void attn_prefill(const at::Tensor& q, const at::Tensor& kc, const at::Tensor& vc, const at::Tensor& block_tables,
                   const at::Tensor& cu_q, const at::Tensor& ctx_lens, const at::Tensor& work, int64_t H, int64_t Hkv,
                   double scale, at::Tensor& out, int64_t rows32, int64_t xf_mt) {
@@ -1720,6 +1748,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("kv8_dequant", &kv8_dequant);
   m.def("kv_copy_blocks", &kv_copy_blocks, py::arg("kv"), py::arg("kv_scale"), py::arg("pairs"));
   m.def("kv_shift", &kv_shift, py::arg("kv"), py::arg("moves"), py::arg("cos"), py::arg("sin"));
+  m.def("kv_shift8", &kv_shift8, py::arg("kv"), py::arg("kv_scale"), py::arg("moves"), py::arg("cos"), py::arg("sin"));
   m.def("silu_mul", &silu_mul);
   m.def("attn_decode", &attn_decode, py::arg("q"), py::arg("kc"), py::arg("vc"), py::arg("block_tables"),
         py::arg("pos"), py::arg("H"), py::arg("Hkv"), py::arg("scale"), py::arg("chunk_blocks"), py::arg("nsplit"),

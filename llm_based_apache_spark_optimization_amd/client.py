@@ -400,6 +400,7 @@ class EngineService(Backend):
                                 "spec_logprobs": bool(getattr(getattr(lp.engine, "runner", None),
                                                               "spec_logprobs", False)),
                                 "context_shift": bool(getattr(lp.engine, "context_shift", False)),
+                                "context_shift_fp8": bool(getattr(lp.engine, "context_shift_fp8", False)),
                                 **lp.engine.stats} for m, lp in self._loops.items()}}
 
 

@@ -97,8 +97,11 @@ class Settings:
     spec_logprobs: bool = dataclasses.field(default_factory=lambda: _env("SPEC_LOGPROBS", False, bool))
     # context shift (off by default): a request that fills its num_ctx window keeps its first num_keep tokens, drops
     # half of the rest and goes on generating, as Ollama does, instead of ending at the window; the option extension
-    # "shift": false opts a request out.  Inert on the fp8 KV cache and with tp > 1
+    # "shift": false opts a request out.  Inert with tp > 1, and on the fp8 KV cache without context_shift_fp8
     context_shift: bool = dataclasses.field(default_factory=lambda: _env("CONTEXT_SHIFT", False, bool))
+    # context shift on the fp8 KV cache too (off by default; needs context_shift): a surviving key is dequantised,
+    # rotated and quantised again once per shift, with a new row scale.  Still inert with tp > 1
+    context_shift_fp8: bool = dataclasses.field(default_factory=lambda: _env("CONTEXT_SHIFT_FP8", False, bool))
     tp: int = dataclasses.field(default_factory=lambda: _env("TP", 1, int))
     dp: int = dataclasses.field(default_factory=lambda: _env("DP", 1, int))
     max_batch: int = dataclasses.field(default_factory=lambda: _env("MAX_BATCH", 32, int))

@@ -250,7 +250,8 @@ class LLMEngine:
     def __init__(self, runner: ModelRunner, tokenizer=None, max_prefill_tokens: int = 16384, sync_every: int = 8,
                  name: Optional[str] = None, prefill_chunk: Optional[int] = None, kv_reserve_tokens: int = BLOCK,
                  spec_tokens: int = 0, prefix_cache: bool = False, prefix_cow_min_tokens: Optional[int] = None,
-                 guided: bool = False, spec_batch: int = 0, logprobs: bool = False, context_shift: bool = False):
+                 guided: bool = False, spec_batch: int = 0, logprobs: bool = False, context_shift: bool = False,
+                 context_shift_fp8: bool = False):
         self.runner = runner
         if spec_tokens:  # speculative decoding for batch-1 greedy requests (the runner clamps it to what it supports)
             runner.spec_tokens = int(spec_tokens)
@@ -323,10 +324,14 @@ class LLMEngine:
             self.stats.update(logprob_requests=0, logprob_steps=0, prompt_logprob_requests=0, prompt_logprob_rows=0)
         self._plp_live = 0  # live requests that asked for prompt-token logprobs: 0 = every prefill call is today's
         # context shift (SamplingParams.shift): a request that fills its window drops half of its context and goes on
-        # (``_shift_contexts``).  The flag is inert -- requests end at the window -- on the fp8 KV cache (the re-rotation
-        # kernel takes bf16 rows) and under tensor parallelism; off (the default) nothing is launched or counted
+        # (``_shift_contexts``).  The flag is inert -- requests end at the window -- under tensor parallelism, and on the
+        # fp8 KV cache unless ``context_shift_fp8`` opts in as well (ops.kv_shift8 then quantises every surviving key
+        # again, once per shift); off (the default) nothing is launched or counted
         tp = getattr(runner, "tp", None)
-        self.context_shift = bool(context_shift) and getattr(runner, "kv_scale", None) is None and \
+        fp8 = getattr(runner, "kv_scale", None) is not None
+        self.context_shift_fp8 = bool(context_shift) and bool(context_shift_fp8) and fp8 and \
+            (tp is None or tp.size == 1)
+        self.context_shift = bool(context_shift) and (not fp8 or self.context_shift_fp8) and \
             (tp is None or tp.size == 1)
         if self.context_shift:
             self.stats.update(context_shifts=0, context_shift_tokens=0)

@@ -1474,17 +1474,21 @@ class ModelRunner:
     def shift_slots(self, entries: Sequence[tuple]) -> None:
         """Context shift (engine.LLMEngine._shift_contexts): ``entries`` = [(slot, moves, blocks, discard)], the
         scheduler's plan for each running slot that drops ``discard`` tokens of its cache.  One ``ops.kv_shift``
-        launch moves and re-rotates the rows of every entry; then each slot's decode-visible block-table row is
+        (on the fp8 cache ``ops.kv_shift8``) launch moves and re-rotates the rows of every entry; then each slot's decode-visible block-table row is
         rewritten (zero-filled past its end) and its position lowered by ``discard`` -- one pinned transfer for the
         rows and the deltas.  All of it runs on the engine's stream between decode runs, so a captured graph reads
-        the shifted state at its next replay.  bf16 cache only (the op refuses the fp8 one)."""
+        the shifted state at its next replay."""
         if not entries:
             return
         mb = self.max_blocks
         for sl, _, blocks, _ in entries:
             assert int(sl) not in self._pending_bt, "shifting a slot whose prompt is still being prefilled"
             assert len(blocks) <= mb, "block table longer than max_model_len"
-        ops.kv_shift(self.kv, self.kv_scale, [m for _, moves, _, _ in entries for m in moves], self.cos, self.sin)
+        moves = [m for _, moves, _, _ in entries for m in moves]
+        if self.kv_fp8:
+            ops.kv_shift8(self.kv, self.kv_scale, moves, self.cos, self.sin)
+        else:
+            ops.kv_shift(self.kv, self.kv_scale, moves, self.cos, self.sin)
         rows = torch.zeros(len(entries), mb + 1, dtype=torch.int32)
         for i, (_, _, blocks, discard) in enumerate(entries):
             rows[i, : len(blocks)] = torch.tensor(list(blocks), dtype=torch.int32)

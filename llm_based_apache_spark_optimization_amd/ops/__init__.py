@@ -1834,32 +1834,21 @@ def kv_copy_blocks(kv: torch.Tensor, kv_scale: Optional[torch.Tensor], pairs) ->
     ext().kv_copy_blocks(kv, kv_scale, host.to(kv.device, non_blocking=True))
 
 
-def kv_shift(kv: torch.Tensor, kv_scale: Optional[torch.Tensor], moves, cos: torch.Tensor, sin: torch.Tensor) -> None:
-    """Context shift: move KV rows between blocks of the arena and rotate the keys back (kernels/kv_shift.hip).
-    ``moves`` = host list of (src, dst, row_lo, row_hi, delta): in every layer and KV head, for rows
-    row_lo <= r < row_hi, K row r of block dst = K row r of block src rotated by -delta with the RoPE tables
-    ``cos`` / ``sin`` [rows, 64] f32 (delta 0: a copy), and V row r of dst = V row r of src when src != dst (the V of
-    an in-place move is not touched).  kv [L, 2, NB, Hkv, 64, 128] bf16; the fp8 cache (``kv_scale`` not None) is
-    refused.  Everything is checked here, before anything is uploaded or launched: 0 < id < NB,
-    0 <= row_lo <= row_hi <= 64, 0 <= delta < rows, no two moves with overlapping destination rows, and no move
-    whose destination rows overlap the source rows of another move (the moves of one launch run in no order)."""
-    moves = [tuple(int(v) for v in m) for m in moves]
-    if kv.dim() != 6 or kv.dtype != torch.bfloat16:
-        raise ValueError("kv_shift: kv must be the bf16 [L, 2, NB, Hkv, 64, 128] arena")
-    if kv_scale is not None:
-        raise ValueError("kv_shift: the fp8 KV cache is not supported")
+def _kv_shift_moves(name: str, kv: torch.Tensor, moves, cos: torch.Tensor, sin: torch.Tensor) -> list:
+    """The checks ``kv_shift`` and ``kv_shift8`` share, on the tables and the move list of a 6-dimensional arena ``kv``
+    (their docstrings state the rule); returns the moves as int tuples."""
     if cos.dim() != 2 or cos.shape[1] != 64 or cos.shape != sin.shape or cos.dtype != torch.float32 or \
             sin.dtype != torch.float32:
-        raise ValueError("kv_shift: cos / sin must be f32 [rows, 64] tables")
+        raise ValueError(f"{name}: cos / sin must be f32 [rows, 64] tables")
     NB, rows = kv.shape[2], cos.shape[0]
     if any(len(m) != 5 for m in moves):
-        raise ValueError("kv_shift: a move is (src, dst, row_lo, row_hi, delta)")
+        raise ValueError(f"{name}: a move is (src, dst, row_lo, row_hi, delta)")
     if any(not (0 < s < NB and 0 < d < NB) for s, d, _, _, _ in moves):
-        raise ValueError(f"kv_shift: block ids must satisfy 0 < id < {NB}: {moves}")
+        raise ValueError(f"{name}: block ids must satisfy 0 < id < {NB}: {moves}")
     if any(not 0 <= lo <= hi <= 64 for _, _, lo, hi, _ in moves):
-        raise ValueError(f"kv_shift: rows must satisfy 0 <= row_lo <= row_hi <= 64: {moves}")
+        raise ValueError(f"{name}: rows must satisfy 0 <= row_lo <= row_hi <= 64: {moves}")
     if any(not 0 <= dl < rows for _, _, _, _, dl in moves):
-        raise ValueError(f"kv_shift: delta must satisfy 0 <= delta < {rows}: {moves}")
+        raise ValueError(f"{name}: delta must satisfy 0 <= delta < {rows}: {moves}")
     dsts: dict = {}
     for i, (_, d, lo, hi, _) in enumerate(moves):
         if hi > lo:
@@ -1867,16 +1856,58 @@ def kv_shift(kv: torch.Tensor, kv_scale: Optional[torch.Tensor], moves, cos: tor
     for rs in dsts.values():
         rs.sort()
         if any(a[1] > b[0] for a, b in zip(rs, rs[1:])):
-            raise ValueError(f"kv_shift: two moves write overlapping rows of one block: {moves}")
+            raise ValueError(f"{name}: two moves write overlapping rows of one block: {moves}")
     for i, (s, _, lo, hi, _) in enumerate(moves):
         if hi > lo and any(j != i and dlo < hi and lo < dhi for dlo, dhi, j in dsts.get(s, ())):
-            raise ValueError(f"kv_shift: a move writes rows that another move reads: {moves}")
+            raise ValueError(f"{name}: a move writes rows that another move reads: {moves}")
+    return moves
+
+
+def kv_shift(kv: torch.Tensor, kv_scale: Optional[torch.Tensor], moves, cos: torch.Tensor, sin: torch.Tensor) -> None:
+    """Context shift: move KV rows between blocks of the arena and rotate the keys back (kernels/kv_shift.hip).
+    ``moves`` = host list of (src, dst, row_lo, row_hi, delta): in every layer and KV head, for rows
+    row_lo <= r < row_hi, K row r of block dst = K row r of block src rotated by -delta with the RoPE tables
+    ``cos`` / ``sin`` [rows, 64] f32 (delta 0: a copy), and V row r of dst = V row r of src when src != dst (the V of
+    an in-place move is not touched).  kv [L, 2, NB, Hkv, 64, 128] bf16; the fp8 cache (``kv_scale`` not None) is
+    refused here -- ``kv_shift8`` takes it.  Everything is checked here, before anything is uploaded or launched:
+    0 < id < NB, 0 <= row_lo <= row_hi <= 64, 0 <= delta < rows, no two moves with overlapping destination rows, and
+    no move whose destination rows overlap the source rows of another move (the moves of one launch run in no order)."""
+    moves = [tuple(int(v) for v in m) for m in moves]
+    if kv.dim() != 6 or kv.dtype != torch.bfloat16:
+        raise ValueError("kv_shift: kv must be the bf16 [L, 2, NB, Hkv, 64, 128] arena")
+    if kv_scale is not None:
+        raise ValueError("kv_shift: the fp8 KV cache is not supported")
+    moves = _kv_shift_moves("kv_shift", kv, moves, cos, sin)
     if not moves:
         return
     if not _gpu(kv):
         return ref.kv_shift(kv, None, moves, cos, sin)
     host = torch.tensor(moves, dtype=torch.int32).pin_memory()  # the moves travel in one pinned transfer
     ext().kv_shift(kv, host.to(kv.device, non_blocking=True), cos, sin)
+
+
+def kv_shift8(kv: torch.Tensor, kv_scale: torch.Tensor, moves, cos: torch.Tensor, sin: torch.Tensor) -> None:
+    """``kv_shift`` on the fp8 cache (kv_shift8_kernel in kernels/kv_shift.hip): kv [L, 2, NB, Hkv, 64, 128] uint8, the
+    e4m3 bytes of every (block, head) tile in token-pair order (``reference.kv8_physical``), and kv_scale
+    [L, 2, NB, Hkv, 64] f32, the row scales in token order.  For rows row_lo <= r < row_hi of a move with delta > 0,
+    K row r of src is dequantised (f32(byte) * scale), rotated by -delta as in ``kv_shift`` and quantised again by the
+    append's rule (``reference.quant_kv_rows``: bytes e4m3(x * 448 / amax), new scale amax / 448 with amax the rotated
+    row's max |x|; an all-zero row stays zeros with scale 0) into row r of dst.  V rows and delta-0 K rows are copied
+    with their scales, bit for bit, when src != dst and not touched when src == dst.  The move list is checked as in
+    ``kv_shift``; everything is refused before anything is uploaded or launched."""
+    moves = [tuple(int(v) for v in m) for m in moves]
+    if kv.dim() != 6 or kv.dtype != torch.uint8:
+        raise ValueError("kv_shift8: kv must be the uint8 (e4m3) [L, 2, NB, Hkv, 64, 128] arena")
+    if not isinstance(kv_scale, torch.Tensor) or kv_scale.dtype != torch.float32 or \
+            tuple(kv_scale.shape) != tuple(kv.shape[:5]):
+        raise ValueError("kv_shift8: kv_scale must be the f32 [L, 2, NB, Hkv, 64] row scales of kv")
+    moves = _kv_shift_moves("kv_shift8", kv, moves, cos, sin)
+    if not moves:
+        return
+    if not _gpu(kv):
+        return ref.kv_shift8(kv, kv_scale, moves, cos, sin)
+    host = torch.tensor(moves, dtype=torch.int32).pin_memory()  # the moves travel in one pinned transfer
+    ext().kv_shift8(kv, kv_scale, host.to(kv.device, non_blocking=True), cos, sin)
 
 
 def spec_draft(prompt_tok, prompt_len, out_tokens, gen_len, input_ids, positions, k, spec_ids, spec_pos, spec_draft_out,

@@ -591,6 +591,33 @@ def kv_shift(kv, kv_scale, moves, cos_t, sin_t):
             kv[:, 1, dst, :, lo:hi] = kv[:, 1, src, :, lo:hi]
 
 
+def kv_shift8(kv, kv_scale, moves, cos_t, sin_t):
+    """Host twin of kv_shift8_kernel (csrc/kernels/kv_shift.hip) and its oracle: ``kv_shift`` on the fp8 cache, kv
+    [L, 2, NB, Hkv, 64, 128] uint8 with every tile in token-pair order, kv_scale [L, 2, NB, Hkv, 64] f32.  A K row
+    with delta > 0 is dequantised, rotated in f32 as in ``kv_shift`` and quantised again (``quant_kv_rows``), which
+    gives it a new scale; V rows and delta-0 K rows are copied with their scales when src != dst, and not touched
+    when src == dst."""
+    for src, dst, lo, hi, delta in moves:
+        if hi <= lo:
+            continue
+        planes = ([0] if delta == 0 else []) + [1]
+        if delta:
+            k = dequant_kv_rows(kv8_logical(kv[:, 0, src])[:, :, lo:hi], kv_scale[:, 0, src, :, lo:hi])
+            x, y = k[..., :64], k[..., 64:]
+            c, s = cos_t[delta].float(), sin_t[delta].float()
+            q, sc = quant_kv_rows(torch.cat([x * c + y * s, y * c - x * s], dim=-1))
+            tile = kv8_logical(kv[:, 0, dst]).clone()
+            tile[:, :, lo:hi] = q
+            kv[:, 0, dst] = kv8_physical(tile)
+            kv_scale[:, 0, dst, :, lo:hi] = sc
+        if src != dst:
+            for pl in planes:
+                tile = kv8_logical(kv[:, pl, dst]).clone()
+                tile[:, :, lo:hi] = kv8_logical(kv[:, pl, src])[:, :, lo:hi]
+                kv[:, pl, dst] = kv8_physical(tile)
+                kv_scale[:, pl, dst, :, lo:hi] = kv_scale[:, pl, src, :, lo:hi]
+
+
 # ----------------------------------------------------------------------------------- speculative decoding
 def attn_verify(q, kc, vc, block_table, pos0, H, Hkv, scale, out, kv_scales=None):
     """Attention of the T new tokens of each sequence (their K / V already appended): q [T, H, D] with one block-table

@@ -11,7 +11,11 @@ launches of a window rotate the same blocks again and again), the prefill with t
 request that ends in the token's read-back; both report the median and the spread of --reps windows.  Writes JSON
 lines to profiles/kv_shift/kv_shift_mi355x.jsonl.  Needs a GPU.
 
-  python scripts/bench_kv_shift.py [--layers N] [--reps 9] [--calls 10] [--skip prefill]
+  --fp8    also time ``kv_shift8`` (the fp8 cache: dequantise, rotate, quantise again) on the same move lists, on an
+           e4m3 arena of the same shape filled with random codes and scales; it moves half the K bytes of the bf16
+           launch plus 8 scale bytes per row ("kv_shift8" records, beside the "kv_shift" ones).
+
+  python scripts/bench_kv_shift.py [--layers N] [--reps 9] [--calls 10] [--skip prefill] [--fp8]
 """
 from __future__ import annotations
 
@@ -53,24 +57,37 @@ def plan(c: int) -> tuple:
     return moves, d
 
 
-def bench_shift(r: ModelRunner, tag: str, c: int, reps: int, calls: int) -> None:
+def fp8_arena(r: ModelRunner) -> tuple:
+    """An e4m3 arena of the runner's shape: random finite codes (0x7f and 0xff are NaN) and scales near 1."""
+    g = torch.Generator(device=r.device).manual_seed(8)
+    kv = torch.randint(0, 0x7f, tuple(r.kv.shape), generator=g, device=r.device, dtype=torch.uint8)
+    kv |= torch.randint(0, 2, tuple(r.kv.shape), generator=g, device=r.device, dtype=torch.uint8) << 7
+    sc = torch.rand(tuple(r.kv.shape[:5]), generator=g, device=r.device) + 0.5
+    return kv, sc
+
+
+def bench_shift(r: ModelRunner, tag: str, c: int, reps: int, calls: int, fp8=None) -> None:
     moves, d = plan(c)
     host = torch.tensor(moves, dtype=torch.int32).pin_memory().to(r.device)
+    if fp8 is None:
+        launch = lambda: ops.ext().kv_shift(r.kv, host, r.cos, r.sin)  # noqa: E731
+    else:
+        launch = lambda: ops.ext().kv_shift8(fp8[0], fp8[1], host, r.cos, r.sin)  # noqa: E731
     for _ in range(3):
-        ops.ext().kv_shift(r.kv, host, r.cos, r.sin)
+        launch()
     ts = []
     for _ in range(reps):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         for _ in range(calls):
-            ops.ext().kv_shift(r.kv, host, r.cos, r.sin)
+            launch()
         e1.record()
         torch.cuda.synchronize()
         ts.append(e0.elapsed_time(e1) * 1e3 / calls)
-    rows = (c - 1 - d - KEEP)  # rotated rows; K read and written
-    nbytes = 2 * rows * r.L * r.Hkv * 128 * 2
+    rows = (c - 1 - d - KEEP)  # rotated rows; K read and written (fp8: one byte per value and a 4-byte scale per row)
+    nbytes = 2 * rows * r.L * r.Hkv * (128 * 2 if fp8 is None else 128 + 4)
     us = statistics.median(ts)
-    emit({"bench": "kv_shift", "model": tag, "layers": r.L, "kv_heads": r.Hkv, "ctx": c, "keep": KEEP, "discard": d,
+    emit({"bench": "kv_shift" if fp8 is None else "kv_shift8", "model": tag, "layers": r.L, "kv_heads": r.Hkv, "ctx": c, "keep": KEEP, "discard": d,
           "moves": len(moves), "k_bytes_read_plus_written": nbytes, "us_median": round(us, 1),
           "us_min": round(min(ts), 1), "us_max": round(max(ts), 1), "gbps": round(nbytes / us / 1e3, 1)})
 
@@ -96,6 +113,7 @@ def main() -> None:
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--calls", type=int, default=10)
     ap.add_argument("--skip", default="")
+    ap.add_argument("--fp8", action="store_true", help="also time kv_shift8 on an fp8 arena of the same shape")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_kv_shift.py needs a GPU: nothing here can be measured without one")
@@ -106,11 +124,14 @@ def main() -> None:
             spec = dataclasses.replace(spec, n_layers=a.layers, name=f"{name}-{a.layers}l")
         r = ModelRunner(init_random(spec, dev, seed=0), max_slots=2, max_model_len=4096, num_kv_blocks=72)
         eng = LLMEngine(r, name=spec.name, context_shift=True)
+        fp8 = fp8_arena(r) if a.fp8 else None
         for c in (2048, 4096):
             bench_shift(r, tag, c, a.reps, a.calls)
+            if fp8 is not None:
+                bench_shift(r, tag, c, a.reps, a.calls, fp8)
             if "prefill" not in a.skip:
                 bench_prefill(eng, tag, c, a.reps)
-        del eng, r
+        del eng, r, fp8
         torch.cuda.empty_cache()
 
 
