@@ -1083,7 +1083,7 @@ def linear_a8_rr(h: torch.Tensor, parts: torch.Tensor, h_out: torch.Tensor, w: P
     splitk = 1 if epi == "silu" else (sk0 if splitk is None else splitk)
     nb, waves, div = nb0 if nb is None else nb, wv0 if waves is None else waves, dv0 if div is None else div
     if not _gpu(h):
-        x = h.view(-1)[:K].float() + parts.float().sum(0).view(-1)
+        x = ref.slab_sum(h.view(-1)[:K].float(), parts.reshape(parts.shape[0], -1)[:, :K])
         h_out.view(-1)[:K].copy_(x)
         q, s = quantize_blocks_fp8(x.view(1, K), 32)
         y = dequant_blocks_fp8(q, s) @ w.dense().float().t()
@@ -1132,10 +1132,13 @@ def add_rmsnorm(h: torch.Tensor, w: torch.Tensor, eps: float, xn: torch.Tensor,
     the f32 values, before the bf16 rounding of xn)."""
     assert x8 is None or xf, "the fp8 output rides on the fragment-major (xf) decode layout"
     if x8 is not None and not _gpu(h):
-        add_rmsnorm(h, w, eps, xn, parts, ids, emb, row_idx, write_h, rows, xf, ss_out, ss_ld, ss_nzero)
         n = rows if rows is not None else xn.shape[0]
-        xr = from_xfrag(xn, n, w.numel()) if xf else xn[:n]
-        quantize_xf8(xr, xfrag_tiles(n), x8, sx8)
+        hc = h.clone()  # the f32 rows, before the bf16 rounding of xn (raw mode: the un-normalised sums)
+        y32 = ref.add_rmsnorm_f32(hc, w, eps, n, parts, ids, emb, row_idx, True)
+        if ss_out is not None:
+            y32 = hc[:n]
+        add_rmsnorm(h, w, eps, xn, parts, ids, emb, row_idx, write_h, rows, xf, ss_out, ss_ld, ss_nzero)
+        quantize_xf8(y32, xfrag_tiles(n), x8, sx8)
         return xn
     if rows is None:
         assert not xf, "xf output needs rows"
@@ -1205,7 +1208,7 @@ def linear_rr(h: torch.Tensor, parts: torch.Tensor, h_out: torch.Tensor, w: Pack
     splitk = 1 if epi == "silu" else (sk0 if splitk is None else splitk)
     nb = nb0 if nb is None else nb
     if not _gpu(h):
-        x = h.view(-1)[:K].float() + parts.float().sum(0).view(-1)
+        x = ref.slab_sum(h.view(-1)[:K].float(), parts.reshape(parts.shape[0], -1)[:, :K])
         h_out.view(-1)[:K].copy_(x)
         xb = x.to(torch.bfloat16).view(1, K)
         if epi == "silu":
@@ -1244,7 +1247,7 @@ def res_add_ss(h: torch.Tensor, parts: Optional[torch.Tensor], xn: torch.Tensor,
     if not _gpu(h):
         hv = h[:rows].float()
         if parts is not None:
-            hv = hv + parts[:, :rows].float().sum(0)
+            hv = ref.slab_sum(hv, parts[:, :rows])
         h[:rows].copy_(hv)
         x16 = hv.to(torch.bfloat16)
         if xf:
@@ -1273,7 +1276,7 @@ def silu_parts(parts: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
     """out [M, F] = silu(gate) * up from f32 split-K slabs [S, M, 2F] of the interleaved gate_up GEMM."""
     if not _gpu(parts):
         S, M, N = parts.shape
-        y = parts.float().sum(0).view(M, N // 32, 2, 16)
+        y = ref.slab_sum(parts[0].float(), parts[1:]).view(M, N // 32, 2, 16)
         g, u = y[:, :, 0, :].reshape(M, N // 2), y[:, :, 1, :].reshape(M, N // 2)
         out.copy_((torch.nn.functional.silu(g) * u).to(out.dtype))
         return out

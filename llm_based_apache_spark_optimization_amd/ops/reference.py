@@ -28,19 +28,31 @@ def linear(x: torch.Tensor, w: torch.Tensor, epi: str = "bf16", splitk: int = 1)
     return y.to(torch.bfloat16)
 
 
-def add_rmsnorm(h, w, eps, xn, parts=None, ids=None, emb=None, row_idx=None, write_h=True):
-    rows = xn.shape[0]
+def slab_sum(v: torch.Tensor, parts) -> torch.Tensor:
+    """v + parts[0] + parts[1] + ... in f32, left to right: the order in which every kernel that consumes split-K slabs
+    adds them (``torch.sum`` promises no order), so the host paths reproduce the residual stream bit for bit."""
+    for s in range(parts.shape[0]):
+        v = v + parts[s].float()
+    return v
+
+
+def add_rmsnorm_f32(h, w, eps, rows, parts=None, ids=None, emb=None, row_idx=None, write_h=True):
+    """The f32 rows of ``add_rmsnorm`` before their rounding to bf16 (what the kernel quantises for its fp8 output)."""
     idx = row_idx.long() if row_idx is not None else torch.arange(rows, device=h.device)
     if ids is not None:
         v = emb[ids.long()[idx]].float()
     else:
         v = h[idx].float()
     if parts is not None:
-        v = v + parts[:, idx].float().sum(0)
+        v = slab_sum(v, parts[:, idx])
     if write_h:
         h[idx] = v
     inv = torch.rsqrt(v.pow(2).mean(-1, keepdim=True) + eps)
-    xn.copy_((v * inv * w.float()).to(torch.bfloat16))
+    return v * inv * w.float()
+
+
+def add_rmsnorm(h, w, eps, xn, parts=None, ids=None, emb=None, row_idx=None, write_h=True):
+    xn.copy_(add_rmsnorm_f32(h, w, eps, xn.shape[0], parts, ids, emb, row_idx, write_h).to(torch.bfloat16))
     return xn
 
 
@@ -105,7 +117,7 @@ def kv8_logical(physical: torch.Tensor) -> torch.Tensor:
 
 def rope_append(qkv, pos, tok_seq, block_tables, cos_t, sin_t, q_out, kc, vc, H, Hkv, kv_scales=None):
     if qkv.dtype == torch.float32 and qkv.dim() == 3:  # f32 split-K slabs [S, T, n]
-        qkv = qkv.sum(0)
+        qkv = slab_sum(qkv[0], qkv[1:])
     T = qkv.shape[0]
     D = 128
     x = qkv.float().view(T, H + 2 * Hkv, D)
