@@ -64,6 +64,11 @@ int lsa_kv_shift(void* kv, const int* moves, int n, int layers, int nb, int hkv,
                  int table_rows, hipStream_t s);
 int lsa_kv_shift8(void* kv, float* kv_scale, const int* moves, int n, int layers, int nb, int hkv, const float* cos_t,
                   const float* sin_t, int table_rows, hipStream_t s);
+int lsa_embed_rowscale(const float* h, const float* parts, int nparts, long part_stride, const int* tseq, const int* cu,
+                       const int* meta, int n, int T, int D, float eps, float* rs, hipStream_t s);
+int lsa_embed_pool(const float* h, const float* parts, int nparts, long part_stride, const int* cu, const int* meta,
+                   int n, int T, int D, const float* rs, const void* gamma, float* acc, int nslots, hipStream_t s);
+int lsa_embed_finish(const int* meta, int n, int D, const float* acc, float* out, int nslots, hipStream_t s);
 int lsa_spec_draft(const int* prompt_tok, int prompt_ld, const int* prompt_len, const int* out_tokens, int max_new,
                    const int* gen_len, const int* input_ids, const int* positions, int rows, int k, int n_max, int n_min,
                    const int* forced, int nf, int forced_ld, int* spec_ids, int* spec_pos, int* spec_draft,
@@ -958,6 +963,80 @@ void kv_shift8(at::Tensor& kv, at::Tensor& kv_scale, const at::Tensor& moves, co
         "kv_shift8");
 }
 
+// Embeddings (kernels/embed.hip): h [T, D] f32 prefill residual rows, parts the optional [np, T, D] f32 split-K slabs
+// the final norm would add, tseq [T] / cu [n + 1] the prefill's row -> sequence map and row offsets, meta [5, n] int32
+// (emode, estart, eslot, efinal, ecount per sequence).  The values of cu / meta are validated on the host before they
+// are uploaded (ops._embed_check); the shapes here.
+struct EmbedDims {
+  int n, T, D, np;
+  long stride;
+};
+
+EmbedDims embed_dims(const at::Tensor& h, const c10::optional<at::Tensor>& parts, const at::Tensor& cu,
+                     const at::Tensor& meta, const char* what) {
+  need(h, at::kFloat, "h");
+  need(cu, at::kInt, "cu");
+  need(meta, at::kInt, "meta");
+  TORCH_CHECK(h.dim() == 2 && h.is_contiguous() && h.size(0) >= 1 && h.size(0) <= INT32_MAX / 2 && h.size(1) >= 4 &&
+                  h.size(1) % 4 == 0 && h.size(1) <= (1 << 20), what, ": h must be a contiguous [T, D] tensor, D % 4 == 0");
+  TORCH_CHECK(meta.dim() == 2 && meta.size(0) == 5 && meta.size(1) >= 1 && meta.size(1) <= 65535 && meta.is_contiguous(),
+              what, ": meta must be a contiguous [5, n] tensor, n <= 65535");
+  TORCH_CHECK(cu.dim() == 1 && cu.is_contiguous() && cu.numel() == meta.size(1) + 1, what, ": cu must be [n + 1]");
+  EmbedDims d{(int)meta.size(1), (int)h.size(0), (int)h.size(1), 0, 0};
+  if (parts.has_value()) {
+    need(*parts, at::kFloat, "parts");
+    TORCH_CHECK(parts->dim() == 3 && parts->size(0) >= 1 && parts->size(0) <= 64 && parts->size(1) == h.size(0) &&
+                    parts->size(2) == h.size(1) && parts->stride(2) == 1 && parts->stride(1) == h.size(1) &&
+                    parts->stride(0) >= h.numel(), what, ": parts must be [np, T, D] slabs of contiguous rows");
+    d.np = (int)parts->size(0);
+    d.stride = (long)parts->stride(0);
+  }
+  return d;
+}
+
+void embed_rowscale(const at::Tensor& h, const c10::optional<at::Tensor>& parts, const at::Tensor& tseq,
+                    const at::Tensor& cu, const at::Tensor& meta, double eps, at::Tensor& rs) {
+  const EmbedDims d = embed_dims(h, parts, cu, meta, "embed_rowscale");
+  need(tseq, at::kInt, "tseq");
+  need(rs, at::kFloat, "rs");
+  TORCH_CHECK(tseq.dim() == 1 && tseq.is_contiguous() && tseq.numel() == d.T, "embed_rowscale: tseq must be [T]");
+  TORCH_CHECK(rs.dim() == 1 && rs.is_contiguous() && rs.numel() >= d.T, "embed_rowscale: rs must hold T rows");
+  check(lsa_embed_rowscale(h.data_ptr<float>(), ptr<const float>(parts), d.np, d.stride, tseq.data_ptr<int>(),
+                           cu.data_ptr<int>(), meta.data_ptr<int>(), d.n, d.T, d.D, (float)eps, rs.data_ptr<float>(),
+                           cur_stream()),
+        "embed_rowscale");
+}
+
+void embed_pool(const at::Tensor& h, const c10::optional<at::Tensor>& parts, const at::Tensor& cu,
+                const at::Tensor& meta, const at::Tensor& rs, const at::Tensor& gamma, at::Tensor& acc) {
+  const EmbedDims d = embed_dims(h, parts, cu, meta, "embed_pool");
+  need(rs, at::kFloat, "rs");
+  need(gamma, at::kBFloat16, "gamma");
+  need(acc, at::kFloat, "acc");
+  TORCH_CHECK(rs.dim() == 1 && rs.is_contiguous() && rs.numel() >= d.T, "embed_pool: rs must hold T rows");
+  TORCH_CHECK(gamma.dim() == 1 && gamma.is_contiguous() && gamma.numel() == d.D, "embed_pool: gamma must be [D]");
+  TORCH_CHECK(acc.dim() == 2 && acc.is_contiguous() && acc.size(1) == d.D && acc.size(0) >= 1 &&
+                  acc.size(0) <= INT32_MAX, "embed_pool: acc must be a contiguous [slots, D] tensor");
+  check(lsa_embed_pool(h.data_ptr<float>(), ptr<const float>(parts), d.np, d.stride, cu.data_ptr<int>(),
+                       meta.data_ptr<int>(), d.n, d.T, d.D, rs.data_ptr<float>(), gamma.data_ptr(),
+                       acc.data_ptr<float>(), (int)acc.size(0), cur_stream()),
+        "embed_pool");
+}
+
+void embed_finish(const at::Tensor& meta, const at::Tensor& acc, at::Tensor& out) {
+  need(meta, at::kInt, "meta");
+  need(acc, at::kFloat, "acc");
+  need(out, at::kFloat, "out");
+  TORCH_CHECK(meta.dim() == 2 && meta.size(0) == 5 && meta.size(1) >= 1 && meta.size(1) <= INT32_MAX / 8 &&
+                  meta.is_contiguous(), "embed_finish: meta must be a contiguous [5, n] tensor");
+  TORCH_CHECK(acc.dim() == 2 && acc.is_contiguous() && out.is_contiguous() && out.sizes() == acc.sizes() &&
+                  acc.size(0) >= 1 && acc.size(0) <= INT32_MAX && acc.size(1) >= 1 && acc.size(1) <= (1 << 20),
+              "embed_finish: acc and out must be contiguous [slots, D] tensors of one shape");
+  check(lsa_embed_finish(meta.data_ptr<int>(), (int)meta.size(1), (int)acc.size(1), acc.data_ptr<float>(),
+                         out.data_ptr<float>(), (int)acc.size(0), cur_stream()),
+        "embed_finish");
+}
+
 void attn_prefill(const at::Tensor& q, const at::Tensor& kc, const at::Tensor& vc, const at::Tensor& block_tables,
                   const at::Tensor& cu_q, const at::Tensor& ctx_lens, const at::Tensor& work, int64_t H, int64_t Hkv,
                   double scale, at::Tensor& out, int64_t rows32, int64_t xf_mt) {
@@ -1749,6 +1828,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("kv_copy_blocks", &kv_copy_blocks, py::arg("kv"), py::arg("kv_scale"), py::arg("pairs"));
   m.def("kv_shift", &kv_shift, py::arg("kv"), py::arg("moves"), py::arg("cos"), py::arg("sin"));
   m.def("kv_shift8", &kv_shift8, py::arg("kv"), py::arg("kv_scale"), py::arg("moves"), py::arg("cos"), py::arg("sin"));
+  m.def("embed_rowscale", &embed_rowscale, py::arg("h"), py::arg("parts"), py::arg("tseq"), py::arg("cu"),
+        py::arg("meta"), py::arg("eps"), py::arg("rs"));
+  m.def("embed_pool", &embed_pool, py::arg("h"), py::arg("parts"), py::arg("cu"), py::arg("meta"), py::arg("rs"),
+        py::arg("gamma"), py::arg("acc"));
+  m.def("embed_finish", &embed_finish, py::arg("meta"), py::arg("acc"), py::arg("out"));
   m.def("silu_mul", &silu_mul);
   m.def("attn_decode", &attn_decode, py::arg("q"), py::arg("kc"), py::arg("vc"), py::arg("block_tables"),
         py::arg("pos"), py::arg("H"), py::arg("Hkv"), py::arg("scale"), py::arg("chunk_blocks"), py::arg("nsplit"),

@@ -111,6 +111,11 @@ class Backend:
         (``EngineService.score`` states the answer's shape)."""
         raise NotImplementedError
 
+    def embed(self, model: str, input, truncate: bool = True, options: Optional[dict] = None) -> dict:
+        """Ollama's ``/api/embed``: one unit vector per input text (``EngineService.embed`` states the semantics and
+        the answer's shape)."""
+        raise NotImplementedError
+
     def models(self) -> list:
         return []
 
@@ -381,6 +386,78 @@ class EngineService(Backend):
         return {"model": model, "prompt_eval_count": len(ids), "scores": scores,
                 "total_duration": int((time.perf_counter() - t0) * 1e9)}
 
+    MAX_EMBED_INPUTS = 64
+
+    @staticmethod
+    def embed_inputs(input, limit: int) -> list:
+        """``input`` (a string or a list of strings) as a list, refused when empty or longer than ``limit``."""
+        texts = [input] if isinstance(input, str) else list(input) if isinstance(input, (list, tuple)) else None
+        if texts is None or any(not isinstance(t, str) for t in texts):
+            raise SamplingOptionError("embed: input must be a string or a list of strings")
+        if not texts:
+            raise SamplingOptionError("embed needs at least one input")
+        if len(texts) > limit:
+            raise SamplingOptionError(f"embed takes at most {limit} inputs a call")
+        return texts
+
+    @staticmethod
+    def embed_pooling(options: Optional[dict]) -> str:
+        """The option extension ``pooling``: "last" (the default) or "mean"."""
+        pooling = (options or {}).get("pooling", "last")
+        if pooling not in ("last", "mean"):
+            raise SamplingOptionError('pooling must be "last" or "mean"')
+        return pooling
+
+    def embed(self, model, input, truncate=True, options=None) -> dict:
+        """One vector per input: the final-norm output of the model (what the lm_head reads, in f32), pooled over the
+        input's tokens -- the last token's row (``"pooling": "last"``, the default) or the mean over all of them, BOS
+        included (``"mean"``) -- and divided by its Euclidean norm.
+
+        Each input is tokenised on its own with BOS and no prompt template.  The window is min(max_model_len, num_ctx),
+        less one position for the request's single discarded token: a longer input keeps its first window - 1 tokens
+        when ``truncate`` (Ollama's default) and is refused otherwise.  Each input is one ordinary engine request of
+        one token and all are submitted together, so they pack into one prefill.  Refused (``SamplingOptionError``):
+        an engine without embeddings or under TP > 1, an unknown pooling, no input or more than 64, an input with no
+        token besides BOS.
+
+        -> {"model", "embeddings": [[float] * d] * n, "total_duration", "load_duration": 0, "prompt_eval_count"}"""
+        t0 = time.perf_counter()
+        texts = self.embed_inputs(input, self.MAX_EMBED_INPUTS)
+        pooling = self.embed_pooling(options)
+        lp = self.loop(model)
+        eng = lp.engine
+        opts = dict(self.defaults)
+        opts.update(options or {})
+        opts.update(num_predict=1, logprobs=False, prompt_logprobs=False, top_logprobs=0)
+        for k in ("regex", "stop"):
+            opts.pop(k, None)
+        params = dataclasses.replace(SamplingParams.from_ollama_options(opts), embed=pooling, max_tokens=1)
+        window = eng.runner.max_model_len if params.num_ctx is None else min(eng.runner.max_model_len,
+                                                                            int(params.num_ctx))
+        seqs = []
+        for t in texts:
+            ids = eng.tok.encode(t, add_bos=True)
+            if len(ids) < 2:
+                raise SamplingOptionError("embed: an input is empty (no tokens besides BOS)")
+            if len(ids) > window - 1:
+                if not truncate:
+                    raise SamplingOptionError(f"embed: an input of {len(ids)} tokens does not fit the context window "
+                                              f"({window}, less the request's one token) and truncate is false")
+                ids = ids[:window - 1]
+            if len(ids) < 2:
+                raise SamplingOptionError(f"embed: the context window ({window}) leaves no room for an input")
+            seqs.append(ids)
+        reqs = lp.submit_many(seqs, params)  # admitted together: one packed prefill
+        vecs = []
+        for req in reqs:
+            if not req.done.wait(self.timeout_s):
+                raise TimeoutError(f"embedding on {model} timed out after {self.timeout_s}s")
+            if req.error:
+                raise RuntimeError(f"engine {model} failed: {req.error}")
+            vecs.append(eng.result(req).embedding)
+        return {"model": model, "embeddings": vecs, "total_duration": int((time.perf_counter() - t0) * 1e9),
+                "load_duration": 0, "prompt_eval_count": sum(len(s) for s in seqs)}
+
     def models(self) -> list:
         return sorted(self._loops)
 
@@ -401,6 +478,7 @@ class EngineService(Backend):
                                                               "spec_logprobs", False)),
                                 "context_shift": bool(getattr(lp.engine, "context_shift", False)),
                                 "context_shift_fp8": bool(getattr(lp.engine, "context_shift_fp8", False)),
+                                "embeddings": bool(getattr(lp.engine, "embeddings_supported", False)),
                                 **lp.engine.stats} for m, lp in self._loops.items()}}
 
 
@@ -435,6 +513,28 @@ class FakeBackend(Backend):
 
     def score(self, model, prompt, completions, system="", options=None, raw=False, top_logprobs=0) -> dict:
         raise SamplingOptionError("the fake backend has no model distribution: completions cannot be scored")
+
+    EMBED_DIM = 64
+
+    def embed(self, model, input, truncate=True, options=None) -> dict:
+        """Deterministic unit vectors of ``EMBED_DIM`` entries, a function of (model, text, pooling) alone."""
+        import hashlib
+
+        texts = EngineService.embed_inputs(input, EngineService.MAX_EMBED_INPUTS)
+        pooling = EngineService.embed_pooling(options)
+        with self._lock:
+            self.calls.append({"model": model, "input": input, "truncate": truncate, "options": options})
+        vecs = []
+        for t in texts:
+            if not t.strip():
+                raise SamplingOptionError("embed: an input is empty (no tokens besides BOS)")
+            raw = b"".join(hashlib.sha256(f"{model}\0{pooling}\0{i}\0{t}".encode()).digest()
+                           for i in range(self.EMBED_DIM // 32))
+            v = [b / 127.5 - 1.0 for b in raw[:self.EMBED_DIM]]
+            nrm = sum(x * x for x in v) ** 0.5 or 1.0
+            vecs.append([x / nrm for x in v])
+        return {"model": model, "embeddings": vecs, "total_duration": 0, "load_duration": 0,
+                "prompt_eval_count": sum(1 + len(t.split()) for t in texts)}
 
     def models(self):
         return ["duckdb-nsql", "llama3.2", "mistral"]
@@ -471,6 +571,23 @@ class RemoteBackend(Backend):
         except urllib.error.HTTPError as e:
             if e.code == 400:  # what the engine refused, as the in-process backend raises it
                 raise SamplingOptionError(e.read().decode(errors="replace")) from None
+            raise
+
+
+    def embed(self, model, input, truncate=True, options=None) -> dict:
+        import urllib.error
+        import urllib.request
+
+        body = json.dumps({"model": model, "input": input, "truncate": bool(truncate), "options": options or {}}).encode()
+        req = urllib.request.Request(self.url + "/api/embed", data=body, headers={"Content-Type": "application/json"})
+        try:
+            with urllib.request.urlopen(req, timeout=self.timeout_s) as f:
+                return json.loads(f.read())
+        except urllib.error.HTTPError as e:
+            if e.code == 400:  # what the engine refused, as the in-process backend raises it
+                raise SamplingOptionError(e.read().decode(errors="replace")) from None
+            if e.code == 501:
+                raise NotImplementedError(e.read().decode(errors="replace")) from None
             raise
 
 
@@ -513,3 +630,9 @@ def score(model: str, prompt: str = "", completions=(), system: str = "", option
     """The log-likelihood the model gives each of ``completions`` (a string or a list) after the prompt:
     ``EngineService.score`` through the configured backend."""
     return get_backend().score(model, prompt, completions, system, options, raw, top_logprobs)
+
+
+def embed(model: str, input="", truncate: bool = True, options: Optional[dict] = None, **_ignored) -> dict:
+    """Drop-in for ``ollama.embed(model=, input=)``: one unit vector per input text (a string or a list), through the
+    configured backend (``EngineService.embed``)."""
+    return get_backend().embed(model, input, truncate, options)

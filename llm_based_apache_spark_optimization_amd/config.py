@@ -102,6 +102,9 @@ class Settings:
     # context shift on the fp8 KV cache too (off by default; needs context_shift): a surviving key is dequantised,
     # rotated and quantised again once per shift, with a new row scale.  Still inert with tp > 1
     context_shift_fp8: bool = dataclasses.field(default_factory=lambda: _env("CONTEXT_SHIFT_FP8", False, bool))
+    # embeddings (off by default): POST /api/embed returns one unit vector per input, pooled on the device from the
+    # final-norm rows of the prefill ("pooling": "last", the default, or "mean").  Refused with tp > 1
+    embeddings: bool = dataclasses.field(default_factory=lambda: _env("EMBEDDINGS", False, bool))
     tp: int = dataclasses.field(default_factory=lambda: _env("TP", 1, int))
     dp: int = dataclasses.field(default_factory=lambda: _env("DP", 1, int))
     max_batch: int = dataclasses.field(default_factory=lambda: _env("MAX_BATCH", 32, int))

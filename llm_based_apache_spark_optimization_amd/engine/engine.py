@@ -120,6 +120,11 @@ class SamplingParams:
     # keeps its first num_keep tokens, drops half of the rest and goes on, as Ollama does; the Ollama option extension
     # "shift": false opts a request out -- it then ends at the window
     shift: bool = True
+    # embeddings, where the engine runs them (LLMEngine(embeddings=True)): "mean" or "last" makes the request an
+    # embedding request -- its prefill pools the final-norm rows of the prompt on the device and the result carries the
+    # unit vector (GenerationResult.embedding); it generates one token, which is discarded.  Set by the embed route
+    # (serving/executor.py); not an Ollama option: ``from_ollama_options`` never sets it
+    embed: Optional[str] = None
 
     @property
     def needs_sampler(self) -> bool:
@@ -203,6 +208,8 @@ class Request:
     shift_w: int = 0
     shifted: int = 0
     drops: list = dataclasses.field(default_factory=list)
+    # embeddings (params.embed): the unit vector [d] f32, read at the host sync that retires the request
+    embedding: Optional[torch.Tensor] = None
 
     @property
     def ctx_ids(self) -> list:
@@ -244,6 +251,8 @@ class GenerationResult:
     # params.prompt_logprobs: one entry per prompt token (len == prompt_tokens): None below max(1, prompt_logprobs_from),
     # else the same shape as a ``logprobs`` entry; None when the request did not ask
     prompt_logprobs: Optional[list] = None
+    # params.embed: the pooled, normalised final-norm vector [d] as a list of floats; None when the request did not ask
+    embedding: Optional[list] = None
 
 
 class LLMEngine:
@@ -251,7 +260,7 @@ class LLMEngine:
                  name: Optional[str] = None, prefill_chunk: Optional[int] = None, kv_reserve_tokens: int = BLOCK,
                  spec_tokens: int = 0, prefix_cache: bool = False, prefix_cow_min_tokens: Optional[int] = None,
                  guided: bool = False, spec_batch: int = 0, logprobs: bool = False, context_shift: bool = False,
-                 context_shift_fp8: bool = False):
+                 context_shift_fp8: bool = False, embeddings: bool = False):
         self.runner = runner
         if spec_tokens:  # speculative decoding for batch-1 greedy requests (the runner clamps it to what it supports)
             runner.spec_tokens = int(spec_tokens)
@@ -323,6 +332,14 @@ class LLMEngine:
                 runner.enable_logprobs()
             self.stats.update(logprob_requests=0, logprob_steps=0, prompt_logprob_requests=0, prompt_logprob_rows=0)
         self._plp_live = 0  # live requests that asked for prompt-token logprobs: 0 = every prefill call is today's
+        # embeddings (SamplingParams.embed): the runner allocates its per-slot accumulators; off (the default) nothing
+        # is allocated, launched or counted.  Under tensor parallelism the flag is kept and every request refused
+        self.embeddings = bool(embeddings) or bool(getattr(runner, "embeddings", False))
+        if self.embeddings:
+            if self.embeddings_supported and not getattr(runner, "embeddings", False):
+                runner.enable_embeddings()
+            self.stats.update(embed_requests=0, embed_tokens=0)
+        self._emb_live = 0  # live embedding requests: 0 = every prefill call is today's
         # context shift (SamplingParams.shift): a request that fills its window drops half of its context and goes on
         # (``_shift_contexts``).  The flag is inert -- requests end at the window -- under tensor parallelism, and on the
         # fp8 KV cache unless ``context_shift_fp8`` opts in as well (ops.kv_shift8 then quantises every surviving key
@@ -396,6 +413,22 @@ class LLMEngine:
         if p.prompt_logprobs and not self.prompt_logprobs_supported:
             raise SamplingOptionError("prompt_logprobs is not served under tensor parallelism (the sequence-parallel "
                                       "prefill keeps a share of the rows per rank)")
+        if p.embed is not None:
+            if p.embed not in ("mean", "last"):
+                raise SamplingOptionError('pooling must be "mean" or "last"')
+            if not self.embeddings:
+                raise SamplingOptionError("this engine was built without embeddings (embeddings=True / "
+                                          "LSA_EMBEDDINGS=1 enables it)")
+            if not self.embeddings_supported:
+                raise SamplingOptionError("embeddings are not served under tensor parallelism (the sequence-parallel "
+                                          "prefill keeps a share of the rows per rank)")
+            if len(prompt_ids) < 2:
+                raise SamplingOptionError("an embedding input needs at least one token besides BOS")
+            # an ordinary request of one greedy token, which is discarded: no stop, logprobs, regex, stream or shift
+            p = dataclasses.replace(p, max_tokens=1, temperature=0.0, repeat_penalty=1.0, presence_penalty=0.0,
+                                    frequency_penalty=0.0, stop=(), regex=None, logprobs=False, top_logprobs=0,
+                                    prompt_logprobs=False, shift=False, speculate=False)
+            stream, shift_w, sched_new = False, 0, 1
         dfa = None
         if p.regex is not None:  # compiled here, so that a bad pattern fails the request, not the engine loop
             if not self.guided:
@@ -414,6 +447,13 @@ class LLMEngine:
             req.prompt_lp = [None] * len(req.prompt_ids)
             req.plp_next = max(1, p.prompt_logprobs_from)
             match_limit = self._plp_match_limit(req)
+        if p.embed is not None:
+            self.stats["embed_requests"] += 1
+            self.stats["embed_tokens"] += len(req.prompt_ids)
+            REGISTRY.inc("lsa_embed_requests_total", 1, "embedding inputs", model=self.name)
+            REGISTRY.inc("lsa_embed_tokens_total", len(req.prompt_ids), "tokens of embedding inputs", model=self.name)
+            if p.embed == "mean":  # every row must be computed, not found in the cache
+                match_limit = 0
         if dfa is not None:
             self.stats["guided_requests"] += 1
             REGISTRY.inc("lsa_guided_requests_total", 1, "requests with a regex constraint", model=self.name)
@@ -428,6 +468,8 @@ class LLMEngine:
             self._reqs[req.rid] = req
             if p.prompt_logprobs:
                 self._plp_live += 1
+            if p.embed is not None:
+                self._emb_live += 1
         return req
 
     def add_requests(self, prompts: Sequence[Sequence[int]], params: SamplingParams) -> list:
@@ -445,6 +487,8 @@ class LLMEngine:
                     self._reqs.pop(q.rid, None)
                     if q.params.prompt_logprobs:
                         self._plp_live -= 1
+                    if q.params.embed is not None:
+                        self._emb_live -= 1
                 raise
             return reqs
 
@@ -453,6 +497,12 @@ class LLMEngine:
         """Prompt-token logprobs are served: the engine runs per-token logprobs and is not tensor-parallel."""
         tp = getattr(self.runner, "tp", None)
         return bool(self.logprobs) and (tp is None or tp.size == 1)
+
+    @property
+    def embeddings_supported(self) -> bool:
+        """Embeddings are served: the engine was built with them and is not tensor-parallel."""
+        tp = getattr(self.runner, "tp", None)
+        return bool(self.embeddings) and (tp is None or tp.size == 1)
 
     def _plp_match_limit(self, q: Request) -> int:
         """Leading tokens of ``q``'s (resumed) prompt that may come from the prefix cache: the row of position
@@ -634,6 +684,12 @@ class LLMEngine:
                         for i, rid in enumerate(running) if int(fin[i])]
             fin_toks = dict(zip([s for s, _ in fin_rows], r.tokens_of_many([s for s, _ in fin_rows],
                                                                            [n for _, n in fin_rows])))
+            if self._emb_live:  # the vectors of the finished embedding requests, before their slots are released
+                emb = [self._reqs[rid] for i, rid in enumerate(running)
+                       if int(fin[i]) and self._reqs[rid].params.embed is not None]
+                if emb:
+                    for q, vec in zip(emb, r.embeddings_of([q.slot for q in emb])):
+                        q.embedding = vec
             for i, rid in enumerate(running):
                 self._reqs[rid].gen_host = int(gl[i])
                 q = self._reqs[rid]
@@ -646,6 +702,8 @@ class LLMEngine:
                     req = self._reqs.pop(rid)
                     if req.params.prompt_logprobs:
                         self._plp_live -= 1
+                    if req.params.embed is not None:
+                        self._emb_live -= 1
                     req.output_ids = req.resumed + fin_toks[req.slot]
                     n = len(req.output_ids)
                     self._admit_hold = False
@@ -845,19 +903,31 @@ class LLMEngine:
             return None
         return q, (lo - a, int(q.params.top_logprobs), q.ctx_ids[lo + 1:hi + 1])
 
+    def _embed_seg(self, slot: int, end: int):
+        """The ``embed`` entry of a prefill segment that ends at position ``end`` of the request in ``slot``: None, or
+        (pooling, the input's tokens, whether the segment holds its last row)."""
+        q = self._reqs.get(self._slot_owner.get(slot, -1))
+        if q is None or q.params.embed is None:
+            return None
+        total = len(q.kept_ids)
+        return q.params.embed, total, end == total
+
     def _run_prefill(self, batch: list, commit: bool, any_sample: bool = False) -> None:
         """One runner prefill call.  While no live request asked for prompt logprobs it is today's call; else the
         segments' rows to score ride along and the call's device records are kept with their requests, unread."""
         r = self.runner
         segs = [self._score_seg(slot, p0, p0 + len(ids)) for slot, ids, p0 in batch] if self._plp_live else []
+        embs = [self._embed_seg(slot, p0 + len(ids)) for slot, ids, p0 in batch] if self._emb_live else []
+        ekw = dict(embed=embs) if any(embs) else {}  # nobody embeds: the call, arguments included, is today's
         if not any(segs):
             if commit:
-                r.prefill(batch, any_sample)
+                r.prefill(batch, any_sample, **ekw)
             else:
-                r.prefill_chunk(batch)
+                r.prefill_chunk(batch, **ekw)
             return
         score = [sg[1] if sg else None for sg in segs]
-        recs = r.prefill(batch, any_sample, score=score) if commit else r.prefill_chunk(batch, score=score)
+        recs = r.prefill(batch, any_sample, score=score, **ekw) if commit else \
+            r.prefill_chunk(batch, score=score, **ekw)
         for i, row0, rows in recs[3]:
             q = segs[i][0]
             q.plp_pending.append((recs[:3], row0, rows, q.plp_next))
@@ -946,6 +1016,8 @@ class LLMEngine:
         self.runner.release_slot(q.slot)
         self._slot_owner.pop(q.slot, None)
         limit = self._plp_match_limit(q) if q.params.prompt_logprobs else -1
+        if q.params.embed == "mean":  # the re-admitted request pools again from position 0: every row is computed
+            limit = 0
         # a request that has shifted re-prefills the context as its cache held it (kept_ids; ctx_ids otherwise); an
         # eligible one tells the scheduler a max_new inside its window, as add_request does
         ids = q.kept_ids
@@ -999,6 +1071,7 @@ class LLMEngine:
                 self.sched.reset_prefix_cache()
             self._reqs.clear()
             self._plp_live = 0
+            self._emb_live = 0
             self._slot_owner.clear()
             self._prefilling.clear()
             self.stats["aborted"] += len(out)
@@ -1080,7 +1153,8 @@ class LLMEngine:
             eval_duration_ns=ns(req.finished_at - req.first_token), done_reason="stop" if ended_eos else "length",
             cached_prompt_tokens=req.cached_tokens, context_shifts=len(req.drops),
             logprobs=self.logprob_entries(req, req.output_ids) if req.params.logprobs else None,
-            prompt_logprobs=self.prompt_logprob_entries(req) if req.params.prompt_logprobs else None)
+            prompt_logprobs=self.prompt_logprob_entries(req) if req.params.prompt_logprobs else None,
+            embedding=req.embedding.tolist() if req.embedding is not None else None)
 
     def text_of(self, token_ids: Sequence[int], req: Request) -> str:
         """The response text of ``token_ids`` exactly as ``result`` builds it (stop strings applied)."""

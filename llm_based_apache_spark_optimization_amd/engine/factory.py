@@ -24,7 +24,7 @@ def build_engine(model: str, device: Optional[str] = None, checkpoint: Optional[
                  spec_batch: int = 1, spec_batch_sampled: bool = False,
                  spec_batch_guided: bool = False, logprobs: bool = False,
                  spec_logprobs: bool = False, context_shift: bool = False,
-                 context_shift_fp8: bool = False) -> LLMEngine:
+                 context_shift_fp8: bool = False, embeddings: bool = False) -> LLMEngine:
     """kv_dtype: paged KV cache dtype, "bf16" | "fp8" (None: LSA_KV_FP8, default bf16).
     max_new_cap: generated-token cap per request (None: the context window).
     kv_reserve_tokens: generated tokens whose KV is reserved at admission (the rest grows lazily; < 0 reserves
@@ -68,7 +68,10 @@ def build_engine(model: str, device: Optional[str] = None, checkpoint: Optional[
     a request out.  Inert on the fp8 KV cache and under tensor parallelism.
     context_shift_fp8: with ``context_shift``, shift on the fp8 KV cache too: a surviving key is dequantised, rotated
     and quantised again with a new row scale, once per shift (``ops.kv_shift8``).  Inert without ``context_shift``, on
-    the bf16 cache (which shifts anyway) and under tensor parallelism."""
+    the bf16 cache (which shifts anyway) and under tensor parallelism.
+    embeddings: serve embedding requests (``SamplingParams.embed``, ``EngineService.embed``, POST /api/embed): the
+    prefill pools the final-norm rows of such a request on the device (off by default: such a request is then
+    rejected); allocates two [max_slots, hidden] f32 buffers.  Requests are refused under tensor parallelism."""
     if device is None:
         device = f"cuda:{torch.cuda.current_device()}" if torch.cuda.is_available() else "cpu"
     t0 = time.perf_counter()
@@ -89,7 +92,8 @@ def build_engine(model: str, device: Optional[str] = None, checkpoint: Optional[
     eng = LLMEngine(runner, tok, sync_every=sync_every, max_prefill_tokens=max_prefill_tokens, name=model,
                     prefill_chunk=prefill_chunk or None, kv_reserve_tokens=kv_reserve_tokens, spec_tokens=spec_tokens,
                     prefix_cache=prefix_cache, prefix_cow_min_tokens=prefix_cow_min_tokens, guided=guided,
-                    logprobs=logprobs, context_shift=context_shift, context_shift_fp8=context_shift_fp8)
+                    logprobs=logprobs, context_shift=context_shift, context_shift_fp8=context_shift_fp8,
+                    embeddings=embeddings)
     if torch.device(device).type == "cuda":
         if warm_graphs:
             runner.capture_all()

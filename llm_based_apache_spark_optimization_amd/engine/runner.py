@@ -301,6 +301,8 @@ class ModelRunner:
         self._g_host_on: set = set()  # slots whose current request carries a constraint (host mirror of g_on)
         # per-token logprobs (``enable_logprobs``): off = no buffer, launch or graph differs
         self.logprobs = False
+        # embeddings (``enable_embeddings``): off = no buffer, launch or transfer word differs
+        self.embeddings = False
         # prompt-token logprobs: the scored prefill rows go through the lm_head in tiles of at most this many rows (the
         # transient logits are tile x V x 4 bytes; <= 64 rows take the skinny GEMMs, more the stream-K kernel)
         self.score_tile_rows = 256
@@ -1271,6 +1273,35 @@ class ModelRunner:
     def _logprob_scan(self, logits, lp_k, finished, gen_len, lp_n0) -> None:
         ops.logprob_scan(logits, lp_k, finished, gen_len, self.lp_raw, lp_n0, workspace=self.lp_ws)
 
+    # ------------------------------------------------------------------------------------ embeddings
+    def enable_embeddings(self) -> None:
+        """Allocate the device side of embeddings (kernels/embed.hip), per slot: the pooled sum emb_acc [S, d] f32 that
+        the prefills of a chunked prompt accumulate into (never cleared: a segment that starts at position 0 starts its
+        sum from +0) and the normalised vector emb_out [S, d] f32; plus the per-call row scales, grown on demand."""
+        if self.embeddings:
+            return
+        assert self.tp is None or self.tp.size == 1, "embeddings are not served under tensor parallelism"
+        f32 = dict(dtype=torch.float32, device=self.device)
+        self.emb_acc = torch.zeros(self.max_slots, self.d, **f32)
+        self.emb_out = torch.zeros(self.max_slots, self.d, **f32)
+        self.emb_rs = torch.zeros(256, **f32)
+        self.embeddings = True
+
+    def _embed_rows(self, h, d_parts, tsd, cud, meta_d, host) -> None:
+        """The three embedding launches of one prefill call, on the prefill's stream: row scales of the pooled rows, the
+        pool into emb_acc, and the final vectors of the inputs that end in this call into emb_out."""
+        T = h.shape[0]
+        if self.emb_rs.numel() < T:
+            self.emb_rs = torch.zeros(max(T, 2 * self.emb_rs.numel()), dtype=torch.float32, device=self.device)
+        ops.embed_rowscale(h, d_parts, tsd, cud, meta_d, self.eps, self.emb_rs, host=host)
+        ops.embed_pool(h, d_parts, cud, meta_d, self.emb_rs, self.w.final_norm, self.emb_acc, host=host)
+        ops.embed_finish(meta_d, self.emb_acc, self.emb_out, host=host)
+
+    def embeddings_of(self, slots: Sequence[int]) -> torch.Tensor:
+        """The vectors emb_out[slots] as a host [n, d] f32 tensor: one device -> host copy."""
+        idx = torch.tensor(list(slots), dtype=torch.long, device=self.device)
+        return self.emb_out.index_select(0, idx).cpu()
+
     # prompt-token logprobs: teacher-forced scoring of prefill rows (kernels/logprobs.hip, the prompt pair)
     def _prompt_lp_ws(self, rows: int) -> tuple:
         """The chunk workspace of one lm_head tile of scored rows (``ops.prompt_logprob_workspace``): allocated by the
@@ -1527,7 +1558,7 @@ class ModelRunner:
 
     # ------------------------------------------------------------------------------------ prefill
     def prefill(self, seqs: list[tuple[int, Sequence[int], int]], sample_any: bool = False,
-                score: Optional[Sequence] = None):
+                score: Optional[Sequence] = None, embed: Optional[Sequence] = None):
         """Prefill ``seqs`` = [(slot, token_ids, start_pos)] and commit each first token into its slot.
 
         ``start_pos`` > 0 continues a chunked prefill (the cache already holds positions < start_pos);
@@ -1539,13 +1570,20 @@ class ModelRunner:
         ``targets[k]`` (the token that follows it in the prompt: the next token of this call, or for its last row the
         first token of the next chunk, which the caller knows).  Returns None, or the call's device records
         (tok, ids, top, [(sequence index, first record row, rows)]) for ``prompt_logprobs_of``; no host sync.
+
+        ``embed`` (embeddings, ``enable_embeddings``): per sequence None or (pooling "mean" | "last", the input's total
+        tokens, whether this call holds the input's last row).  The sequence's final-norm rows of this call are pooled
+        into its slot's accumulator (a segment with start_pos 0 restarts it), and the call with the last row leaves
+        the normalised vector in ``emb_out[slot]`` for ``embeddings_of``; no host sync.
         """
-        return self._prefill(seqs, commit=True, sample_any=sample_any, score=score)
+        return self._prefill(seqs, commit=True, sample_any=sample_any, score=score, embed=embed)
 
-    def prefill_chunk(self, seqs: list[tuple[int, Sequence[int], int]], score: Optional[Sequence] = None):
-        return self._prefill(seqs, commit=False, score=score)
+    def prefill_chunk(self, seqs: list[tuple[int, Sequence[int], int]], score: Optional[Sequence] = None,
+                      embed: Optional[Sequence] = None):
+        return self._prefill(seqs, commit=False, score=score, embed=embed)
 
-    def _prefill(self, seqs, commit: bool, sample_any: bool = False, score: Optional[Sequence] = None):
+    def _prefill(self, seqs, commit: bool, sample_any: bool = False, score: Optional[Sequence] = None,
+                 embed: Optional[Sequence] = None):
         dev, w, d = self.device, self.w, self.d
         n = len(seqs)
         lens = [len(t) for _, t, _ in seqs]
@@ -1574,8 +1612,20 @@ class ModelRunner:
             stgt.extend(int(x) for x in tg)
             sk.extend([K] * len(tg))
         R = len(srow)
-        host = torch.tensor(toks + pos + tseq + cu + ctx + [c - 1 for c in cu[1:]] + srow + stgt + sk,
-                            dtype=torch.int32)
+        # embedding sequences: meta [5, n] (emode, estart, eslot, efinal, ecount) behind the scored rows' words, only
+        # when some sequence of this call embeds
+        emeta = None
+        if embed is not None and any(e is not None for e in embed):
+            assert self.embeddings, "a sequence asks for an embedding but the runner was built without embeddings"
+            assert self.tp is None or self.tp.size == 1, "embeddings are not served under tensor parallelism"
+            assert len(embed) == n, (len(embed), n)
+            emeta = [[0] * n for _ in range(5)]
+            for i, e in enumerate(embed):
+                if e is not None:
+                    emeta[0][i], emeta[1][i], emeta[2][i] = ops.EMBED_MODES[e[0]], int(seqs[i][2]), int(slots[i])
+                    emeta[3][i], emeta[4][i] = int(bool(e[2])), int(e[1])
+        host = torch.tensor(toks + pos + tseq + cu + ctx + [c - 1 for c in cu[1:]] + srow + stgt + sk +
+                            (sum(emeta, []) if emeta is not None else []), dtype=torch.int32)
         if self.on_gpu:
             host = host.pin_memory()
         dv = host.to(dev, non_blocking=True)
@@ -1589,6 +1639,7 @@ class ModelRunner:
         if R:  # the final norm gathers the scored rows behind (commit) or instead of (chunk) the last rows, in one launch
             last = dv[o:o + n + R] if commit else dv[o + n:o + n + R]
             tgt_d, k_d = dv[o + n + R:o + n + 2 * R], dv[o + n + 2 * R:o + n + 3 * R]
+        meta_d = dv[o + n + 3 * R:o + n + 3 * R + 5 * n].view(5, n) if emeta is not None else None
         slot_t = torch.tensor(slots, dtype=torch.long, device=dev)
         bt = self.block_tables.index_select(0, slot_t)
         for i, sl in enumerate(slots):  # deferred tables: prefill writes through them; the commit publishes
@@ -1607,10 +1658,16 @@ class ModelRunner:
 
         tps = self.tp.size if self.tp is not None else 1
         if self.seq_parallel and tps > 1 and T >= self.sp_min_tokens:
+            assert emeta is None, "embeddings are not served under tensor parallelism"
             xl = self._prefill_layers_sp(T, ids, posd, tsd, bt, cud, ctxd, last, work, n, commit)
         else:
-            xl = self._prefill_layers(T, ids, posd, tsd, bt, cud, ctxd, last, work, last.numel() if R else n,
-                                      commit or R > 0)
+            # host path: a call that pools embeddings computes every row on its own (ops/reference.py row_stable), so
+            # that a vector is the same bits however the call was packed or the prompt chunked
+            with ref.row_stable(emeta is not None and not self.on_gpu):
+                xl, h, d_parts = self._prefill_layers(T, ids, posd, tsd, bt, cud, ctxd, last, work,
+                                                      last.numel() if R else n, commit or R > 0)
+            if emeta is not None:
+                self._embed_rows(h, d_parts, tsd, cud, meta_d, (cu, emeta))
         recs = None
         if R:
             recs = (*self._score_rows(xl[-R:], tgt_d, k_d, max(sk) > 0), smeta)
@@ -1667,9 +1724,11 @@ class ModelRunner:
         return recs
 
     def _prefill_layers(self, T, ids, posd, tsd, bt, cud, ctxd, last, work, n, commit):
-        """Prefill layer stack with full-sequence residuals; returns the normalised states of the n rows ``last``
-        names (each sequence's last row, and / or the rows a prompt-logprob request scores), None when not ``commit``
-        (a chunk that neither commits a token nor scores a row)."""
+        """Prefill layer stack with full-sequence residuals; returns (xl, h, d_parts): xl the normalised states of the n
+        rows ``last`` names (each sequence's last row, and / or the rows a prompt-logprob request scores), None when not
+        ``commit`` (a chunk that neither commits a token nor scores a row); h [T, d] the f32 residual stream and d_parts
+        the last down projection's split-K slabs still to be added to it (None: already in h), which the embedding
+        pool reads (``_embed_rows``)."""
         dev, w, d = self.device, self.w, self.d
         f32 = dict(dtype=torch.float32, device=dev)
         bf = dict(dtype=torch.bfloat16, device=dev)
@@ -1728,10 +1787,10 @@ class ModelRunner:
                     d_parts = d_parts.view(1, T, d)
                 d_parts = self._reduce_parts(d_parts)
         if not commit:
-            return None
+            return None, h, d_parts
         xl = torch.empty(n, d, **bf)
         ops.add_rmsnorm(h, w.final_norm, self.eps, xl, parts=d_parts, row_idx=last, write_h=False)
-        return xl
+        return xl, h, d_parts
 
     def _prefill_attention(self, xn, lw, l, qkv, q, attn, posd, tsd, bt, cud, ctxd, work, T, xf=False):
         """qkv projection + RoPE + KV-cache append + causal attention of one prefill layer.  xf: xn and attn are

@@ -150,6 +150,12 @@ def numerics_class(runner, decode_batch: int) -> str:
     return "w8a8" if a8 or runner.kv_fp8 else "w8a16"
 
 
+def hidden_rel_max(cls: str, n_layers: int) -> float:
+    """The bound ``check_recorded`` puts on the mean relative L2 error of the final hidden state for numerics class
+    ``cls`` on a network of ``n_layers`` layers (TIED_THRESHOLDS: rel_c x sqrt(n_layers))."""
+    return round(TIED_THRESHOLDS[cls][1] * n_layers ** 0.5, 5)
+
+
 def spec_numerics_class(runner) -> str:
     """The threshold row of speculative decoding's verify rows: every projection weight-only
     (``ModelRunner.spec_oracle_plan``), so what ``numerics_class`` returns for a runner with no e4m3-activation
@@ -239,7 +245,7 @@ def check_recorded(eng, prompts, toks, elog, n_steps: int, check_rows: Sequence[
     pk, rel = torch.cat(pks), torch.cat(rels)
     pk_layer, rel_c = TIED_THRESHOLDS[cls]
     pk_max = round(pk_layer * nl, 6)
-    rel_max = round(rel_c * nl ** 0.5, 5)
+    rel_max = hidden_rel_max(cls, nl)
     res.update(tied_head=True, probe_kl=round(float(pk.mean()), 6), probe_kl_max=round(float(pk.max()), 6),
                hidden_rel_err=round(float(rel.mean()), 5), hidden_rel_err_max=round(float(rel.max()), 5))
     res["ok"] = bool(res["probe_kl"] < pk_max and res["hidden_rel_err"] < rel_max

@@ -1913,6 +1913,110 @@ def kv_shift8(kv: torch.Tensor, kv_scale: torch.Tensor, moves, cos: torch.Tensor
     ext().kv_shift8(kv, kv_scale, host.to(kv.device, non_blocking=True), cos, sin)
 
 
+# ----------------------------------------------------------------------------------- embeddings
+EMBED_MODES = {"mean": ref.EMBED_MEAN, "last": ref.EMBED_LAST}
+
+
+def _embed_host(name: str, cu, meta, host):
+    """(cu, meta) as host lists: ``host`` when the caller has them (the runner: no device read), else read from the
+    tensors (a synchronising read on the GPU; tests)."""
+    if host is not None:
+        cu_h, meta_h = host
+    else:
+        cu_h, meta_h = (cu.tolist() if cu is not None else None), meta.tolist()
+    if len(meta_h) != 5 or any(len(r) != len(meta_h[0]) for r in meta_h) or not len(meta_h[0]):
+        raise ValueError(f"{name}: meta is [5, n]: emode, estart, eslot, efinal, ecount per sequence")
+    return ([int(v) for v in cu_h] if cu_h is not None else None), [[int(v) for v in r] for r in meta_h]
+
+
+def _embed_check(name: str, cu_h, meta_h, T: Optional[int], nslots: Optional[int]) -> None:
+    """The value checks the three embedding ops share, made on the host before any launch: modes 0 / 1 / 2; for an
+    embedding sequence estart >= 0, efinal 0 / 1, ecount >= 1, 0 <= eslot < slots and no slot named twice (a second
+    workgroup would read what the first writes); cu non-decreasing from 0 to T."""
+    n = len(meta_h[0])
+    mode, start, slot, fin, count = meta_h
+    if any(m not in (0, 1, 2) for m in mode):
+        raise ValueError(f"{name}: emode must be 0 (none), 1 (mean) or 2 (last): {mode}")
+    on = [i for i in range(n) if mode[i]]
+    if any(start[i] < 0 or fin[i] not in (0, 1) or count[i] < 1 for i in on):
+        raise ValueError(f"{name}: estart >= 0, efinal 0 / 1 and ecount >= 1: {meta_h}")
+    if nslots is not None and any(not 0 <= slot[i] < nslots for i in on):
+        raise ValueError(f"{name}: eslot must satisfy 0 <= slot < {nslots}: {slot}")
+    if len({slot[i] for i in on}) != len(on):
+        raise ValueError(f"{name}: two embedding sequences of one call name one slot: {slot}")
+    if cu_h is not None and (len(cu_h) != n + 1 or cu_h[0] != 0 or cu_h[-1] != T or
+                             any(a > b for a, b in zip(cu_h, cu_h[1:]))):
+        raise ValueError(f"{name}: cu must be [n + 1], non-decreasing from 0 to T = {T}: {cu_h}")
+
+
+def _embed_operands(name: str, h, parts, cu, meta, rs):
+    if h.dim() != 2 or h.dtype != torch.float32 or h.shape[1] % 4 or not h.is_contiguous():
+        raise ValueError(f"{name}: h must be a contiguous f32 [T, D] tensor with D % 4 == 0")
+    if parts is not None:
+        if parts.dim() == 2:
+            parts = parts.unsqueeze(0)
+        if parts.dtype != torch.float32 or parts.dim() != 3 or tuple(parts.shape[1:]) != tuple(h.shape):
+            raise ValueError(f"{name}: parts must be f32 [np, T, D] slabs")
+    if meta.dtype != torch.int32 or meta.dim() != 2 or meta.shape[0] != 5 or cu.dtype != torch.int32 or \
+            cu.dim() != 1 or cu.numel() != meta.shape[1] + 1:
+        raise ValueError(f"{name}: meta must be int32 [5, n] and cu int32 [n + 1]")
+    if rs.dtype != torch.float32 or rs.dim() != 1 or rs.numel() < h.shape[0]:
+        raise ValueError(f"{name}: rs must be an f32 vector of at least T = {h.shape[0]} entries")
+    return parts
+
+
+def embed_rowscale(h: torch.Tensor, parts: Optional[torch.Tensor], tseq: torch.Tensor, cu: torch.Tensor,
+                   meta: torch.Tensor, eps: float, rs: torch.Tensor, host=None) -> None:
+    """Embeddings, step 1 (kernels/embed.hip): rs[t] = rsqrt(sum(v_t^2) / D + eps) for every row the pool visits, with
+    v_t = h[t] + parts[0][t] + ... left to right (the sum the final add_rmsnorm forms).  h [T, D] f32, parts None or
+    f32 [np, T, D], tseq [T] / cu [n + 1] / meta [5, n] int32 on h's device (meta rows: emode 0 none / 1 mean / 2 last,
+    estart, eslot, efinal, ecount).  ``host`` = (cu, meta) as host lists when the caller has them.  Everything is
+    checked before any launch."""
+    parts = _embed_operands("embed_rowscale", h, parts, cu, meta, rs)
+    if tseq.dtype != torch.int32 or tseq.dim() != 1 or tseq.numel() != h.shape[0]:
+        raise ValueError("embed_rowscale: tseq must be int32 [T]")
+    cu_h, meta_h = _embed_host("embed_rowscale", cu, meta, host)
+    _embed_check("embed_rowscale", cu_h, meta_h, h.shape[0], None)
+    if not _gpu(h):
+        return ref.embed_rowscale(h, parts, tseq, cu_h, meta_h, eps, rs)
+    ext().embed_rowscale(h, parts, tseq, cu, meta, float(eps), rs)
+
+
+def embed_pool(h: torch.Tensor, parts: Optional[torch.Tensor], cu: torch.Tensor, meta: torch.Tensor, rs: torch.Tensor,
+               gamma: torch.Tensor, acc: torch.Tensor, host=None) -> None:
+    """Embeddings, step 2: per embedding sequence a = +0 when estart == 0 else acc[eslot]; a = a + (v_t * rs[t]) * gamma
+    over the sequence's rows of this call in position order (every product and sum a rounded f32); acc[eslot] = a.  A
+    last-mode sequence stores the y of the last row of its efinal segment, and nothing from an earlier segment.  gamma
+    [D] bf16 (the final norm), acc [slots, D] f32.  The same bits as ``reference.embed_pool`` for the same rs, and
+    the same bits however the rows were split over calls."""
+    parts = _embed_operands("embed_pool", h, parts, cu, meta, rs)
+    if gamma.dtype != torch.bfloat16 or gamma.dim() != 1 or gamma.numel() != h.shape[1]:
+        raise ValueError("embed_pool: gamma must be the bf16 [D] norm weights")
+    if acc.dtype != torch.float32 or acc.dim() != 2 or acc.shape[1] != h.shape[1] or not acc.is_contiguous():
+        raise ValueError("embed_pool: acc must be a contiguous f32 [slots, D] tensor")
+    cu_h, meta_h = _embed_host("embed_pool", cu, meta, host)
+    _embed_check("embed_pool", cu_h, meta_h, h.shape[0], acc.shape[0])
+    if not _gpu(h):
+        return ref.embed_pool(h, parts, cu_h, meta_h, rs, gamma, acc)
+    ext().embed_pool(h, parts, cu, meta, rs, gamma, acc)
+
+
+def embed_finish(meta: torch.Tensor, acc: torch.Tensor, out: torch.Tensor, host=None) -> None:
+    """Embeddings, step 3, for the sequences with efinal: m = acc[eslot] / ecount (mean) or acc[eslot] (last);
+    out[eslot] = m / sqrt(sum(m^2)), zeros when the sum is 0.  The sum runs in a fixed order
+    (``reference.embed_finish`` reproduces its bits).  acc, out [slots, D] f32."""
+    if meta.dtype != torch.int32 or meta.dim() != 2 or meta.shape[0] != 5:
+        raise ValueError("embed_finish: meta must be int32 [5, n]")
+    if acc.dtype != torch.float32 or out.dtype != torch.float32 or acc.dim() != 2 or acc.shape != out.shape or \
+            not acc.is_contiguous() or not out.is_contiguous():
+        raise ValueError("embed_finish: acc and out must be contiguous f32 [slots, D] tensors of one shape")
+    _, meta_h = _embed_host("embed_finish", None, meta, (None, host[1]) if host is not None else None)
+    _embed_check("embed_finish", None, meta_h, None, acc.shape[0])
+    if not _gpu(acc):
+        return ref.embed_finish(meta_h, acc, out)
+    ext().embed_finish(meta, acc, out)
+
+
 def spec_draft(prompt_tok, prompt_len, out_tokens, gen_len, input_ids, positions, k, spec_ids, spec_pos, spec_draft_out,
                n_max: int = 3, n_min: int = 1, forced=None):
     """Prompt-lookup drafter, one row per entry of ``prompt_len`` (kernels/spec.hip).  forced [nf, k] int32 replaces

@@ -7,6 +7,7 @@ production: ``ops`` refuses to fall back when the extension is missing on a GPU 
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import struct
 
@@ -15,9 +16,32 @@ import torch
 BLOCK = 64  # tokens per KV-cache block (kernels assume 64)
 
 
+# Row-stable host prefill (``row_stable``): torch's CPU matmul sums a row's products in an order that depends on how
+# many rows the call has (below about 16 rows it takes another path), so a prompt's residual rows differ in their last
+# bits with the packing and the chunking of the call.  While the flag is set, ``linear`` multiplies one row at a time and
+# ``attn_prefill`` attends one query row at a time over exactly the keys it sees: every row is then computed by calls
+# whose shapes depend on that row alone.  The host prefill sets it for calls that pool embeddings (engine/runner.py),
+# whose vectors are then the same bits alone, packed or chunked; no other call changes.
+_ROW_STABLE = False
+
+
+@contextlib.contextmanager
+def row_stable(on: bool = True):
+    global _ROW_STABLE
+    old, _ROW_STABLE = _ROW_STABLE, bool(on) or _ROW_STABLE
+    try:
+        yield
+    finally:
+        _ROW_STABLE = old
+
+
 def linear(x: torch.Tensor, w: torch.Tensor, epi: str = "bf16", splitk: int = 1) -> torch.Tensor:
     """x [M,K] @ w[N,K]^T.  epi: bf16 | f32 | silu (w rows interleaved gate/up per 16)."""
-    y = x.float() @ w.float().t()
+    if _ROW_STABLE:
+        xf, wt = x.float(), w.float().t()
+        y = torch.cat([xf[i:i + 1] @ wt for i in range(xf.shape[0])]) if xf.shape[0] else xf @ wt
+    else:
+        y = x.float() @ w.float().t()
     if epi == "f32":
         return y
     if epi == "silu":
@@ -181,6 +205,13 @@ def attn_prefill(q, kc, vc, block_tables, cu_q, ctx_lens, H, Hkv, scale, out, kv
         k = _gather_kv(kc, block_tables[sq], n, ks).float().repeat_interleave(G, 0)
         v = _gather_kv(vc, block_tables[sq], n, vs).float().repeat_interleave(G, 0)
         qq = q[q0:q1].float().transpose(0, 1)  # [H, ql, D]
+        if _ROW_STABLE:  # one query row at a time over exactly its n - ql + r + 1 keys
+            for r in range(ql):
+                m = n - ql + r + 1
+                p = (torch.einsum("hqd,hnd->hqn", qq[:, r:r + 1], k[:, :m]) * scale).softmax(-1)
+                o = torch.einsum("hqn,hnd->hqd", p, v[:, :m])
+                out[q0 + r] = o[:, 0].to(out.dtype).view_as(out[q0 + r])
+            continue
         s = torch.einsum("hqd,hnd->hqn", qq, k) * scale
         qpos = torch.arange(n - ql, n, device=q.device).view(ql, 1)
         kpos = torch.arange(n, device=q.device).view(1, n)
@@ -628,6 +659,85 @@ def kv_shift8(kv, kv_scale, moves, cos_t, sin_t):
                 tile[:, :, lo:hi] = kv8_logical(kv[:, pl, src])[:, :, lo:hi]
                 kv[:, pl, dst] = kv8_physical(tile)
                 kv_scale[:, pl, dst, :, lo:hi] = kv_scale[:, pl, src, :, lo:hi]
+
+
+# ----------------------------------------------------------------------------------- embeddings
+EMBED_NONE, EMBED_MEAN, EMBED_LAST = 0, 1, 2
+EMBED_FINISH_LANES = 256  # threads of embed_finish_kernel: the partial sums its fixed-order reduction starts from
+
+
+def _embed_rows(cu, meta, i):
+    """(mode, start, slot, final, count, first row, end row) of sequence i; the rows are those the kernels visit: all of
+    a mean sequence, the last row of a final last-mode segment, none otherwise."""
+    mode, start, slot, fin, count = (int(meta[k][i]) for k in range(5))
+    r0, r1 = int(cu[i]), int(cu[i + 1])
+    if mode == EMBED_LAST:
+        r0 = r1 - 1 if fin else r1
+    elif mode != EMBED_MEAN:
+        r0 = r1
+    return mode, start, slot, fin, count, r0, r1
+
+
+def _embed_v(h, parts, t):
+    v = h[t].float()
+    return slab_sum(v, parts[:, t]) if parts is not None else v
+
+
+def embed_rowscale(h, parts, tseq, cu, meta, eps, rs):
+    """Host twin of embed_rowscale_kernel (csrc/kernels/embed.hip): rs[t] = rsqrt(sum(v_t^2) / D + eps) in f32 for
+    every pooled row t, v_t = h[t] + parts[0][t] + parts[1][t] + ... left to right; other entries of rs are not
+    written.  cu [n + 1] and meta [5, n] are host lists (or CPU tensors); ``tseq`` is implied by cu here."""
+    D = h.shape[1]
+    for i in range(len(cu) - 1):
+        *_, r0, r1 = _embed_rows(cu, meta, i)
+        for t in range(r0, r1):
+            v = _embed_v(h, parts, t)
+            rs[t] = torch.rsqrt((v * v).sum() / D + eps)
+
+
+def embed_pool(h, parts, cu, meta, rs, gamma, acc):
+    """Host twin of embed_pool_kernel: per embedding sequence a = +0 when estart == 0 else acc[slot]; then for its rows
+    of this call in position order a = a + (v_t * rs[t]) * gamma, every product and sum a rounded f32; acc[slot] = a.
+    A last-mode sequence stores the y of the last row of its final segment and nothing before it.  Bit for bit what the
+    kernel gives for the same rs."""
+    g = gamma.float()
+    for i in range(len(cu) - 1):
+        mode, start, slot, _, _, r0, r1 = _embed_rows(cu, meta, i)
+        if r0 >= r1:
+            continue
+        if mode == EMBED_LAST:
+            acc[slot] = (_embed_v(h, parts, r0) * rs[r0]) * g
+            continue
+        a = torch.zeros_like(acc[slot]) if start == 0 else acc[slot].clone()
+        for t in range(r0, r1):
+            a = a + (_embed_v(h, parts, t) * rs[t]) * g
+        acc[slot] = a
+
+
+def embed_finish(meta, acc, out):
+    """Host twin of embed_finish_kernel, for final sequences: m = acc[slot] / ecount (mean) or acc[slot] (last); ss =
+    sum(m^2) in the kernel's order (lane i of 256 sums columns i, i + 256, ... in order, then a halving tree over the
+    lanes); out[slot] = m / sqrt(ss), zeros when ss == 0.  ``meta`` [5, n] is a host list (or CPU tensor)."""
+    n, D, W = len(meta[0]), acc.shape[1], EMBED_FINISH_LANES
+    for i in range(n):
+        mode, slot, fin, count = int(meta[0][i]), int(meta[2][i]), int(meta[3][i]), int(meta[4][i])
+        if mode not in (EMBED_MEAN, EMBED_LAST) or not fin or count <= 0:
+            continue
+        m = acc[slot] / torch.tensor(float(count), dtype=torch.float32) if mode == EMBED_MEAN else acc[slot].clone()
+        sq = torch.zeros((D + W - 1) // W * W, dtype=torch.float32, device=acc.device)
+        sq[:D] = m * m
+        lanes = torch.zeros(W, dtype=torch.float32, device=acc.device)
+        for k in range(sq.numel() // W):
+            lanes = lanes + sq[k * W:(k + 1) * W]
+        w = W // 2
+        while w > 0:
+            lanes = lanes[:w] + lanes[w:2 * w]
+            w //= 2
+        tot = float(lanes[0])
+        # the correctly rounded f32 square root, as the kernel's sqrtf: the float64 root rounded to f32 (53 bits are more
+        # than the 2 * 24 + 2 that make the double rounding harmless); torch.sqrt on the CPU is off by an ulp now and then
+        nrm = torch.tensor(math.sqrt(tot), dtype=torch.float32)
+        out[slot] = torch.zeros_like(m) if tot == 0.0 else m / nrm
 
 
 # ----------------------------------------------------------------------------------- speculative decoding

@@ -23,7 +23,7 @@ from __future__ import annotations
 import json
 import os
 import time
-from typing import Optional
+from typing import Optional, Union
 
 from fastapi import FastAPI, HTTPException, Request
 from fastapi.responses import JSONResponse, PlainTextResponse, StreamingResponse
@@ -88,6 +88,15 @@ class ScoreRequest(BaseModel):
     completion: Optional[str] = None
     completions: Optional[list[str]] = None
     top_logprobs: int = 0
+    options: Optional[dict] = None
+
+
+class EmbedRequest(BaseModel):
+    """Ollama's ``/api/embed``: ``input`` is one text or a list of them; ``options`` may carry ``num_ctx`` and the
+    extension ``pooling`` ("last", the default, or "mean")."""
+    model: str
+    input: Union[str, list[str]] = ""
+    truncate: bool = True
     options: Optional[dict] = None
 
 
@@ -215,6 +224,19 @@ def create_app(ctx: Optional[AppContext] = None) -> FastAPI:
             raise HTTPException(501, "this backend does not score completions") from None
         REGISTRY.observe("lsa_request_seconds", time.perf_counter() - t0, "e2e latency", route="api_score")
         REGISTRY.inc("lsa_requests_total", 1, "requests", route="api_score", outcome="ok")
+        return out
+
+    @app.post("/api/embed")
+    def api_embed(req: EmbedRequest):
+        # what the engine refuses (no embeddings, TP > 1, an unknown pooling, no input or more than 64, an empty input,
+        # an over-long one with truncate false) is a SamplingOptionError: 400 through the handler above
+        t0 = time.perf_counter()
+        try:
+            out = ctx.backend.embed(req.model, req.input, req.truncate, req.options)
+        except NotImplementedError:
+            raise HTTPException(501, "this backend does not embed") from None
+        REGISTRY.observe("lsa_request_seconds", time.perf_counter() - t0, "e2e latency", route="api_embed")
+        REGISTRY.inc("lsa_requests_total", 1, "requests", route="api_embed", outcome="ok")
         return out
 
     @app.get("/api/tags")

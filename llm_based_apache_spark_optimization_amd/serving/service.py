@@ -37,7 +37,7 @@ def engine_factory(settings: Settings, tp_factory=None):
                            spec_batch=settings.spec_batch, spec_batch_sampled=settings.spec_batch_sampled,
                            spec_batch_guided=settings.spec_batch_guided, logprobs=settings.logprobs,
                            spec_logprobs=settings.spec_logprobs, context_shift=settings.context_shift,
-                           context_shift_fp8=settings.context_shift_fp8)
+                           context_shift_fp8=settings.context_shift_fp8, embeddings=settings.embeddings)
         if settings.spec_min_accept >= 0:
             eng.runner.spec_min_accept = settings.spec_min_accept
         return eng
