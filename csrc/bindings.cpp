@@ -163,6 +163,9 @@ int lsa_ar_run(float* data, long n, float* out, uint8_t* const* regions, int ran
 int lsa_fp4_gemm_ex(const void* X, int ldx, int M, int K, const void* Wq, const void* S, int N, void* out, int epi,
                     int nb, int splitk, int waves, int xfrag, const LsaEpi* ep, hipStream_t stream);
 int lsa_fp4_dequant(const void* Wq, const void* S, int N, int K, void* Wf, hipStream_t s);
+int lsa_q4_gemm_ex(const void* X, int ldx, int M, int K, const void* Wq, const void* D, int N, void* out, int epi,
+                   int nb, int splitk, int waves, int xfrag, const LsaEpi* ep, hipStream_t stream);
+int lsa_q4_dequant(const void* Wq, const void* D, int N, int K, void* Wf, hipStream_t s);
 int lsa_gemm_z12(const void* X, int M, int K, const void* lo, const void* hi, const void* esc, int base, int N,
                  void* out, int epi, int nb, int splitk, int waves, int div, const LsaEpi* ep, hipStream_t stream);
 }
@@ -681,6 +684,65 @@ void fp4_dequant(const at::Tensor& wq, const at::Tensor& sw, int64_t N, int64_t 
   need(wf, at::kBFloat16, "wf");
   TORCH_CHECK(wf.is_contiguous() && wf.numel() >= N * K, "fp4_dequant: output too small");
   check(lsa_fp4_dequant(wq.data_ptr(), sw.data_ptr(), N, K, wf.data_ptr(), cur_stream()), "fp4_dequant");
+}
+
+// GGUF Q4_0 weights (kernels/gemm_q4.hip, ops.pack_q4_0): wq [N/16, K/128, 64, 16] codes, dw [N/16, ceil(K/256), 64, 2]
+// f16 block scales.  The refusals of lsa_q4_gemm_ex (shape, row count, split-K with a non-f32 epilogue) are left to it:
+// a call it would refuse goes straight to it, it returns its code before any launch or memory access, and the code
+// surfaces as the exception.  The checks here are what it cannot see: dtypes, devices and buffer sizes.
+bool q4_launcher_refuses(int64_t M, int64_t N, int64_t K, int64_t epi, int64_t splitk) {
+  return N <= 0 || K <= 0 || N % 16 != 0 || K % 128 != 0 || M <= 0 || M > 64 || (epi != 1 && splitk > 1);
+}
+
+void check_q4(const at::Tensor& wq, const at::Tensor& dw, int64_t N, int64_t K) {
+  TORCH_CHECK(N > 0 && K > 0 && N % 16 == 0 && K % 128 == 0, "q4_0: N % 16 == 0, K % 128 == 0");
+  TORCH_CHECK(on_dev(wq) && wq.element_size() == 1 && wq.is_contiguous() && wq.numel() == N * K / 2,
+              "wq must be N*K/2 contiguous Q4_0 code bytes");
+  TORCH_CHECK(on_dev(dw) && dw.is_contiguous() &&
+                  dw.numel() * dw.element_size() == (N / 16) * ((K / 128 + 1) / 2) * 256,
+              "dw must be the [N/16, ceil(K/256), 64, 2] f16 block scales");
+}
+
+void q4_gemm(const at::Tensor& x, const at::Tensor& wq, const at::Tensor& dw, int64_t N, at::Tensor& out, int64_t epi,
+             int64_t nb, int64_t splitk, int64_t waves, const c10::optional<at::Tensor>& rowss, double eps) {
+  need(x, at::kBFloat16, "x");
+  TORCH_CHECK(x.dim() == 2 && x.stride(1) == 1, "x must be a row-major matrix");
+  const int64_t M = x.size(0), K = x.size(1);
+  TORCH_CHECK(epi >= 0 && epi <= 2, "q4_gemm: epilogue bf16 | f32 | silu");
+  if (q4_launcher_refuses(M, N, K, epi, splitk))
+    check(lsa_q4_gemm_ex(nullptr, 0, M, K, nullptr, nullptr, N, nullptr, epi, nb, splitk, waves, 0, nullptr, cur_stream()),
+          "q4_gemm");
+  check_q4(wq, dw, N, K);
+  check_out(epi, out, splitk, M, N, 0);
+  const EpiOpts eo = epi_opts(epi, M, N, K, rowss, eps, c10::nullopt, c10::nullopt, 0, c10::nullopt, c10::nullopt, N / 16);
+  check(lsa_q4_gemm_ex(x.data_ptr(), x.stride(0), M, K, wq.data_ptr(), dw.data_ptr(), N, out.data_ptr(), epi, nb, splitk,
+                       waves, 0, eo.on ? &eo.e : nullptr, cur_stream()),
+        "q4_gemm");
+}
+
+void q4_gemm_xf(const at::Tensor& xf, int64_t M, int64_t K, const at::Tensor& wq, const at::Tensor& dw, int64_t N,
+                at::Tensor& out, int64_t epi, int64_t nb, int64_t splitk, int64_t waves,
+                const c10::optional<at::Tensor>& rowss, double eps) {
+  need(xf, at::kBFloat16, "xf");
+  TORCH_CHECK(epi >= 0 && epi <= 2, "q4_gemm_xf: epilogue bf16 | f32 | silu");
+  if (q4_launcher_refuses(M, N, K, epi, splitk))
+    check(lsa_q4_gemm_ex(nullptr, 0, M, K, nullptr, nullptr, N, nullptr, epi, nb, splitk, waves, 1, nullptr, cur_stream()),
+          "q4_gemm_xf");
+  check_q4(wq, dw, N, K);
+  const int64_t mt = M <= 16 ? 1 : (M <= 32 ? 2 : 4);
+  TORCH_CHECK(xf.is_contiguous() && xf.numel() >= mt * 16 * K, "xf too small");
+  check_out(epi, out, splitk, M, N, mt);
+  const EpiOpts eo = epi_opts(epi, M, N, K, rowss, eps, c10::nullopt, c10::nullopt, 0, c10::nullopt, c10::nullopt, N / 16);
+  check(lsa_q4_gemm_ex(xf.data_ptr(), K, M, K, wq.data_ptr(), dw.data_ptr(), N, out.data_ptr(), epi, nb, splitk, waves,
+                       1, eo.on ? &eo.e : nullptr, cur_stream()),
+        "q4_gemm_xf");
+}
+
+void q4_dequant(const at::Tensor& wq, const at::Tensor& dw, int64_t N, int64_t K, at::Tensor& wf) {
+  check_q4(wq, dw, N, K);
+  need(wf, at::kBFloat16, "wf");
+  TORCH_CHECK(wf.is_contiguous() && wf.numel() >= N * K, "q4_dequant: output too small");
+  check(lsa_q4_dequant(wq.data_ptr(), dw.data_ptr(), N, K, wf.data_ptr(), cur_stream()), "q4_dequant");
 }
 
 void add_rmsnorm(at::Tensor& h, const c10::optional<at::Tensor>& parts, int64_t nparts, int64_t part_stride,
@@ -1798,6 +1860,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("rowss") = py::none(), py::arg("eps") = 1e-5, py::arg("h") = py::none(), py::arg("xout") = py::none(),
         py::arg("xmt") = 0, py::arg("ss_out") = py::none(), py::arg("tickets") = py::none());
   m.def("fp4_dequant", &fp4_dequant);
+  m.def("q4_gemm", &q4_gemm, py::arg("x"), py::arg("wq"), py::arg("dw"), py::arg("N"), py::arg("out"), py::arg("epi"),
+        py::arg("nb"), py::arg("splitk"), py::arg("waves") = 4, py::arg("rowss") = py::none(), py::arg("eps") = 1e-5);
+  m.def("q4_gemm_xf", &q4_gemm_xf, py::arg("xf"), py::arg("M"), py::arg("K"), py::arg("wq"), py::arg("dw"),
+        py::arg("N"), py::arg("out"), py::arg("epi"), py::arg("nb"), py::arg("splitk"), py::arg("waves") = 4,
+        py::arg("rowss") = py::none(), py::arg("eps") = 1e-5);
+  m.def("q4_dequant", &q4_dequant);
   m.def("fp8_gemm", &fp8_gemm, py::arg("x"), py::arg("wq"), py::arg("wscale"), py::arg("N"), py::arg("out"),
         py::arg("epi"), py::arg("nb"), py::arg("splitk"), py::arg("waves") = 4, py::arg("depth") = 1,
         py::arg("rowss") = py::none(), py::arg("eps") = 1e-5, py::arg("h") = py::none(), py::arg("xout") = py::none(), py::arg("xmt") = 0, py::arg("ss_out") = py::none(), py::arg("tickets") = py::none());

@@ -479,7 +479,23 @@ class EngineService(Backend):
                                 "context_shift": bool(getattr(lp.engine, "context_shift", False)),
                                 "context_shift_fp8": bool(getattr(lp.engine, "context_shift_fp8", False)),
                                 "embeddings": bool(getattr(lp.engine, "embeddings_supported", False)),
+                                **_weights_health(lp.engine),
                                 **lp.engine.stats} for m, lp in self._loops.items()}}
+
+
+def _weights_health(engine) -> dict:
+    """The weight kind an engine serves (the kind it was built for, on the CPU too) and, for a GGUF load, the file's
+    tensor count per ggml type."""
+    w = getattr(getattr(engine, "runner", None), "w", None)
+    if w is None:
+        return {}
+    pw = w.layers[0].wqkv
+    out = {"weight_kind": getattr(pw, "requested", None) or pw.kind}
+    src = getattr(w, "source", None)
+    if src:
+        out["checkpoint_format"] = src.get("format")
+        out["gguf_tensor_types"] = dict(src.get("tensor_types") or {})
+    return out
 
 
 # -------------------------------------------------------------------------------------- fake

@@ -40,7 +40,12 @@ class Settings:
     # engine: "hip" (MI355X engine), "fake" (deterministic test engine), "remote" (HTTP to another server)
     engine: str = dataclasses.field(default_factory=lambda: _env("ENGINE", "hip"))
     remote_url: str = dataclasses.field(default_factory=lambda: _env("REMOTE_URL", "http://127.0.0.1:8000"))
+    # checkpoints of the NL->SQL and the explain model: an HF directory (config.json + *.safetensors) or a GGUF file
+    # (an Ollama blob); unset = seeded random weights
     checkpoint_dir: Optional[str] = dataclasses.field(default_factory=lambda: _env("CHECKPOINT_DIR", None))
+    explain_checkpoint_dir: Optional[str] = dataclasses.field(
+        default_factory=lambda: _env("EXPLAIN_CHECKPOINT_DIR", None))
+    # weight kinds: "bf16" | "fp8" | "mxfp4" | "q4_0" (a GGUF file's own Q4_0 codes and scales, engine/factory.py)
     dtype: str = dataclasses.field(default_factory=lambda: _env("DTYPE", "bf16"))
     explain_dtype: str = dataclasses.field(default_factory=lambda: _env("EXPLAIN_DTYPE", "bf16"))
     # paged KV cache dtype of every engine: "bf16" | "fp8" (e4m3 rows + per-row scales, ops.KV_FP8)

@@ -1,4 +1,4 @@
-"""Build an LLMEngine for a named model (random-init or a checkpoint directory)."""
+"""Build an LLMEngine for a named model (random-init, a safetensors checkpoint directory or a GGUF file)."""
 from __future__ import annotations
 
 import time
@@ -7,7 +7,8 @@ from typing import Optional
 import torch
 
 from ..models import get_spec, tokenizer_for
-from ..models.llama import init_random, load_safetensors_dir
+from ..models.gguf import is_gguf
+from ..models.llama import init_random, load_gguf, load_safetensors_dir
 from .engine import LLMEngine
 from .runner import ModelRunner
 
@@ -25,7 +26,11 @@ def build_engine(model: str, device: Optional[str] = None, checkpoint: Optional[
                  spec_batch_guided: bool = False, logprobs: bool = False,
                  spec_logprobs: bool = False, context_shift: bool = False,
                  context_shift_fp8: bool = False, embeddings: bool = False) -> LLMEngine:
-    """kv_dtype: paged KV cache dtype, "bf16" | "fp8" (None: LSA_KV_FP8, default bf16).
+    """checkpoint: an HF directory (config.json + *.safetensors) or a GGUF file (recognised by its magic; Ollama blobs
+    carry no extension).  dtype: "bf16" | "fp8" | "mxfp4" | "q4_0"; "q4_0" serves a GGUF file's own Q4_0 codes and scales
+    (``models.llama.load_gguf`` has the rules), quantises by ggml's rule where there is no such file, runs at TP = 1
+    only (else bf16, with a warning) and takes plain steps whatever ``spec_tokens`` says.
+    kv_dtype: paged KV cache dtype, "bf16" | "fp8" (None: LSA_KV_FP8, default bf16).
     max_new_cap: generated-token cap per request (None: the context window).
     kv_reserve_tokens: generated tokens whose KV is reserved at admission (the rest grows lazily; < 0 reserves
     prompt + max_new up front).
@@ -76,7 +81,15 @@ def build_engine(model: str, device: Optional[str] = None, checkpoint: Optional[
         device = f"cuda:{torch.cuda.current_device()}" if torch.cuda.is_available() else "cpu"
     t0 = time.perf_counter()
     tpr, tps = (tp.rank, tp.size) if tp is not None else (0, 1)
-    if checkpoint:
+    if dtype == "q4_0" and tps > 1 and not (checkpoint and is_gguf(checkpoint)):
+        import warnings
+
+        warnings.warn(f"dtype q4_0 runs at tp = 1 only (tp = {tps}): loading as bf16")
+        dtype = "bf16"
+    if checkpoint and is_gguf(checkpoint):
+        w = load_gguf(checkpoint, device, kind=dtype, name=model, tp_rank=tpr, tp_size=tps)
+        tok = tokenizer_for(w.spec, checkpoint, (w.source or {}).get("tokenizer"))
+    elif checkpoint:
         w = load_safetensors_dir(checkpoint, device, kind=dtype, name=model, tp_rank=tpr, tp_size=tps)
         tok = tokenizer_for(w.spec, checkpoint)
     else:

@@ -6,8 +6,10 @@ Per layer: ``wqkv`` (fused q|k|v rows, column-parallel), ``wo`` (row-parallel), 
 
 Sources: seeded random init directly on the device (the benchmark path: the reference's models are
 Ollama GGUF blobs we cannot download), a HuggingFace-format state dict (``from_hf_state_dict``),
-or safetensors files (``load_safetensors_dir``).  ``kind='fp8'`` quantises every projection to
-e4m3fn with per-output-channel scales at load time (BASELINE config 5).
+safetensors files (``load_safetensors_dir``) or a GGUF file (``load_gguf``).  ``kind='fp8'`` quantises every
+projection to e4m3fn with per-output-channel scales at load time (BASELINE config 5); ``kind='q4_0'`` keeps a GGUF
+file's own Q4_0 codes and scales (or quantises by ggml's rule where there is no such file) and never folds the norm
+gammas: a gamma varies inside a 32-block, so folding it would mean quantising again.
 """
 from __future__ import annotations
 
@@ -18,6 +20,7 @@ import json
 import os
 from typing import Optional
 
+import numpy as np
 import torch
 
 from .. import ops
@@ -51,6 +54,7 @@ class LlamaWeights:
     lm_head: ops.PackedWeight  # [V / tp, d]
     tp_rank: int = 0
     tp_size: int = 1
+    source: Optional[dict] = None  # a GGUF load: {"format", "tensor_types": count per file type, "tokenizer": ...}
 
     @property
     def device(self) -> torch.device:
@@ -92,7 +96,8 @@ def pack_layer(spec: ModelSpec, wq, wk, wv, wo, wg, wu, wd, an, mn, rank=0, tp=1
     gu = ops.interleave_gate_up(_shard_rows(wg, rank, tp), _shard_rows(wu, rank, tp))
     wd_s = _shard_cols(wd, rank, tp)
     an, mn = an.to(torch.bfloat16), mn.to(torch.bfloat16)
-    if FOLD_NORMS:
+    fold = FOLD_NORMS and kind != "q4_0"
+    if fold:
         wqkv = (wqkv.float() * an.float()[None, :]).to(torch.bfloat16)
         gu = (gu.float() * mn.float()[None, :]).to(torch.bfloat16)
         an, mn = torch.ones_like(an), torch.ones_like(mn)
@@ -102,7 +107,7 @@ def pack_layer(spec: ModelSpec, wq, wk, wv, wo, wg, wu, wd, an, mn, rank=0, tp=1
 
     return LayerWeights(P(wqkv.contiguous(), kind), P(wo_s.contiguous(), kind), P(gu.contiguous(), kind),
                         P(wd_s.contiguous(), kind), an.contiguous(),
-                        mn.contiguous(), norms_folded=FOLD_NORMS)
+                        mn.contiguous(), norms_folded=fold)
 
 
 def init_random(spec: ModelSpec, device="cpu", seed: int = 0, kind: str = "bf16", std: float = 0.02,
@@ -185,6 +190,157 @@ def load_safetensors_dir(path: str, device="cpu", kind="bf16", name: Optional[st
     for fn in sorted(glob.glob(os.path.join(path, "*.safetensors"))):
         sd.update(load_file(fn))
     return from_hf_state_dict(spec, sd, device, kind, tp_rank, tp_size)
+
+
+# ----------------------------------------------------------------------------------- GGUF
+_GGUF_PROJ = ("attn_q", "attn_k", "attn_v", "attn_output", "ffn_gate", "ffn_up", "ffn_down")
+
+
+def _unpermute_rows(w: torch.Tensor, n_head: int) -> torch.Tensor:
+    """Undo the interleaved-rotary row order llama.cpp's converter stores q and k in (a row permutation, so it applies
+    to dense rows, Q4_0 code rows and their scale rows alike)."""
+    n, k = w.shape
+    hd = n // n_head
+    return w.reshape(n_head, hd // 2, 2, k).swapaxes(1, 2).reshape(n, k)
+
+
+def _gguf_spec(g, name: Optional[str], template: Optional[str]) -> ModelSpec:
+    """The served spec of a GGUF file: the named project spec, every dimension cross-checked against the metadata, or
+    -- an unknown name -- one built from the metadata alone (template raw unless given)."""
+    from . import gguf as G
+    from .spec import get_spec
+
+    dims = G.model_dims(g)
+    tied = "output.weight" not in g.tensors
+    try:
+        spec = get_spec(name) if name else None
+    except KeyError:
+        spec = None
+    if spec is not None:
+        for field, (key, val) in dims.items():
+            want = getattr(spec, field)
+            same = math.isclose(val, want, rel_tol=1e-3) if isinstance(want, float) else val == want
+            if not same:
+                raise ValueError(f"GGUF: {key}: the file has {field} = {val}, model {spec.name!r} has {want}")
+        if tied != spec.tie_embeddings:
+            raise ValueError(f"GGUF: output.weight: {'absent (tied embeddings)' if tied else 'present (untied)'} in the "
+                             f"file, model {spec.name!r} has tie_embeddings = {spec.tie_embeddings}")
+        return dataclasses.replace(spec, template=template) if template else spec
+    if "rope_freqs.weight" in g.tensors:
+        raise ValueError("GGUF: rope_freqs.weight: the file carries RoPE frequency factors and the model name "
+                         f"{name!r} is unknown, so their scaling rule is too")
+    md = g.metadata
+    eos = md.get("tokenizer.ggml.eos_token_id", 2)
+    return ModelSpec(
+        name=name or "gguf", tie_embeddings=tied, max_position=int(md.get("llama.context_length", 4096)),
+        bos_id=int(md.get("tokenizer.ggml.bos_token_id", 1)), eos_ids=(int(eos),), template=template or "raw",
+        **{field: val for field, (_, val) in dims.items()})
+
+
+def load_gguf(path: str, device="cpu", kind="bf16", name: Optional[str] = None, template: Optional[str] = None,
+              tp_rank=0, tp_size=1) -> LlamaWeights:
+    """Load a llama-architecture GGUF file, tensor by tensor: the raw bytes of one tensor go to ``device`` and are
+    dequantised there (models/gguf.py), so neither an f32 nor a bf16 copy of the model ever exists on the host.
+
+    ``kind='q4_0'`` at TP = 1 with all seven projection tensors of every layer stored as Q4_0 keeps their codes and
+    scales verbatim (``PackedWeight.from_q4_0``), gammas unfolded; ``output.weight`` is native too when it is Q4_0,
+    else a bf16 weight of its dequantised values; the embedding is always bf16.  If any projection is not Q4_0 (or
+    TP > 1, or a shape the Q4_0 kernels do not take) the whole model loads dequantised as bf16, with a warning.
+    Every other kind dequantises and packs through ``pack_layer``, folding included."""
+    import warnings
+
+    from . import gguf as G
+
+    dev = torch.device(device)
+    with G.GGUFFile(path) as g:
+        spec = _gguf_spec(g, name, template)
+        check_tp(spec, tp_size)
+        L = spec.n_layers
+        need = ["token_embd.weight", "output_norm.weight"]
+        for i in range(L):
+            need += [f"blk.{i}.{t}.weight" for t in _GGUF_PROJ + ("attn_norm", "ffn_norm")]
+        for n in need:
+            if n not in g.tensors:
+                raise ValueError(f"GGUF: required tensor {n!r} is missing")
+        hd = spec.head_dim
+        shapes = {"attn_q": (spec.n_heads * hd, spec.hidden), "attn_k": (spec.n_kv_heads * hd, spec.hidden),
+                  "attn_v": (spec.n_kv_heads * hd, spec.hidden), "attn_output": (spec.hidden, spec.n_heads * hd),
+                  "ffn_gate": (spec.ffn, spec.hidden), "ffn_up": (spec.ffn, spec.hidden),
+                  "ffn_down": (spec.hidden, spec.ffn), "attn_norm": (spec.hidden,), "ffn_norm": (spec.hidden,)}
+        for i in range(L):
+            for t, shp in shapes.items():
+                ti = g.tensors[f"blk.{i}.{t}.weight"]
+                if ti.shape != shp:
+                    raise ValueError(f"GGUF: ne of {ti.name!r}: shape {ti.shape} is not {shp}")
+        for n, shp in (("token_embd.weight", (spec.vocab_size, spec.hidden)), ("output_norm.weight", (spec.hidden,)),
+                       ("output.weight", (spec.vocab_size, spec.hidden))):
+            if n in g.tensors and g.tensors[n].shape != shp:
+                raise ValueError(f"GGUF: ne of {n!r}: shape {g.tensors[n].shape} is not {shp}")
+
+        native = kind == "q4_0"
+        if native:
+            why = None
+            if tp_size > 1:
+                why = f"tensor parallelism (tp = {tp_size})"
+            else:
+                for i in range(L):
+                    for t in _GGUF_PROJ:
+                        ti = g.tensors[f"blk.{i}.{t}.weight"]
+                        if why is None and ti.ggml_type != G.Q4_0:
+                            why = f"tensor {ti.name!r} is stored as {ti.type_name}"
+                        if why is None and (ti.shape[0] % 16 or ti.shape[1] % 128):
+                            why = f"tensor {ti.name!r} has shape {ti.shape} (rows % 16, columns % 128)"
+            if why is not None:
+                warnings.warn(f"GGUF {path}: dtype q4_0 needs every projection as Q4_0 at tp = 1; {why}: "
+                              "loading the whole model dequantised as bf16")
+                native, kind = False, "bf16"
+
+        def bf(n):  # one tensor: bytes to the device, f32 there, bf16 kept
+            return g.tensor_f32(n, dev).to(torch.bfloat16)
+
+        def q4(n):
+            ti = g.tensors[n]
+            codes, d = G.q4_0_split(torch.from_numpy(np.array(g.raw(n))).to(dev))
+            N, K = ti.shape
+            return codes.reshape(N, K), d.reshape(N, K // 32)
+
+        layers = []
+        for i in range(L):
+            p = f"blk.{i}."
+            an, mn = bf(p + "attn_norm.weight"), bf(p + "ffn_norm.weight")
+            if native:
+                cq, dq = (_unpermute_rows(t, spec.n_heads) for t in q4(p + "attn_q.weight"))
+                ck, dk = (_unpermute_rows(t, spec.n_kv_heads) for t in q4(p + "attn_k.weight"))
+                cv, dv = q4(p + "attn_v.weight")
+                cg, dg = q4(p + "ffn_gate.weight")
+                cu, du = q4(p + "ffn_up.weight")
+                layers.append(LayerWeights(
+                    ops.PackedWeight.from_q4_0(torch.cat([cq, ck, cv], 0).contiguous(), torch.cat([dq, dk, dv], 0).contiguous()),
+                    ops.PackedWeight.from_q4_0(*q4(p + "attn_output.weight")),
+                    ops.PackedWeight.from_q4_0(ops.interleave_gate_up(cg, cu).contiguous(),
+                                               ops.interleave_gate_up(dg, du).contiguous()),
+                    ops.PackedWeight.from_q4_0(*q4(p + "ffn_down.weight")),
+                    an.contiguous(), mn.contiguous(), norms_folded=False))
+            else:
+                layers.append(pack_layer(
+                    spec, _unpermute_rows(bf(p + "attn_q.weight"), spec.n_heads),
+                    _unpermute_rows(bf(p + "attn_k.weight"), spec.n_kv_heads), bf(p + "attn_v.weight"),
+                    bf(p + "attn_output.weight"), bf(p + "ffn_gate.weight"), bf(p + "ffn_up.weight"),
+                    bf(p + "ffn_down.weight"), an, mn, tp_rank, tp_size, kind))
+        embed = bf("token_embd.weight").contiguous()
+        out = g.tensors.get("output.weight")
+        if native and out is not None and out.ggml_type == G.Q4_0 and out.shape[0] % 16 == 0:
+            lm_head = ops.PackedWeight.from_q4_0(*q4("output.weight"))
+        else:
+            head = embed if out is None else bf("output.weight")
+            lm_head = ops.PackedWeight.from_dense(_shard_rows(head, tp_rank, tp_size).contiguous(),
+                                                  "bf16" if native else kind)
+            if tp_size == 1:
+                lm_head.add_z12()
+        source = {"format": f"gguf v{g.version}", "tensor_types": g.type_counts(),
+                  "tokenizer": G.tokenizer_dict(g.metadata)}
+        return LlamaWeights(spec, embed, layers, bf("output_norm.weight").contiguous(), lm_head, tp_rank, tp_size,
+                            source=source)
 
 
 @torch.no_grad()

@@ -84,6 +84,14 @@ class HFTokenizer:
         self.bos_id = bos_id if bos_id is not None else (self._sp.bos_id() if self._sp else 1)
         self.eos_ids = tuple(eos_ids) or ((self._sp.eos_id(),) if self._sp else (2,))
 
+    @classmethod
+    def from_tokenizer(cls, tk, bos_id: int = 1, eos_ids: Sequence[int] = (2,)) -> "HFTokenizer":
+        """Wrap an already built ``tokenizers.Tokenizer`` (a GGUF file's vocabulary, ``tokenizer_from_gguf``)."""
+        self = cls.__new__(cls)
+        self._sp, self._tk = None, tk
+        self.bos_id, self.eos_ids = bos_id, tuple(eos_ids) or (2,)
+        return self
+
     def encode(self, text: str, add_bos: bool = True) -> list[int]:
         if self._tk is not None:
             ids = self._tk.encode(text, add_special_tokens=False).ids
@@ -103,11 +111,51 @@ LLAMA3_SPECIALS = ("<|begin_of_text|>", "<|start_header_id|>", "<|end_header_id|
 MISTRAL_SPECIALS = ("[INST]", "[/INST]")
 
 
-def tokenizer_for(spec: ModelSpec, path: Optional[str] = None):
+def _sp_merges(tokens, scores) -> list:
+    """The BPE merges of a SentencePiece vocabulary that carries only scores (Llama-2 GGUF files), as "left right"
+    strings, best first: the rule of transformers' GGUF tokenizer skeleton, with set lookups (its list lookups take
+    minutes at 32k pieces)."""
+    rank = {t: i for i, t in enumerate(tokens)}
+    score = {t: scores[i] for i, t in enumerate(tokens)}
+    merges = []
+    for piece, sc in score.items():
+        local = [(piece[:i], piece[i:]) for i in range(1, len(piece)) if piece[:i] in rank and piece[i:] in rank]
+        local.sort(key=lambda lr: (score[lr[0]], score[lr[1]]), reverse=True)
+        merges.extend((l, r, sc) for l, r in local if " " not in l and " " not in r)
+    merges.sort(key=lambda m: m[2], reverse=True)
+    return [f"{l} {r}" for l, r, _ in merges]
+
+
+def tokenizer_from_gguf(spec: ModelSpec, tokdict: dict) -> HFTokenizer:
+    """The tokenizer a GGUF file describes in its ``tokenizer.ggml.*`` metadata (models/gguf.py tokenizer_dict),
+    built by transformers' GGUF converter of the llama architecture: a ``llama`` (SentencePiece-style, scores) or a
+    ``gpt2`` (byte-level BPE, merges) vocabulary."""
+    from transformers.integrations.ggml import convert_gguf_tokenizer  # lazy: only GGUF loads without tokenizer files
+
+    td = dict(tokdict)
+    kind = td.get("tokenizer_type")
+    if kind == "llama" and "merges" not in td and "scores" in td:
+        td["merges"] = _sp_merges(td["tokens"], td["scores"])
+    tk, _ = convert_gguf_tokenizer("llama", td)  # the architecture's converter reads tokenizer_type itself
+    return HFTokenizer.from_tokenizer(tk, spec.bos_id, spec.eos_ids)
+
+
+def tokenizer_for(spec: ModelSpec, path: Optional[str] = None, gguf_tokenizer: Optional[dict] = None):
     # a checkpoint directory with its tokenizer files: the real tokenizer; weights-only directories
-    # fall back to the byte tokenizer below
+    # fall back to the byte tokenizer below.  A GGUF file: tokenizer files beside it first, else the vocabulary in its
+    # own metadata (``gguf_tokenizer``); a vocabulary that cannot be built falls back too, with a warning
+    if path and os.path.isfile(path):
+        path = os.path.dirname(os.path.abspath(path))
     if path and any(os.path.exists(os.path.join(path, f)) for f in ("tokenizer.json", "tokenizer.model")):
         return HFTokenizer(path, spec.bos_id, spec.eos_ids)
+    if gguf_tokenizer:
+        try:
+            return tokenizer_from_gguf(spec, gguf_tokenizer)
+        except Exception as e:  # noqa: BLE001 - any converter failure: the load goes on with the byte tokenizer
+            import warnings
+
+            warnings.warn(f"GGUF tokenizer ({gguf_tokenizer.get('tokenizer_type')!r}) could not be built "
+                          f"({type(e).__name__}: {e}); falling back to the byte tokenizer")
     specials = LLAMA3_SPECIALS if spec.template == "llama3" else MISTRAL_SPECIALS if spec.template == "mistral" else ()
     tok = ByteTokenizer(spec.vocab_size, bos_id=spec.bos_id if spec.bos_id < spec.vocab_size else 1,
                         eos_ids=[e for e in spec.eos_ids if e < spec.vocab_size] or [2], specials=specials)

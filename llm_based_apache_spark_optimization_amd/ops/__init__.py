@@ -191,6 +191,74 @@ def dequantize_mxfp4(wq: torch.Tensor, sw: torch.Tensor, N: int, K: int) -> torc
     return (vals.view(N, K // 32, 32) * scale[..., None]).view(N, K)
 
 
+# GGUF Q4_0 (ggml block_q4_0): 32 consecutive k share one f16 scale d, elements are 4-bit codes q.  The value rule of
+# every consumer (csrc/kernels/gemm_q4.hip, dequantize_q4_0): w = bf16_rne(f32(d) * f32(q - 8)); the f32 product is
+# exact (11 significand bits x 4), so the one rounding is the one to bf16.
+def _check_q4_shape(N: int, K: int) -> None:
+    if N <= 0 or K <= 0 or N % 16 or K % 128:
+        raise ValueError(f"q4_0 weights need N % 16 == 0 and K % 128 == 0, got N = {N}, K = {K}")
+
+
+def quantize_q4_0(w: torch.Tensor):
+    """[N, K] -> (codes uint8 [N, K] in 0..15, d f16 [N, K/32]) by ggml's reference rule, in f32: per block of 32,
+    max = the first element of largest magnitude (with its sign), d = max / -8, id = 1 / d (0 for d = 0),
+    q = min(15, trunc(x * id + 8.5)); d is stored as f16."""
+    N, K = w.shape
+    if K % 32:
+        raise ValueError(f"q4_0 blocks are 32 wide, got K = {K}")
+    x = w.float().reshape(N, K // 32, 32)
+    a = x.abs()
+    pos = torch.arange(32, device=x.device)
+    first = torch.where(a == a.amax(-1, keepdim=True), pos, pos.new_full((), 32)).amin(-1, keepdim=True)
+    d = x.gather(-1, first.clamp(max=31)).squeeze(-1) / -8.0
+    inv = torch.where(d != 0, 1.0 / d, torch.zeros_like(d))
+    q = ((x * inv[..., None]) + 8.5).to(torch.int32).clamp(max=15)
+    return q.to(torch.uint8).reshape(N, K), d.to(torch.float16)
+
+
+def q4_0_values(codes: torch.Tensor, d: torch.Tensor) -> torch.Tensor:
+    """The value rule on plain (codes [N, K], d [N, K/32]): bf16 [N, K]."""
+    N, K = codes.shape
+    v = d.float()[..., None] * (codes.reshape(N, K // 32, 32).float() - 8.0)
+    return v.to(torch.bfloat16).reshape(N, K)
+
+
+def pack_q4_0(codes: torch.Tensor, d: torch.Tensor):
+    """codes [N, K], d f16 [N, K/32] -> the gemm_q4 layouts: Wq [N/16, K/128, 64 lanes, 16 B] (lane = 16 g + r holds
+    W[16 nb + r][128 kb + 32 g .. + 31], one Q4_0 block; byte 4 s + i = element 8 s + i in the low nibble, element
+    8 s + 4 + i in the high one) and D f16 [N/16, ceil(K/256), 64, 2] (the lane's d of two consecutive 128-k steps in
+    one word)."""
+    N, K = codes.shape
+    _check_q4_shape(N, K)
+    if tuple(d.shape) != (N, K // 32) or d.dtype != torch.float16 or codes.dtype != torch.uint8:
+        raise ValueError(f"pack_q4_0: codes uint8 [N, K] and d f16 [N, K/32], got {codes.dtype} {tuple(codes.shape)}, "
+                         f"{d.dtype} {tuple(d.shape)}")
+    c = codes.reshape(N, K // 8, 2, 4)
+    packed = (c[:, :, 0] | (c[:, :, 1] << 4)).reshape(N, K // 2)
+    kb = K // 128
+    wq = packed.view(N // 16, 16, kb, 4, 16).permute(0, 2, 3, 1, 4).reshape(N // 16, kb, 64, 16).contiguous()
+    kb2 = (kb + 1) // 2
+    dl = d.reshape(N // 16, 16, kb, 4).permute(0, 2, 3, 1).reshape(N // 16, kb, 64)
+    dp = torch.zeros(N // 16, kb2 * 2, 64, dtype=torch.float16, device=codes.device)
+    dp[:, :kb] = dl
+    return wq, dp.view(N // 16, kb2, 2, 64).permute(0, 1, 3, 2).contiguous()
+
+
+def unpack_q4_0(wq: torch.Tensor, dw: torch.Tensor, N: int, K: int):
+    """The inverse of ``pack_q4_0``: (codes uint8 [N, K], d f16 [N, K/32])."""
+    _check_q4_shape(N, K)
+    kb = K // 128
+    p = wq.reshape(N // 16, kb, 4, 16, 16).permute(0, 3, 1, 2, 4).reshape(N, K // 8, 4)
+    codes = torch.stack([p & 15, p >> 4], dim=2).reshape(N, K)
+    dl = dw.reshape(N // 16, -1, 64, 2).permute(0, 1, 3, 2).reshape(N // 16, -1, 64)[:, :kb]
+    return codes, dl.reshape(N // 16, kb, 4, 16).permute(0, 3, 1, 2).reshape(N, K // 32)
+
+
+def dequantize_q4_0(wq: torch.Tensor, dw: torch.Tensor, N: int, K: int) -> torch.Tensor:
+    """The exact values the gemm_q4 kernels multiply with, from the packed layout, as f32: the value rule."""
+    return q4_0_values(*unpack_q4_0(wq, dw, N, K)).float()
+
+
 # "z12": the bf16 values of a weight as a lossless 12-bit stream for the 17-32-row decode GEMM (csrc/kernels/gemm_z12.hip
 # documents the format).  The exponents of a weight matrix sit in a handful of binades, so per tensor one window of 8
 # consecutive values of exp[7:1] (16 binades) covers all but ~1e-4 of the elements; those are patched exactly from a
@@ -273,7 +341,7 @@ class PackedWeight:
 
     N: int
     K: int
-    kind: str  # "dense" (CPU reference) | "bf16" (fragment layout) | "fp8" | "mxfp4"
+    kind: str  # "dense" (CPU reference) | "bf16" (fragment layout) | "fp8" | "mxfp4" | "q4_0"
     data: torch.Tensor
     scale: Optional[torch.Tensor] = None
     requested: Optional[str] = None  # "dense" only: the kind the weight was packed for (the CPU keeps every kind dense)
@@ -289,6 +357,9 @@ class PackedWeight:
     @staticmethod
     def from_dense(w: torch.Tensor, kind: str = "bf16") -> "PackedWeight":
         N, K = w.shape
+        if kind == "q4_0":  # the CPU keeps the quantised-then-dequantised values: the GPU engine's numerics class
+            _check_q4_shape(N, K)
+            return PackedWeight.from_q4_0(*quantize_q4_0(w))
         if not w.is_cuda:
             return PackedWeight(N, K, "dense", w.to(torch.bfloat16).contiguous(), None, kind)
         if kind == "fp8":
@@ -300,6 +371,16 @@ class PackedWeight:
         wb = w.to(torch.bfloat16)
         return PackedWeight(N, K, "bf16", shuffle_weight(wb))
 
+    @staticmethod
+    def from_q4_0(codes: torch.Tensor, d: torch.Tensor) -> "PackedWeight":
+        """Q4_0 codes uint8 [N, K] and block scales f16 [N, K/32] taken verbatim (a GGUF tensor's own)."""
+        N, K = codes.shape
+        _check_q4_shape(N, K)
+        if not codes.is_cuda:
+            return PackedWeight(N, K, "dense", q4_0_values(codes, d).contiguous(), None, "q4_0")
+        wq, dw = pack_q4_0(codes, d)
+        return PackedWeight(N, K, "q4_0", wq, dw)
+
     def dense(self) -> torch.Tensor:
         if self.kind == "dense":
             return self.data
@@ -307,6 +388,8 @@ class PackedWeight:
             return unshuffle_weight(self.data, self.N, self.K)
         if self.kind == "mxfp4":
             return dequantize_mxfp4(self.data, self.scale, self.N, self.K).to(torch.bfloat16)
+        if self.kind == "q4_0":
+            return q4_0_values(*unpack_q4_0(self.data, self.scale, self.N, self.K))
         return dequantize_fp8(self.data, self.scale, self.N, self.K).to(torch.bfloat16)
 
     @property
@@ -367,12 +450,15 @@ def pick_gemm_config(M: int, N: int, K: int, epi: str, xf: bool = False,
     """(nb, splitk, waves, div) for a decode GEMM: the tuning table when it has the shape (entries
     measured with fragment-major activations carry a ':xf' suffix, fp8-weight entries ':fp8'), else
     the heuristic below (div 4, 4-wave workgroups won most measured shapes)."""
-    if kind == "mxfp4":  # W4A16 decode GEMM (gemm_fp4.hip): its own sweep entries (scripts/bench_fp4_decode.py)
+    if kind in ("mxfp4", "q4_0"):  # W4A16 decode GEMM (gemm_fp4.hip): its own sweep entries (scripts/bench_fp4_decode.py);
+        # Q4_0 (gemm_q4.hip) looks under ':q4' and, without an entry, takes the same heuristic: the same byte stream
+        # per lane and the same MFMA count
         b = 1
         while b < M:
             b *= 2
-        e = _tuning_table().get(f"{N}x{K}:{epi}:b{b}:fp4") or _tuning_table().get(
-            f"{N}x{K}:{'f32' if epi == 'res' else epi}:b{b}:fp4")
+        sfx = "fp4" if kind == "mxfp4" else "q4"
+        e = _tuning_table().get(f"{N}x{K}:{epi}:b{b}:{sfx}") or _tuning_table().get(
+            f"{N}x{K}:{'f32' if epi == 'res' else epi}:b{b}:{sfx}")
         if e is not None and M <= 64:
             return e["nb"], e["splitk"], e["waves"], 4
         nbt = N // 16
@@ -723,6 +809,10 @@ def linear(x: torch.Tensor, w: PackedWeight, epi: str = "bf16", out: Optional[to
             e.fp8_gemm_t256(x8, sx, w.data, w.scale, w.N, out, EPI[epi], splitk)
     elif w.kind == "mxfp4":  # W4A16 decode GEMM, e2m1 -> bf16 in registers (v_cvt_scalef32_pk_bf16_fp4)
         e.fp4_gemm(x, w.data, w.scale, w.N, out, EPI[epi], nb, splitk, waves, **kw)
+    elif w.kind == "q4_0":  # GGUF Q4_0 decode GEMM, codes -> bf16 in registers by the value rule (gemm_q4.hip)
+        if res is not None:
+            raise ValueError("q4_0 weights have no residual epilogue")
+        e.q4_gemm(x, w.data, w.scale, w.N, out, EPI[epi], nb, splitk, waves, **kw)
     else:
         raise ValueError(f"weight kind {w.kind} on GPU")
     return out
@@ -734,7 +824,7 @@ FP8_W8A8 = os.environ.get("LSA_FP8_W8A8", "1") != "0"
 def tile_weight(w: PackedWeight, device) -> Optional[torch.Tensor]:
     """The bf16 fragment-layout weight the stream-K route of ``linear`` (M > 64) multiplies by, for a caller that runs
     several such products over ``w`` back to back and passes it on as ``linear(..., wf=)``: the weight itself (bf16),
-    one dequantisation into the stream's scratch (MXFP4; fp8 where the W8A8 tile kernel does not apply), or None where
+    one dequantisation into the stream's scratch (MXFP4, Q4_0; fp8 where the W8A8 tile kernel does not apply), or None where
     that route is not taken (CPU, W8A8 fp8).  Valid until the next dequantisation on the same stream."""
     if torch.device(device).type != "cuda" or (w.kind == "fp8" and FP8_W8A8 and w.K % 128 == 0):
         return None
@@ -754,6 +844,8 @@ def _dequant_scratch(w: PackedWeight, device) -> torch.Tensor:
         _dq_scratch[key] = buf
     if w.kind == "mxfp4":
         ext().fp4_dequant(w.data, w.scale, w.N, w.K, buf)
+    elif w.kind == "q4_0":
+        ext().q4_dequant(w.data, w.scale, w.N, w.K, buf)
     else:
         ext().fp8_dequant(w.data, w.scale, w.N, w.K, buf)
     return buf[: w.N * w.K]
@@ -835,7 +927,7 @@ def linear_xf(xf: torch.Tensor, M: int, w: PackedWeight, epi: str = "bf16", out:
     ``z12``: the caller allows the 12-bit weight stream (gemm_z12.hip) where the weight has one and 16 < M <= 32; same
     values, same summation order, fewer bytes.  A weight without it (not compressible) runs the bf16 kernel, as does
     a shape whose ':z12' tuning entry says "off" (measured slower) unless the call names its own ``nb``."""
-    if not _gpu(xf) or w.kind not in ("bf16", "fp8", "mxfp4"):
+    if not _gpu(xf) or w.kind not in ("bf16", "fp8", "mxfp4", "q4_0"):
         if epi != "silu":
             return linear(from_xfrag(xf, M, w.K), w, epi, out, splitk, nb, waves, div, rownorm, res, _xf=True)
         y = to_xfrag(linear(from_xfrag(xf, M, w.K), w, epi, None, splitk, nb, waves, div, rownorm))
@@ -873,6 +965,10 @@ def linear_xf(xf: torch.Tensor, M: int, w: PackedWeight, epi: str = "bf16", out:
         ext().fp8_gemm_xf(xf, M, w.K, w.data, w.scale, w.N, out, EPI[epi], nb, splitk, waves, _fp8_depth(div), **kw)
     elif w.kind == "mxfp4":
         ext().fp4_gemm_xf(xf, M, w.K, w.data, w.scale, w.N, out, EPI[epi], nb, splitk, waves, **kw)
+    elif w.kind == "q4_0":
+        if res is not None:
+            raise ValueError("q4_0 weights have no residual epilogue")
+        ext().q4_gemm_xf(xf, M, w.K, w.data, w.scale, w.N, out, EPI[epi], nb, splitk, waves, **kw)
     else:
         ext().gemm_xf(xf, M, w.K, w.data, w.N, out, EPI[epi], nb, splitk, waves, div, **kw)
     return out

@@ -25,7 +25,9 @@ def engine_factory(settings: Settings, tp_factory=None):
         log.info("building engine %s (%s, max_batch=%d, tp=%d)", model, dtype, settings.max_batch,
                  tp.size if tp is not None else 1)
         # two models co-serve one GPU: each engine's KV arena takes a share of the memory free at its build
-        eng = build_engine(model, checkpoint=settings.checkpoint_dir if model == settings.nl2sql_model else None,
+        ckpt = settings.checkpoint_dir if model == settings.nl2sql_model else (
+            settings.explain_checkpoint_dir if model == settings.explain_model else None)
+        eng = build_engine(model, checkpoint=ckpt,
                            dtype=dtype, max_slots=settings.max_batch, max_model_len=settings.max_model_len,
                            kv_memory_fraction=settings.kv_memory_fraction, warm_graphs=True, tp=tp,
                            prefill_chunk=settings.prefill_chunk, kv_dtype=settings.kv_dtype,

@@ -2,9 +2,9 @@
 
     python scripts/gemm_resource_table.py [CSRC_KERNELS_DIR] > table.txt
 
-Compiles the five decode-GEMM files for the device only, with the package's kernel flags, and prints one line per
+Compiles the six decode-GEMM files for the device only, with the package's kernel flags, and prints one line per
 kernel (sorted): kernel<template arguments>, VGPRs, AGPRs, SGPRs, scratch bytes per lane, occupancy (waves per SIMD),
-LDS bytes per block; a file's decode kernel is named by the file (gemm, z12, fp8, fp4, fp8a).  Two tables (two trees)
+LDS bytes per block; a file's decode kernel is named by the file (gemm, z12, fp8, fp4, fp8a, q4).  Two tables (two trees)
 are compared with diff; no GPU is needed.
 """
 import re
@@ -17,7 +17,7 @@ REPO = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(REPO))
 from llm_based_apache_spark_optimization_amd.ops.build import ARCH, HIPCC  # noqa: E402
 
-FILES = ["gemm", "gemm_z12", "gemm_fp8", "gemm_fp4", "gemm_fp8a"]
+FILES = ["gemm", "gemm_z12", "gemm_fp8", "gemm_fp4", "gemm_fp8a", "gemm_q4"]
 FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast", "-Wno-unused-result"]
 KEYS = {"VGPRs": "vgpr", "AGPRs": "agpr", "TotalSGPRs": "sgpr", "ScratchSize [bytes/lane]": "scratch",
         "Occupancy [waves/SIMD]": "occ", "LDS Size [bytes/block]": "lds"}
